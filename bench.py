@@ -23,7 +23,15 @@ OUTPUT: stdout carries exactly ONE line -- a compact JSON record (< 4 KB: the he
 {us, frac} pair per side leg under "legs").  Everything else (full roofline blocks of the legs, clocks, spreads, notes) goes to
 `bench_detail.json` beside this script and to stderr.
 
-Modes (--mode picks the headline `value`; the Gym-cadence legs run by default, the rest with --all-legs)
+A plain run (`--gpus 1 --steps K --warmup W`) times the headline and nothing else: set-up, pre-warm + W warm-up steps, the K timed
+steps, the result line.  Everything else the benchmark measures -- the side legs below, the heterogeneous fleet, the general path,
+the CPU baseline, the per-round spread and the per-kernel durations of the headline, the device clocks -- runs with --full (which
+--all-legs and --legs imply).  `--dump-outputs DIR` writes what the timed path returned in its last step (the [K, N] outputs of the
+last min(launches per step, 4) rounds, at a fixed seeded sample of grids) as DIR/<name>.npy: the pre-warm runs by wall time, so the
+step counter and the state are restored behind it and the W + K steps start from the same row and state, with the same actions, in
+every run.
+
+Modes (--mode picks the headline `value`; with --full the Gym-cadence legs run too, the rest with --all-legs)
   fused (default)  parameters and state stay in registers for the 64 steps of a round, actions / series rows / per-step
                    outputs (reward, done, SoC) stream.  The rank's grids are stepped as --shards (2) contiguous ranges on
                    the engine's internal HIP streams (mgx_set_shards): ranges are not joined between rounds, so one range's
@@ -42,6 +50,7 @@ Launch:  python bench.py [--gpus N --steps K --warmup W]      N > 1 without WORL
 """
 import argparse
 import json
+import math
 import os
 import socket
 import subprocess
@@ -61,6 +70,8 @@ SIDE_ROUNDS = (192, 64)    # (timed, warm-up) rounds of the modes that are not t
 LAT_FLOOR_US = 1.7         # launch boundary of a kernel that cannot overlap its predecessor (MI355X_MICROARCH.md: 1.5-1.9 us)
 LAT_STREAM_GBS = 6000.0    # ... and the rate at which its one dependent round trip then moves (what the chip sustains)
 MAX_LINE = 4096            # the compact stdout record stays below this (tests/test_bench_contract.py)
+DUMP_BYTES = 48 << 20      # --dump-outputs: bytes written over all ranks (the grid sample shrinks to fit)
+DUMP_SEED = 20240607       # --dump-outputs: seed of the grid sample
 
 
 def parse(argv=None):
@@ -112,11 +123,22 @@ def parse(argv=None):
                     help="where the full record goes (the stdout line is the compact one); '' = nowhere")
     ap.add_argument("--launch-check", action="store_true",
                     help="only bring the N ranks up, check the process group and the metrics all-reduce, print {n_gpus: N} (no GPU work)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything that is not the headline: the side legs, the heterogeneous fleet, the general path, "
+                         "the CPU baseline, the headline's per-round spread and kernel durations, the device clocks (implied by "
+                         "--all-legs and --legs).  Off: the run times the headline only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the outputs of the headline's last timed step (a fixed seeded sample of grids, <= 64 MB) as DIR/<name>.npy")
     args = ap.parse_args(argv)
     if args.grids is None:
         args.grids = 100_000 if args.config == 2 else 125_000
     if args.config == 4 and args.hetero_steps <= 0:
         ap.error("--config 4 reports the heterogeneous fleet: --hetero-steps must be > 0")
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.dump_outputs and args.config == 4:
+        ap.error("--dump-outputs writes the outputs of the Template-4 headline (--config 2 / 3)")
+    args.full = args.full or args.all_legs or args.legs is not None
     return args
 
 
@@ -162,6 +184,7 @@ class Runner:
         self.rbc_table = table_array(lists)
         self.rbc_ids = torch.from_numpy(default_priority_ids(eng.batch, lists, remove_redundant_gensets=False)).to(dev)
         self.rounds = 0            # rounds issued since the process started (per mode runner)
+        self.state0 = eng.batch.state()        # charge / SoC / genset status before the first step (restart())
         self.env = None            # a BatchedMicrogridEnv around self.eng (the step_env leg)
         self.act_views = None
         self.streams = []
@@ -179,6 +202,19 @@ class Runner:
             self.env.reset()
         else:
             self.eng.reset(want_obs=False)
+
+    def restart(self):
+        """Back to the first row with the state the batch started with (a reset moves the step counter only, as the reference's)."""
+        self.eng.batch.load_state(self.state0)
+        self.reset()
+
+    def last_outputs(self, rounds, names, grid_index):
+        """What the last `rounds` rounds returned (<= OUT_SETS: older ones are overwritten), at the grids `grid_index`, in issue
+        order, on the host: {name: [rounds x chunk, len(grid_index)] float64}."""
+        assert rounds <= OUT_SETS
+        idx = torch.as_tensor(grid_index, dtype=torch.long, device=self.eng.device)
+        sets = [self.outs[r % OUT_SETS] for r in range(self.rounds - rounds, self.rounds)]
+        return {n: torch.cat([o[n].index_select(1, idx) for o in sets]).to(torch.float64).cpu().numpy() for n in names}
 
     def _room(self):
         if self.eng.current_step + self.chunk > self.eng.layout.final_step:
@@ -339,7 +375,7 @@ def timed(run, fn, rounds, device, mdist, per_round=False):
     return t1 - t0, max(e0.elapsed_time(e1) for e0, e1 in ev) * 1e-3, round_us
 
 
-def hetero_gym_steps(N, dev, rank, world, steps, mdist, rows, series, uniform, all_legs=False, K_ring=32):
+def hetero_gym_steps(N, dev, rank, world, steps, mdist, rows, series, uniform, all_legs=False, K_ring=32, dtypes=("float64", "float32")):
     """BASELINE configs[4] per GPU: a heterogeneous fleet (1/3 genset+battery, 1/3 battery+grid, 1/3 genset+battery+grid;
     forecast_horizon = 24, T = `rows`) stepped through the Gym surface WITH observations, under both observation contracts:
       rows   step() returns the [N, D] rows (D = 56 / 152 / 156): written ahead in rings of 16 row blocks, the step adds the
@@ -359,6 +395,8 @@ def hetero_gym_steps(N, dev, rank, world, steps, mdist, rows, series, uniform, a
     for contract_name in (("rows", "rows_rowmajor", "views") if all_legs else ("rows",)):
         contract = "rows" if contract_name.startswith("rows") else "views"
         for dt_name, dt in (("float64", torch.float64), ("float32", torch.float32)):
+            if dt_name not in dtypes:
+                continue
             name = f"{dt_name}_{contract_name}"
             batches = [generate(per * world, n_steps=rows, seed=43 + k, arch=arch, horizon=24, device=dev, rank=rank,
                                 world=world, series=series, uniform_columns=uniform) for k, arch in enumerate(archs)]
@@ -1009,7 +1047,7 @@ def main():
 
     device_state = {}
 
-    def measure(mode, sharded, rounds, warmup, series=None, run=None, spread=False):
+    def measure(mode, sharded, rounds, warmup, series=None, run=None, spread=False, capture=None):
         run = run or runner(series or args.series)
         eng, S = run.eng, run.S
         sharded = sharded and S > 1
@@ -1025,7 +1063,7 @@ def main():
         r0 = run.rounds
         run.eng.fork()
         sampler = None
-        if mode == args.mode and not device_state and rank == 0:      # the headline's pre-warm: what the device runs at under this load
+        if args.full and mode == args.mode and not device_state and rank == 0:      # the headline's pre-warm: what the device runs at under this load
             sampler = sample_device_state(device_state)
         t_end = time.perf_counter() + args.prewarm
         while time.perf_counter() < t_end:
@@ -1034,9 +1072,19 @@ def main():
                 run.eng.join(); torch.cuda.synchronize(dev); run.eng.fork(); r0 = run.rounds
         if sampler is not None:
             sampler.join(2.0)
+        # the pre-warm runs by wall time: pad it to a whole cycle of the action pool / output sets and restart behind it, so that the
+        # W warm-up and K timed rounds start from the same row and state with the same actions in every run (join / fork order the
+        # restored state behind the pre-warm's last round and ahead of the next one on the device: the host does not wait, the
+        # device does not idle)
+        fn(-run.rounds % math.lcm(run.pool.shape[0], OUT_SETS))
+        run.eng.join()
+        run.restart()
+        run.eng.fork()
         fn(warmup)
         first = run.rounds
         wall, gpu, _ = timed(run, fn, rounds, dev, mdist)
+        if capture is not None:                                    # before anything else steps this runner again
+            capture.update(run.last_outputs(min(LPS, OUT_SETS), capture.pop("names"), capture.pop("grid_index")))
         # the spread of a timed region: a second pass directly behind it, with an event behind every round on every launch stream
         # (inside the timed region itself the extra host calls would be part of what is measured)
         round_us = timed(run, fn, min(rounds, 256), dev, mdist, per_round=True)[2] if spread else None
@@ -1108,7 +1156,7 @@ def main():
                 roof["launch"] = (f"every env-step = {S} launches of {n_launch} grids, one per shard stream, each shard's dependent chain "
                                   f"issued by a host thread of its own (mgx_set_launch_threads): a range's step k + 1 waits for its own "
                                   f"step k only; open loop (actions staged ahead), joined once behind the timed region")
-        if mode in ("fused", "rbc", "fused_rich"):
+        if mode in ("fused", "rbc", "fused_rich") and args.full:
             roof["kernel_avg_duration_us"] = run.kernel_durations_us(fn)
         if mode == "rbc" and fact:
             roof["note"] = ("with factorised series this kernel reads nothing per step (18.5 B/env-step are its reward / SoC writes): "
@@ -1129,8 +1177,22 @@ def main():
                 "roofline": roof, "roofline_valu": roof_valu, "per_rank_env_steps_per_s": [N * rounds * chunk / w for w in walls]}
 
     # the headline first (its launch indices in a rocprofv3 trace are then [prewarm + W x LPS, prewarm + (W + K) x LPS) per queue)
+    capture = None
+    if args.dump_outputs:
+        # a fixed seeded sample of the rank's grids: DUMP_BYTES over all ranks, rows = the kept rounds x chunk per output
+        names = ["reward"] + (["soc_trace"] if args.mode in ("fused", "rbc") and L.has_battery else [])
+        per_grid = len(names) * min(LPS, OUT_SETS) * chunk * 8
+        n_dump = max(1, min(N, DUMP_BYTES // (per_grid * world)))
+        grid_index = np.sort(np.random.default_rng(DUMP_SEED).choice(N, n_dump, replace=False))
+        capture = {"names": names, "grid_index": grid_index}
     results = {args.mode: measure(args.mode, sharded=args.mode in ("fused", "rbc"), rounds=args.steps * LPS, warmup=args.warmup * LPS,
-                                  spread=True)}
+                                  spread=args.full, capture=capture)}
+    if capture is not None:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        suffix = f"_rank{rank}" if world > 1 else ""
+        for name, arr in capture.items():
+            np.save(os.path.join(args.dump_outputs, f"{name}{suffix}.npy"), arr)
+        np.save(os.path.join(args.dump_outputs, f"grid_index{suffix}.npy"), grid_index.astype(np.float64))
 
     def guarded(what, fn):
         """The side legs must not take the headline down with them: a failure is reported in the record instead.  With several
@@ -1147,7 +1209,7 @@ def main():
         return out if err is None else {"error": err}
 
     side = (min(args.steps * LPS, SIDE_ROUNDS[0]), min(args.warmup * LPS, SIDE_ROUNDS[1]))
-    if not args.no_side_modes:
+    if args.full and not args.no_side_modes:
         # the Gym cadence: single-step launches issued by one C call, and the Gym surface itself from a Python loop
         legs_only = [x for x in args.legs.split(",") if x] if args.legs is not None else None
 
@@ -1206,17 +1268,18 @@ def main():
 
     # The GENERAL path: 2 gensets + 2 batteries + 1 grid per microgrid (module_container.py:355-413 allows any multiplicity)
     general = None
-    if not args.no_side_modes and (args.legs is None or "general" in args.legs.split(",")):
+    if args.full and not args.no_side_modes and (args.legs is None or "general" in args.legs.split(",")):
         general = guarded("general_path_2g2b1grid", lambda: general_path_leg(args, N, n_total, chunk, dev, rank, world, mdist))
         torch.cuda.empty_cache()
 
     hetero = None
-    if args.hetero_steps > 0:
+    if args.hetero_steps > 0 and (args.full or args.config == 4):     # (--config 4: the fleet is the headline)
         # --config 4: the fleet IS the job -- `--steps` bench steps of `chunk` fleet Gym steps each are what the head reports
         fleet_steps = args.steps * chunk if args.config == 4 else args.hetero_steps
         hetero = guarded("hetero_h24_gym_steps", lambda: hetero_gym_steps(N, dev, rank, world, fleet_steps, mdist, args.rows,
                                                                           args.series, args.series == "factorised" and args.uniform_columns,
-                                                                          all_legs=args.all_legs, K_ring=args.fleet_ring))
+                                                                          all_legs=args.all_legs, K_ring=args.fleet_ring,
+                                                                          dtypes=("float64", "float32") if args.full else ("float64",)))
 
     # metrics vector: episode-return sum + mean SoC, all-reduced over ranks (the ONLY collective; RCCL over xGMI)
     local_sums = eng.metrics(torch.stack([run.outs[0]["reward"][-1], batch.cols["soc"]]))
@@ -1225,7 +1288,7 @@ def main():
     mdist.barrier()
 
     cpu = None
-    if rank == 0 and not args.no_cpu_baseline:      # rank 0 only; for N > 1 a shorter sample while the other ranks wait
+    if rank == 0 and args.full and not args.no_cpu_baseline:      # rank 0 only; for N > 1 a shorter sample while the other ranks wait
         try:
             cpu = cpu_baseline(eng, run.pool, args.cpu_seconds if world == 1 else min(args.cpu_seconds, 4.0))
         except Exception as e:          # noqa: BLE001  (a host without gcc / OpenMP must not cost the GPU numbers)

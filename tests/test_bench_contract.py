@@ -7,6 +7,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -97,10 +98,48 @@ def test_gpus_mismatch_fails_loudly():
     assert r.returncode != 0 and "--gpus 2" in (r.stdout + r.stderr)
 
 
+def test_full_is_off_by_default_and_implied_by_the_leg_options():
+    sys.path.insert(0, ROOT)
+    import bench
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert not a.full and a.steps == 7 and a.warmup == 2 and a.dump_outputs is None
+    assert bench.parse(["--full"]).full and bench.parse(["--all-legs"]).full and bench.parse(["--legs", "step"]).full
+    assert bench.parse(["--dump-outputs", "out"]).dump_outputs == "out"
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_headline_only_and_dumps_the_same_outputs_every_time(device, tmp_path):
+    """A plain run: the headline's K timed steps and the line, no side legs, no CPU baseline.  --dump-outputs writes what the last
+    timed step returned at a fixed grid sample, and two runs whose wall-time pre-warms differ write the same arrays."""
+    dumps = []
+    for j, prewarm in enumerate(("0.05", "0.3")):
+        det, out = str(tmp_path / f"detail{j}.json"), tmp_path / f"out{j}"
+        args = [a if a != "0.05" else prewarm for a in SMALL]
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--detail", det, "--dump-outputs", str(out)] + args,
+                           capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        d = _line(r.stdout)
+        assert KEYS <= set(d) and d["steps"] == 3 and d["ms_per_step"] > 0 and d["legs"] == {} and d["cpu_baseline"] is None
+        assert abs(d["value"] - 20000 * 3 * 64 / (d["ms_per_step"] * 3e-3)) < 1e-6 * d["value"]
+        assert d["roofline"]["launches"] == 3 * 2
+        full = json.load(open(det))
+        assert "round_us" not in full["roofline"] and full["hetero_h24_gym_steps"] is None and full["general_path_2g2b1grid"] is None
+        files = sorted(os.listdir(out))
+        assert files == ["grid_index.npy", "reward.npy", "soc_trace.npy"], files
+        arrs = {f: np.load(out / f) for f in files}
+        assert sum(a.nbytes for a in arrs.values()) <= 64 << 20
+        assert all(a.dtype == np.float64 for a in arrs.values())
+        assert arrs["reward.npy"].shape == arrs["soc_trace.npy"].shape == (2 * 32, 20000) and np.isfinite(arrs["reward.npy"]).all()
+        dumps.append(arrs)
+    for f in dumps[0]:
+        assert np.array_equal(dumps[0][f], dumps[1][f]), f
+
+
 @pytest.mark.gpu
 def test_bench_one_rank_json_line(device, tmp_path):
     det = str(tmp_path / "detail.json")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--detail", det] + SMALL, capture_output=True, text=True, timeout=600)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--detail", det] + SMALL, capture_output=True, text=True,
+                       timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _line(r.stdout)
     assert KEYS <= set(d) and d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 1 and d["value"] > 0
@@ -135,7 +174,7 @@ def test_bench_one_rank_json_line(device, tmp_path):
 
 @pytest.mark.gpu
 def test_bench_all_legs_still_one_short_line(device, tmp_path):
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--all-legs", "--no-cpu-baseline", "--detail", str(tmp_path / "d.json")] + SMALL,
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--all-legs", "--no-cpu-baseline", "--detail", str(tmp_path / "d.json")] + SMALL,
                        capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _line(r.stdout)
@@ -149,7 +188,7 @@ def test_bench_all_legs_still_one_short_line(device, tmp_path):
 def test_bench_two_ranks_self_launched(device):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(MGX_DIST_BACKEND="gloo", MGX_FORCE_LOCAL_RANK="0")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--no-side-modes"] + SMALL
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--no-side-modes"] + SMALL
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     d = _line(r.stdout)

@@ -398,45 +398,24 @@ def test_gym_flat_order_layout():
     assert list(M.obs_slices()) == ["load", "pv", "genset", "battery", "grid"] and M.obs_dim == L.obs_dim == 24
 
 
-@pytest.mark.refcheck
 def test_reference_flat_observation_under_a_key_sorting_dict_is_the_gym_order():
     """The reference builds gym.spaces.Dict(obs_space) from a plain dict (envs/base/base.py:128-163) and flattens observations
     through it (:211-223); gym <= 0.26 / gymnasium SORT the keys of such a Dict.  With a Dict that does what gym does, the
-    reference's own flat observation == the nested observation concatenated in BatchLayout(flat_order="gym") order."""
-    import _refenv
-    if not _refenv.reference_available():
-        pytest.skip("reference not present")
-    from collections import OrderedDict
+    reference's own flat observation == the nested observation concatenated in BatchLayout(flat_order="gym") order
+    (tests/golden/gym_order.npz: both observations as the reference computed them, make_gym_order_goldens.py)."""
+    import json
 
-    class SortingDict(_refenv.Dict):                       # gym/spaces/dict.py: OrderedDict(sorted(spaces.items())) for a plain dict
-        def __init__(self, spaces=None, seed=None, **kw):
-            super().__init__(spaces, seed, **kw)
-            self.spaces = OrderedDict(sorted(self.spaces.items()))
-    _refenv.import_reference()
-    import gym
-    from pymgrid.envs import DiscreteMicrogridEnv
+    from conftest import golden
     from pymgrid_amd import BatchLayout
-    old = gym.spaces.Dict
-    import pymgrid.envs.base.base as base_mod
-    old_base = base_mod.Dict
-    try:
-        gym.spaces.Dict = base_mod.Dict = SortingDict
-        for n in (0, 1, 2):
-            nested_env = DiscreteMicrogridEnv.from_scenario(n)
-            nested_env._flat_spaces = False
-            flat_env = DiscreteMicrogridEnv.from_scenario(n)
-            np.random.seed(n)
-            o_n, o_f = nested_env.reset(), flat_env.reset()
-            names = {k for k in ("genset", "battery", "grid") if k in o_n}
-            L = BatchLayout(n_grids=1, n_steps=8760, horizon=23, has_genset="genset" in names, has_battery="battery" in names,
-                            has_grid="grid" in names, flat_order="gym")
-            for k in range(5):
-                expect = np.concatenate([np.asarray(o_n[name][0], dtype=np.float64) for name in L.obs_slices()])
-                assert o_f.shape == (L.obs_dim,) and np.array_equal(np.asarray(o_f, dtype=np.float64), expect), (n, k)
-                a = k % flat_env.action_space.n
-                o_n, o_f = nested_env.step(a)[0], flat_env.step(a)[0]
-    finally:
-        gym.spaces.Dict, base_mod.Dict = old, old_base
+    z = golden("gym_order.npz")
+    for n in (0, 1, 2):
+        names = set(json.loads(str(z[f"n{n}_keys"])))
+        L = BatchLayout(n_grids=1, n_steps=8760, horizon=23, has_genset="genset" in names, has_battery="battery" in names,
+                        has_grid="grid" in names, flat_order="gym")
+        for k in range(5):
+            expect = np.concatenate([z[f"n{n}_k{k}_{name}"] for name in L.obs_slices()])
+            o_f = z[f"n{n}_k{k}_flat"]
+            assert o_f.shape == (L.obs_dim,) and np.array_equal(o_f, expect), (n, k)
 
 
 @pytest.mark.gpu

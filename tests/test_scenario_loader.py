@@ -1,14 +1,16 @@
 """Scenario loader: the reference's !Microgrid YAML + csv.gz files -> parameter dicts.
-Needs the reference's data directory, so it only runs in the build container."""
+The tests that read the reference's data directory or import the reference itself only run in the build container; the
+round trips through this repo's own dump and loader run everywhere."""
 import os
 
 import numpy as np
 import pytest
 
 REF_SCENARIOS = "/root/reference/src/pymgrid/data/scenario"
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF_SCENARIOS), reason="reference data files not present")
+needs_reference = pytest.mark.skipif(not os.path.isdir(REF_SCENARIOS), reason="reference data files not present")
 
 
+@needs_reference
 def test_yaml_loader_equals_reference_loader(pymgrid25):
     """All 25 pymgrid25 scenarios: the parameter dict read from YAML + csv.gz by this repo's loader equals the one
     extracted from Microgrid.from_scenario(n) by the reference (fixture pymgrid25_inputs.npz), bit for bit."""
@@ -75,6 +77,7 @@ def test_dump_and_load_round_trip(pymgrid25, tmp_path):
                 assert p[k] == v, (n, k, p[k], v)
 
 
+@needs_reference
 def test_the_reference_loads_what_we_dump(pymgrid25, tmp_path):
     """Microgrid.load(<file written by dump_scenario_yaml>) in the real reference == the scenario it came from."""
     import sys
@@ -158,6 +161,7 @@ def test_multi_instance_scenarios_round_trip(tmp_path):
     assert len(bucket_by_layout(all_p)) == len(all_p)          # every module mix is a layout of its own
 
 
+@needs_reference
 def test_scenario_features_the_reference_serialises(tmp_path):
     """What round 5's loader refused and Microgrid.load (microgrid.py:848-908) accepts, both directions against the REAL reference:
     a trajectory function, modules built with raise_errors=True, time-series modules with forecast horizons of their own, a

@@ -1,7 +1,7 @@
 #!/bin/bash
 # GPU: rule-based rollout timing (bench --mode rbc) + SQ instruction counters of rollout_kernel
 for rep in 1 2; do
-python bench.py --gpus 1 --mode rbc --steps 64 --warmup 16 --no-side-modes --no-cpu-baseline --hetero-steps 0 --shards 1 2>/dev/null | python -c "
+python bench.py --full --gpus 1 --mode rbc --steps 64 --warmup 16 --no-side-modes --no-cpu-baseline --hetero-steps 0 --shards 1 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); r=d['roofline']
 print('rbc one stream: %.2f us per 64-step launch  frac %.3f  %.2f G env-steps/s' % (r['avg_launch_us'], r['frac'], d['value']/1e9))"

@@ -7,9 +7,9 @@ TAG=$1; shift
 OUT=$REPO/gpurun_out/pmc_$TAG
 mkdir -p "$OUT"; export TMPDIR=/tmp; cd /tmp
 ARGS="--steps 32 --warmup 8 --no-cpu-baseline --hetero-steps 0 --no-side-modes $*"     # rounds of 64 env-steps, the headline mode only
-timeout 300 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_INSTS_VMEM SQ_WAVES --kernel-trace -d "$OUT/sq" -o b --output-format csv -- python "$REPO/bench.py" $ARGS > "$OUT/sq.log" 2>&1
-timeout 300 rocprofv3 --pmc SQ_INSTS_LDS SQ_WAIT_INST_LDS SQ_ACTIVE_INST_LDS SQ_INSTS_SALU SQ_INSTS_SMEM SQ_BUSY_CYCLES --kernel-trace -d "$OUT/sq2" -o b --output-format csv -- python "$REPO/bench.py" $ARGS > "$OUT/sq2.log" 2>&1
-timeout 300 rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum TCC_EA0_RDREQ_sum TCC_EA0_WRREQ_sum --kernel-trace -d "$OUT/tcc" -o b --output-format csv -- python "$REPO/bench.py" $ARGS > "$OUT/tcc.log" 2>&1
+timeout 300 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_INSTS_VMEM SQ_WAVES --kernel-trace -d "$OUT/sq" -o b --output-format csv -- python "$REPO/bench.py" --full $ARGS > "$OUT/sq.log" 2>&1
+timeout 300 rocprofv3 --pmc SQ_INSTS_LDS SQ_WAIT_INST_LDS SQ_ACTIVE_INST_LDS SQ_INSTS_SALU SQ_INSTS_SMEM SQ_BUSY_CYCLES --kernel-trace -d "$OUT/sq2" -o b --output-format csv -- python "$REPO/bench.py" --full $ARGS > "$OUT/sq2.log" 2>&1
+timeout 300 rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum TCC_EA0_RDREQ_sum TCC_EA0_WRREQ_sum --kernel-trace -d "$OUT/tcc" -o b --output-format csv -- python "$REPO/bench.py" --full $ARGS > "$OUT/tcc.log" 2>&1
 cd "$REPO"
 python - "$OUT" <<'PY' | tee "$OUT/summary.txt"
 import csv, glob, os, re, sys

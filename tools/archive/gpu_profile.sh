@@ -11,10 +11,10 @@ mkdir -p "$OUT"
 export TMPDIR=/tmp
 cd /tmp
 ARGS="${*:---gpus 1 --steps 20 --warmup 5}"
-timeout 600 rocprofv3 --kernel-trace --stats -d "$OUT/stats" -o bench --output-format csv -- python "$REPO/bench.py" $ARGS > "$OUT/stats.log" 2> "$OUT/stats.err"
+timeout 600 rocprofv3 --kernel-trace --stats -d "$OUT/stats" -o bench --output-format csv -- python "$REPO/bench.py" --full $ARGS > "$OUT/stats.log" 2> "$OUT/stats.err"
 PMCARGS="$ARGS --no-cpu-baseline --hetero-steps 0 --no-closed-loop"
-timeout 600 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d "$OUT/pmc_fetch" -o bench --output-format csv -- python "$REPO/bench.py" $PMCARGS > "$OUT/pmc_fetch.log" 2>&1
-timeout 600 rocprofv3 --pmc WRITE_SIZE --kernel-trace -d "$OUT/pmc_write" -o bench --output-format csv -- python "$REPO/bench.py" $PMCARGS > "$OUT/pmc_write.log" 2>&1
+timeout 600 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d "$OUT/pmc_fetch" -o bench --output-format csv -- python "$REPO/bench.py" --full $PMCARGS > "$OUT/pmc_fetch.log" 2>&1
+timeout 600 rocprofv3 --pmc WRITE_SIZE --kernel-trace -d "$OUT/pmc_write" -o bench --output-format csv -- python "$REPO/bench.py" --full $PMCARGS > "$OUT/pmc_write.log" 2>&1
 cd "$REPO"
 python tools/summarize_profile.py "$OUT" > "$OUT/summary.txt" 2>&1
 # stamp the workload the counters belong to (bench.py only reports `traffic` for a matching launch shape)

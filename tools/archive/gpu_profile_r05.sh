@@ -17,10 +17,10 @@ cd /tmp
 HASH=$(cd "$REPO" && python -c "from pymgrid_amd import _lib; print(_lib.built_hash() or _lib.source_hash())")
 echo "csrc_hash $HASH" > "$OUT/csrc_hash.txt"
 ARGS="--gpus 1 --steps 20 --warmup 5"
-timeout 600 rocprofv3 --kernel-trace --stats -d "$OUT/stats" -o bench --output-format csv -- python "$REPO/bench.py" $ARGS --detail "$OUT/bench_detail.json" > "$OUT/stats.log" 2> "$OUT/stats.err"
+timeout 600 rocprofv3 --kernel-trace --stats -d "$OUT/stats" -o bench --output-format csv -- python "$REPO/bench.py" --full $ARGS --detail "$OUT/bench_detail.json" > "$OUT/stats.log" 2> "$OUT/stats.err"
 PMCARGS="$ARGS --no-cpu-baseline --hetero-steps 0 --no-closed-loop --detail $OUT/bench_detail_pmc.json"
-timeout 600 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d "$OUT/pmc_fetch" -o bench --output-format csv -- python "$REPO/bench.py" $PMCARGS > "$OUT/pmc_fetch.log" 2>&1
-timeout 600 rocprofv3 --pmc WRITE_SIZE --kernel-trace -d "$OUT/pmc_write" -o bench --output-format csv -- python "$REPO/bench.py" $PMCARGS > "$OUT/pmc_write.log" 2>&1
+timeout 600 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d "$OUT/pmc_fetch" -o bench --output-format csv -- python "$REPO/bench.py" --full $PMCARGS > "$OUT/pmc_fetch.log" 2>&1
+timeout 600 rocprofv3 --pmc WRITE_SIZE --kernel-trace -d "$OUT/pmc_write" -o bench --output-format csv -- python "$REPO/bench.py" --full $PMCARGS > "$OUT/pmc_write.log" 2>&1
 cd "$REPO"
 python tools/summarize_profile.py "$OUT" > "$OUT/summary.txt" 2>&1
 python - "$OUT/traffic.json" "$HASH" <<'PY'
@@ -35,7 +35,7 @@ PY
 cd /tmp
 SQARGS="--gpus 1 --steps 4 --warmup 1 --no-cpu-baseline --hetero-steps 0 --no-side-modes --no-closed-loop --detail /dev/null"
 for MODE in fused rbc; do
-  timeout 300 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES --kernel-trace -d "$OUT/sq_$MODE" -o b --output-format csv -- python "$REPO/bench.py" $SQARGS --mode $MODE > "$OUT/sq_$MODE.log" 2>&1
+  timeout 300 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES --kernel-trace -d "$OUT/sq_$MODE" -o b --output-format csv -- python "$REPO/bench.py" --full $SQARGS --mode $MODE > "$OUT/sq_$MODE.log" 2>&1
 done
 cd "$REPO"
 python - "$OUT" "$HASH" <<'PY'

@@ -7,7 +7,7 @@ mkdir -p "$(dirname "$OUT")"
 : > "$OUT"
 cd "$REPO"
 for HS in 256 2048 256 2048; do
-  timeout 600 python bench.py --no-cpu-baseline --no-side-modes --no-closed-loop --hetero-steps $HS 2>/dev/null | python -c "
+  timeout 600 python bench.py --full --no-cpu-baseline --no-side-modes --no-closed-loop --hetero-steps $HS 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); h=d['hetero_h24_gym_steps']
 print('hetero-steps $HS:', '  '.join(f\"{k} {v['us_per_step']:.2f} us ({v['roofline']['frac']:.3f})\" for k,v in h.items() if isinstance(v,dict) and 'roofline' in v))" >> "$OUT"

@@ -9,7 +9,7 @@ timeout 900 python -m pytest tests/test_multi_windows.py tests/test_ring_layout.
 : > "$OUT/exp_refill_col_packs.txt"
 for cfg in 0 1 0 1 1; do
 export MGX_WIN_PAIRS=$cfg
-timeout 600 python bench.py --gpus 1 --no-cpu-baseline --detail /dev/null 2> /dev/null | python -c "
+timeout 600 python bench.py --full --gpus 1 --no-cpu-baseline --detail /dev/null 2> /dev/null | python -c "
 import json, sys
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('packs=$cfg', {k: v['us'] for k, v in d['legs'].items() if k.startswith('config5') or k.startswith('general_gym')})" | tee -a "$OUT/exp_refill_col_packs.txt"

@@ -7,7 +7,7 @@ mkdir -p "$OUT"
 cd "$REPO"
 for j in a b; do
   SECONDS=0
-  python bench.py --gpus 1 --steps 20 --warmup 5 --detail "$OUT/bench_detail_final_$j.json" > "$OUT/bench_driver_cmd_final_$j.json" 2> "$OUT/bench_driver_cmd_final_$j.err"
+  python bench.py --full --gpus 1 --steps 20 --warmup 5 --detail "$OUT/bench_detail_final_$j.json" > "$OUT/bench_driver_cmd_final_$j.json" 2> "$OUT/bench_driver_cmd_final_$j.err"
   echo "rc $? length $(wc -c < "$OUT/bench_driver_cmd_final_$j.json") wall $SECONDS s"
   cat "$OUT/bench_driver_cmd_final_$j.json"
 done

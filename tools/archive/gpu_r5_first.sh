@@ -9,7 +9,7 @@ cd "$REPO"
 python -c "from pymgrid_amd import _lib; print('csrc_hash', _lib.built_hash() or _lib.source_hash())" > "$OUT/csrc_hash.txt"
 timeout 900 python -m pytest tests -m gpu -q --maxfail=20 -p no:cacheprovider > "$OUT/pytest_gpu.log" 2>&1
 tail -15 "$OUT/pytest_gpu.log"
-timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 --detail "$OUT/bench_detail.json" > "$OUT/bench_driver_cmd.json" 2> "$OUT/bench_driver_cmd.err"
+timeout 600 python bench.py --full --gpus 1 --steps 20 --warmup 5 --detail "$OUT/bench_detail.json" > "$OUT/bench_driver_cmd.json" 2> "$OUT/bench_driver_cmd.err"
 echo "bench rc $? line length $(wc -c < "$OUT/bench_driver_cmd.json")"
 cat "$OUT/bench_driver_cmd.json"
 timeout 300 python tools/exp_r5_env_host.py > "$OUT/exp_env_host.txt" 2>&1

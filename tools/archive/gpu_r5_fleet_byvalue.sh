@@ -9,7 +9,7 @@ timeout 900 python -m pytest tests/test_ring_layout.py tests/test_fleet_stagger.
 : > "$OUT/exp_fleet_byvalue.txt"
 for cfg in 0 1 0 1; do
 export MGX_FLEET_BYVALUE=$cfg
-timeout 600 python bench.py --gpus 1 --no-cpu-baseline --all-legs --detail /dev/null 2> /dev/null | python -c "
+timeout 600 python bench.py --full --gpus 1 --no-cpu-baseline --all-legs --detail /dev/null 2> /dev/null | python -c "
 import json, sys
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('byvalue=$cfg', {k: v['us'] for k, v in d['legs'].items() if k.startswith('config5')})" | tee -a "$OUT/exp_fleet_byvalue.txt"

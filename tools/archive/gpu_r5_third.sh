@@ -8,7 +8,7 @@ mkdir -p "$OUT"
 cd "$REPO"
 timeout 900 python -m pytest tests -m gpu -q --maxfail=20 -p no:cacheprovider > "$OUT/pytest_gpu3.log" 2>&1
 tail -12 "$OUT/pytest_gpu3.log"
-timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 --detail "$OUT/bench_detail3.json" > "$OUT/bench_driver_cmd3.json" 2> "$OUT/bench_driver_cmd3.err"
+timeout 600 python bench.py --full --gpus 1 --steps 20 --warmup 5 --detail "$OUT/bench_detail3.json" > "$OUT/bench_driver_cmd3.json" 2> "$OUT/bench_driver_cmd3.err"
 echo "bench rc $? line length $(wc -c < "$OUT/bench_driver_cmd3.json")"
 cat "$OUT/bench_driver_cmd3.json"
 timeout 300 python tools/exp_r5_env_host.py > "$OUT/exp_env_host3.txt" 2>&1

@@ -1,7 +1,8 @@
 #!/bin/bash
-# Run ON THE GPU BOX (through gpurun): GPU test suite + the driver's bench command, results under gpurun_out/r02/.
-mkdir -p gpurun_out/r02
+# Run on an MI355X box: GPU test suite + the driver's bench command (with every leg), results under the directory given as $1.
+OUT=${1:?usage: gpu_round2.sh OUTDIR}
+mkdir -p "$OUT"
 python -m pytest tests -x -q -m gpu 2>&1 | tail -15
-python bench.py --gpus 1 --steps 20 --warmup 5 > gpurun_out/r02/bench_driver_cmd.json 2> gpurun_out/r02/bench_driver_cmd.err
-tail -c 2000 gpurun_out/r02/bench_driver_cmd.err
-python tools/show_bench.py gpurun_out/r02/bench_driver_cmd.json
+python bench.py --full --gpus 1 --steps 20 --warmup 5 > "$OUT/bench_driver_cmd.json" 2> "$OUT/bench_driver_cmd.err"
+tail -c 2000 "$OUT/bench_driver_cmd.err"
+python tools/archive/show_bench.py "$OUT/bench_driver_cmd.json"

@@ -19,10 +19,10 @@ cd /tmp
 HASH=$(cd "$REPO" && python -c "from pymgrid_amd import _lib; print(_lib.built_hash() or _lib.source_hash())")
 echo "csrc_hash $HASH" > "$OUT/csrc_hash.txt"
 ARGS="--gpus 1 --steps 20 --warmup 5"
-timeout 600 rocprofv3 --kernel-trace --stats -d "$OUT/stats" -o bench --output-format csv -- python "$REPO/bench.py" $ARGS --detail "$OUT/bench_detail.json" > "$OUT/stats.log" 2> "$OUT/stats.err"
+timeout 600 rocprofv3 --kernel-trace --stats -d "$OUT/stats" -o bench --output-format csv -- python "$REPO/bench.py" --full $ARGS --detail "$OUT/bench_detail.json" > "$OUT/stats.log" 2> "$OUT/stats.err"
 PMCARGS="$ARGS --no-cpu-baseline --hetero-steps 0 --no-closed-loop --detail $OUT/bench_detail_pmc.json"
-timeout 600 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d "$OUT/pmc_fetch" -o bench --output-format csv -- python "$REPO/bench.py" $PMCARGS > "$OUT/pmc_fetch.log" 2>&1
-timeout 600 rocprofv3 --pmc WRITE_SIZE --kernel-trace -d "$OUT/pmc_write" -o bench --output-format csv -- python "$REPO/bench.py" $PMCARGS > "$OUT/pmc_write.log" 2>&1
+timeout 600 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d "$OUT/pmc_fetch" -o bench --output-format csv -- python "$REPO/bench.py" --full $PMCARGS > "$OUT/pmc_fetch.log" 2>&1
+timeout 600 rocprofv3 --pmc WRITE_SIZE --kernel-trace -d "$OUT/pmc_write" -o bench --output-format csv -- python "$REPO/bench.py" --full $PMCARGS > "$OUT/pmc_write.log" 2>&1
 cd "$REPO"
 python tools/summarize_profile.py "$OUT" > "$OUT/summary.txt" 2>&1
 python - "$OUT/traffic.json" "$HASH" <<'PY'
@@ -39,7 +39,7 @@ for LEG in step_env_obs step_full; do
   cd /tmp
   LO=$OUT/leg_$LEG; mkdir -p "$LO"
   for c in FETCH_SIZE WRITE_SIZE; do
-    timeout 300 rocprofv3 --pmc $c --kernel-trace -d "$LO/$c" -o b --output-format csv -- python "$REPO/bench.py" --gpus 1 --steps 4 --warmup 1 --no-cpu-baseline --hetero-steps 0 --legs $LEG --detail /dev/null > "$LO/$c.log" 2>&1
+    timeout 300 rocprofv3 --pmc $c --kernel-trace -d "$LO/$c" -o b --output-format csv -- python "$REPO/bench.py" --full --gpus 1 --steps 4 --warmup 1 --no-cpu-baseline --hetero-steps 0 --legs $LEG --detail /dev/null > "$LO/$c.log" 2>&1
   done
   cd "$REPO"
   python - "$LO" "$OUT/traffic.json" $LEG <<'PY'
@@ -68,10 +68,10 @@ done
 cd /tmp
 SQARGS="--gpus 1 --steps 4 --warmup 1 --no-cpu-baseline --hetero-steps 0 --no-side-modes --no-closed-loop --detail /dev/null"
 for MODE in fused rbc; do
-  timeout 300 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES --kernel-trace -d "$OUT/sq_$MODE" -o b --output-format csv -- python "$REPO/bench.py" $SQARGS --mode $MODE > "$OUT/sq_$MODE.log" 2>&1
+  timeout 300 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES --kernel-trace -d "$OUT/sq_$MODE" -o b --output-format csv -- python "$REPO/bench.py" --full $SQARGS --mode $MODE > "$OUT/sq_$MODE.log" 2>&1
 done
 # (the full-output form of the fused kernel: a side leg of the fused headline)
-timeout 300 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES --kernel-trace -d "$OUT/sq_rich" -o b --output-format csv -- python "$REPO/bench.py" --gpus 1 --steps 4 --warmup 1 --no-cpu-baseline --hetero-steps 0 --no-closed-loop --legs fused_rich --detail /dev/null > "$OUT/sq_rich.log" 2>&1
+timeout 300 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES --kernel-trace -d "$OUT/sq_rich" -o b --output-format csv -- python "$REPO/bench.py" --full --gpus 1 --steps 4 --warmup 1 --no-cpu-baseline --hetero-steps 0 --no-closed-loop --legs fused_rich --detail /dev/null > "$OUT/sq_rich.log" 2>&1
 # (the general path's K-step launch: 100 000 grids, 32 steps per launch)
 timeout 300 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES --kernel-trace -d "$OUT/sq_kstep" -o b --output-format csv -- python "$REPO/tools/exp_r5_general_prof.py" kstep 512 > "$OUT/sq_kstep.log" 2>&1
 # (three of a kind, and RuleBasedControl's list roll-out on the general path: 100 000 grids, 32 steps per launch)

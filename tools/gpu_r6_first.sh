@@ -9,7 +9,7 @@ python -c "from pymgrid_amd import _lib; print('csrc_hash', _lib.built_hash() or
 nproc > "$OUT/nproc.txt"
 timeout 600 python tools/exp_r6_two_chains.py > "$OUT/exp_two_chains.txt" 2>&1
 cat "$OUT/exp_two_chains.txt" | grep -v amdgpu.ids
-timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 --detail "$OUT/bench_detail.json" > "$OUT/bench_driver_cmd.json" 2> "$OUT/bench_driver_cmd.err"
+timeout 600 python bench.py --full --gpus 1 --steps 20 --warmup 5 --detail "$OUT/bench_detail.json" > "$OUT/bench_driver_cmd.json" 2> "$OUT/bench_driver_cmd.err"
 echo "bench rc $? line length $(wc -c < "$OUT/bench_driver_cmd.json")"
 cat "$OUT/bench_driver_cmd.json"
 grep -v "^bench_detail\|amdgpu.ids" "$OUT/bench_driver_cmd.err" | tail -20

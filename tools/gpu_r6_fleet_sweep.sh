@@ -6,7 +6,7 @@ OUT=$REPO/gpurun_out/r06
 mkdir -p "$OUT"
 cd "$REPO"
 run() {
-  timeout 600 python bench.py --gpus 1 --steps 4 --warmup 1 --no-side-modes --no-cpu-baseline --detail /dev/null "$@" 2> /dev/null | python -c "
+  timeout 600 python bench.py --full --gpus 1 --steps 4 --warmup 1 --no-side-modes --no-cpu-baseline --detail /dev/null "$@" 2> /dev/null | python -c "
 import json, sys
 d = json.loads(sys.stdin.readline())
 print('$*', {k: (v['us'], v['frac']) for k, v in d['legs'].items() if k.startswith('config5')})" | tee -a "$OUT/exp_fleet_resweep2.txt"
