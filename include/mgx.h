@@ -337,6 +337,9 @@ int mgx_reset_episodes(mgx_handle *h, const int32_t *start, const int32_t *lengt
  * step kernel itself -- so that the step's `obs` is, for those grids, the first observation of their new episode (what a
  * vectorised Gym env with auto-reset returns) and no further launch is needed.  start_io / length_io / t0_io as for
  * mgx_reset_grids_random (device [N], each may be NULL; kept until the mode is switched off or the next mgx_reset*).
+ * Steps that restart so: mgx_step, mgx_step_discrete and, on layouts with several modules of a kind,
+ * mgx_step_lists (discrete steps over priority lists of module instances: in ONE launch where the layout holds at most two
+ * modules of a kind, in its two launches otherwise -- the restart then happens in the second).
  * enable = 0 switches it off. */
 int mgx_set_auto_reset(mgx_handle *h, int32_t enable, uint64_t seed, int32_t fixed_length, int32_t *start_io, int32_t *length_io,
                        int32_t *t0_io);
@@ -493,7 +496,8 @@ int mgx_step_discrete(mgx_handle *h, const int32_t *action_id, const int32_t *ta
 
 /* (minor 2) DiscreteMicrogridEnv.step (discrete.py:109-143) for priority lists over module INSTANCES: mgx_expand_lists +
  * mgx_step(normalized=0).  ONE launch -- the list walked and the control kept in registers -- where the layout holds at most two
- * modules of a kind and steps in lock-step or per-grid windows; two launches through `control` otherwise.  control [N, A]: optional
+ * modules of a kind and steps in lock-step, per-grid windows or in-place episodes (mgx_reset_episodes, restarts of
+ * mgx_set_auto_reset included); two launches through `control` otherwise.  control [N, A]: optional
  * where one launch is taken (it receives the expanded control when given), REQUIRED (the buffer between the two launches) for any
  * other layout -- MGX_ERR_INVALID without it.  lists as in mgx_expand_lists; the other outputs are those of mgx_step. */
 int mgx_step_lists(mgx_handle *h, const int32_t *action_id, const int32_t *lists, int32_t n_lists, int32_t list_len,

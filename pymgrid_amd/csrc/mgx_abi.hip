@@ -1751,16 +1751,23 @@ int mgx_step_lists(mgx_handle *h, const int32_t *action_id, const int32_t *lists
     if (int rc = check_step_args(h, action_id, reward, obs, 1, "mgx_step_lists")) return rc;
     hipStream_t st = (hipStream_t)stream;
     const bool noisy_rows = obs && !h->k.obs_state_only && (h->k.c.load_noise_std || h->k.c.pv_noise_std || h->k.c.grid_noise_std);
-    const bool one_launch = h->multi && h->multi_small && !h->inplace && !h->rolling && !noisy_rows && tune(MGX_TUNE_MULTI_SMALL_OWN) != 0 &&
-                            h->k.n_load >= 1 && h->k.n_pv >= 1;
+    // in-place episodes (mgx_reset_episodes) take the one launch too (the EP form: the grid's own rows, the auto-reset restarts in the
+    // kernel); the gathered rolling window buffers (mgx_reset_windows_rolling) are single-instance and never get here
+    const bool one_launch = h->multi && h->multi_small && (h->inplace || !h->rolling) && !noisy_rows &&
+                            tune(MGX_TUNE_MULTI_SMALL_OWN) != 0 && h->k.n_load >= 1 && h->k.n_pv >= 1;
     if (!one_launch) {                                    // any other layout: the control passes through the caller's buffer
         if (!control) return fail(MGX_ERR_INVALID, "mgx_step_lists: this layout steps in two launches and needs the control buffer [N, A]");
         if (int rc = launch_expand_lists(h, action_id, lists, n_lists, list_len, control, nullptr, st)) return rc;
         return step_once(h, control, 0, reward, done, obs, log, st);
     }
     for_each_shard_threaded(h, st, [&](const KArgs &k, hipStream_t s) {
-        MGX_DISPATCH_F(h->flags, (step_lists_small_kernel<F><<<multi_blocks(k.g1 - k.g0), BLOCK_MULTI, 0, s>>>(
-                                      k, action_id, lists, n_lists, list_len, t_arg(h), control, reward, done, obs, log)));
+        if (h->inplace && k.ep_off) {
+            MGX_DISPATCH_F(h->flags, (step_lists_small_kernel<F, true><<<multi_blocks(k.g1 - k.g0), BLOCK_MULTI, 0, s>>>(
+                                          k, action_id, lists, n_lists, list_len, t_arg(h), control, reward, done, obs, log)));
+        } else {
+            MGX_DISPATCH_F(h->flags, (step_lists_small_kernel<F><<<multi_blocks(k.g1 - k.g0), BLOCK_MULTI, 0, s>>>(
+                                          k, action_id, lists, n_lists, list_len, t_arg(h), control, reward, done, obs, log)));
+        }
     });
     hipError_t e = launch_error();
     if (e != hipSuccess) return hip_fail(e, "step_lists_small_kernel launch");

@@ -2327,7 +2327,9 @@ __global__ __launch_bounds__(BLOCK_MULTI, (M >= 3 ? MGX_M3_WAVES : 1)) void step
 // mgx_step_lists on the register form (round 6, ABI minor 2): ONE discrete Gym step of a layout with at most MS modules of a kind --
 // the grid's priority list packed into a word, walked out of registers (populate_multi_small), the step, the observation.  What
 // DiscreteMicrogridEnv.step was as two launches (expand_multi_kernel -> control [N, A] -> step_multi_kernel).
-template <int F>
+// EP: in-place per-grid episodes (mgx_reset_episodes; the restarts of mgx_set_auto_reset in the kernel, as step_multi_kernel<F, true>) --
+// the lock-step form carries none of it.
+template <int F, bool EP = false>
 __global__ __launch_bounds__(BLOCK_MULTI) void step_lists_small_kernel(const KArgs a, const int32_t *__restrict__ ids,
                                                                        const int32_t *__restrict__ lists, int32_t n_lists, int32_t list_len,
                                                                        int32_t t, double *__restrict__ control, double *__restrict__ reward,
@@ -2341,7 +2343,9 @@ __global__ __launch_bounds__(BLOCK_MULTI) void step_lists_small_kernel(const KAr
         Outputs o;
         MultiRegs R; MultiStepIn sin;
         load_multi_regs<F>(a, i, R);
-        load_multi_series<F>(a, i, t, sin);
+        int32_t off = 0, tr = t;                               // EP: the grid's own row, counter + ep_off[i]
+        if constexpr (EP) { off = a.ep_off[i]; tr = (int32_t)episode_row(a, t, off); }
+        load_multi_series<F>(a, i, tr, sin);
         int32_t id = ids[i];
         id = (id >= 0 && id < n_lists) ? id : 0;              // ids outside [0, n) fall back to list 0 (the reference raises)
         const uint64_t plw = pack_priority_list(lists + (int64_t)id * list_len * 3, list_len, NG, NB, NR);
@@ -2358,7 +2362,9 @@ __global__ __launch_bounds__(BLOCK_MULTI) void step_lists_small_kernel(const KAr
         step_multi_small<F>(a, R, sin, i, false, log ? log + i : nullptr, o, nullptr, xv);
         store_multi_state<F>(a, i, R);
         reward[i] = shaped_reward<F>(a.shaper, o);
-        if (done) done[i] = done_at(a, i, t);
+        const uint8_t dn = done_at(a, i, t);
+        if (done) done[i] = dn;
+        if constexpr (EP) { off = episode_auto_restart(a, i, t, off, dn != 0); t += off; }  // (the observation: row counter + 1 + offset)
         if (obs) {
             if (a.obs_state_only == 1 && a.obs_colpitch) {
                 const int64_t P = a.obs_colpitch, k0 = (int64_t)(a.n_load + a.n_pv) * (1 + a.H);

@@ -521,6 +521,13 @@ class PerGridWindowEnv:
     meaningful -- what a vectorised Gym env reports -- the others may hold older rows).  With a forecast horizon the
     observation rings stay in use: they are refilled on the caller's stream and the restarted grids' rows are patched into them
     (``mgx_patch_windows``).
+
+    Several modules of a kind per grid (``layout.multi``, e.g. a ``widen(...)`` batch): ``auto_reset=True`` runs in place
+    (``mgx_reset_episodes``; every grid reads its own rows of the ``[T, n, N]`` series, observation rows per step) with continuous
+    or discrete (``discrete=True``: priority lists over module instances) controls.  Device draws (``generator=None``) restart the
+    finished grids inside the step kernel -- a discrete step of a layout with at most two modules of a kind is one launch; a
+    ``generator``'s draws restart them behind the step (``mgx_reset_grids``).  ``final_observation`` and ``native=False`` are not
+    offered there.
     """
 
     FINAL_BUFFERS = 4
@@ -529,12 +536,14 @@ class PerGridWindowEnv:
                  final_observation=False, seed=0, native=None, **env_kwargs):
         L = full_batch.layout
         # Several modules of a kind per grid (round 6): equal-length windows are gathered per reset (mgx_reset_windows on the general
-        # path); auto_reset runs IN PLACE only (mgx_reset_episodes: the grid reads its own rows of the [T, n, N] series, the step kernel
-        # restarts it) with device draws and rows per step -- the rolling window buffers and the ring patches are single-instance
+        # path); auto_reset runs IN PLACE only (mgx_reset_episodes: the grid reads its own rows of the [T, n, N] series) with rows per
+        # step -- the rolling window buffers and the ring patches are single-instance.  Continuous or discrete controls; device draws
+        # restart the finished grids in the step kernel (mgx_set_auto_reset: a discrete step of at most two modules of a kind is ONE
+        # launch of step_lists_small_kernel), a torch generator's draws are applied behind the step (mgx_reset_grids)
         if L.multi:
-            if auto_reset and (generator is not None or final_observation or native is False or discrete):
-                raise NotImplementedError("several modules of a kind per grid: auto_reset runs in place with device draws "
-                                          "(generator=None, native, continuous controls, no final_observation)")
+            if auto_reset and (final_observation or native is False):
+                raise NotImplementedError("several modules of a kind per grid: auto_reset runs in place (native) without "
+                                          "final_observation")
             if auto_reset:
                 env_kwargs = dict(env_kwargs, obs_prefetch=0)
                 native = True
