@@ -50,8 +50,8 @@ extern "C" {
 #endif
 
 #define MGX_ABI_VERSION 9    /* frozen: struct layouts and the meaning of every v9 entry point do not change any more */
-#define MGX_ABI_MINOR 2      /* additions only: 1 = mgx_abi_minor, mgx_set_tunable / mgx_get_tunable, mgx_set_launch_threads,
-                              * mgx_action_bounds; 2 = mgx_step_lists */
+#define MGX_ABI_MINOR 3      /* additions only: 1 = mgx_abi_minor, mgx_set_tunable / mgx_get_tunable, mgx_set_launch_threads,
+                              * mgx_action_bounds; 2 = mgx_step_lists; 3 = MGX_TUNE_FLEET_EPISODES */
 
 enum mgx_status {
     MGX_OK = 0,
@@ -226,7 +226,8 @@ enum mgx_tunable {
     MGX_TUNE_FLEET_BYVALUE = 8,    /* 0: mgx_fleet_step launches the pointer form of the fleet kernel (default 1: by value) */
     MGX_TUNE_LAUNCH_THREADS = 9,   /* mode (0 / 1 / 2) handles created afterwards start with: mgx_set_launch_threads (default 1) */
     MGX_TUNE_MULTI_STATIC = 10,    /* 0: mgx_step_k of small general layouts never takes a compile-time-count specialisation (A/B, tests) */
-    MGX_TUNE_COUNT_ = 11
+    MGX_TUNE_FLEET_EPISODES = 11,  /* 0: mgx_fleet_step steps in-place-episode items beside its launches (default 1: one launch for them) */
+    MGX_TUNE_COUNT_ = 12
 };
 int mgx_set_tunable(int32_t id, int64_t value);                                /* MGX_ERR_INVALID: unknown id / value out of range */
 int mgx_get_tunable(int32_t id, int64_t *value, int64_t *default_value);       /* either pointer may be NULL */
@@ -650,6 +651,16 @@ typedef struct mgx_fleet_item {
     int32_t reserved;
 } mgx_fleet_item;
 int mgx_fleet_step(const mgx_fleet_item *items, int32_t n_items, int normalized, mgx_stream stream);
+/* Launch rule of mgx_fleet_step.  Lock-step items with one module of every kind (and those with at most two modules of a kind,
+ * continuous controls and no forecast noise) share one launch of the fleet kernel per MGX_FLEET_MAX = 5 items.  Items whose handle
+ * steps in-place per-grid episodes (mgx_reset_episodes; mgx_set_auto_reset / mgx_set_final_obs as for mgx_step) with one module of
+ * every kind, no shards, no device counter, and rows written by the step itself -- no rows, whole H = 0 rows, or the state columns of
+ * a ring block (MGX_OBS_ROWS_STATE_ONLY) -- share a launch of the fleet kernel's episode form per 5 items: each grid reads its own
+ * rows, writes the row before its restart and restarts itself, as mgx_step / mgx_step_discrete do for one handle, with the same
+ * values bit for bit.  MGX_TUNE_FLEET_EPISODES = 0 steps them beside instead.  Every other item is stepped beside the shared
+ * launches through the single-handle path (several modules of a kind in episodes, rolling window buffers, rows with a horizon
+ * written behind the step, shards, device counters).  The caller's per-handle work after a step (ring patches of the restarted
+ * grids, mgx_patch_windows; restarts drawn on the host, mgx_reset_grids) follows the call on the same stream. */
 /* The bound form of a fleet's Gym step: every handle carries an env plan (mgx_env_bind: rotating reward / done / row / log slots,
  * three observation rings) and the call is mgx_fleet_step over the items those plans produce -- handle j steps with actions[j]
  * (continuous controls [N, A], or int32 priority-list ids [N] where the plan holds a table) into its next slot and ring block,

@@ -26,10 +26,10 @@ V_EXPAND_CONSUME, V_EXPAND_PRODUCE, V_EXPAND_SIGN = 64, 128, 256
 V_EXPAND = V_EXPAND_CONSUME | V_EXPAND_PRODUCE | V_EXPAND_SIGN      # states in which _populate_action asserts
 V_ASSERTS = V_GENSET_GOAL | V_GENSET_NEGATIVE | V_NEGATIVE_LIMIT | V_EXPAND    # the reference raises whatever raise_errors says
 ABI_VERSION = 9
-ABI_MINOR = 2
+ABI_MINOR = 3
 # enum mgx_tunable (process-wide launch-shape knobs; set_tunable / get_tunable below)
 TUNABLES = ("win_threads", "win_group", "win_pairs", "win_min_lds", "prefetch_pool", "multi_generic", "multi_small_own",
-            "grid_major_copy", "fleet_byvalue", "launch_threads", "multi_static")
+            "grid_major_copy", "fleet_byvalue", "launch_threads", "multi_static", "fleet_episodes")
 MAX_INSTANCES = 8          # MGX_MAX_INSTANCES: gensets / batteries / grids per microgrid
 
 

@@ -115,6 +115,7 @@ const int64_t kTuneDefault[MGX_TUNE_COUNT_] = {
     /* MGX_TUNE_FLEET_BYVALUE   */ 1,
     /* MGX_TUNE_LAUNCH_THREADS  */ 1,      // 0 / 1 / 2: see mgx_set_launch_threads
     /* MGX_TUNE_MULTI_STATIC    */ 1,
+    /* MGX_TUNE_FLEET_EPISODES  */ 1,
 };
 struct TuneInit { TuneInit() { for (int j = 0; j < MGX_TUNE_COUNT_; j++) g_tune[j].store(kTuneDefault[j], std::memory_order_relaxed); } } g_tune_init;
 inline int64_t tune(int id) { return g_tune[id].load(std::memory_order_relaxed); }
@@ -2035,9 +2036,14 @@ int mgx_fleet_step(const mgx_fleet_item *items, int32_t n, int normalized, mgx_s
     // One launch for all batches (continuous and discrete items alike) that can share it; an item that needs kernels of its own
     // (several modules of a kind, rolling windows, a device counter, shards, per-step rows with a horizon) is stepped beside it --
     // the others still share their launch (round 6: one such bucket used to send EVERY bucket of the fleet to its own launch).
+    // Items stepping in-place per-grid episodes (mgx_reset_episodes) with one module of every kind and rows written inline (none,
+    // H = 0 rows, or the state columns of a ring block) share a launch of their own: the episode form fleet_step_kernel_v<true>
+    // (MGX_TUNE_FLEET_EPISODES = 0: they are stepped beside, one step_kernel<F, true> / step_discrete_kernel<F, true> each).
     if (n > 64) return fail(MGX_ERR_INVALID, "mgx_fleet_step: at most 64 items per call");
-    bool fuse[64];
+    bool fuse[64], epf[64];
     int32_t fz[64], nf = 0;                                 // the items that share the launch, in item order
+    int32_t ez[64], ne = 0;                                 // the in-place items that share the episode-form launch, in item order
+    const bool ep_launch = tune(MGX_TUNE_FLEET_EPISODES) != 0;
     bool any_chunks = tune(MGX_TUNE_FLEET_BYVALUE) == 0;    // window chunks ride with the POINTER form of the kernel: single-instance layouts only
     for (int32_t j = 0; j < n; j++) any_chunks = any_chunks || (items[j].refill_ring && items[j].refill_chunks > 0);
     for (int32_t j = 0; j < n; j++) {
@@ -2048,9 +2054,15 @@ int mgx_fleet_step(const mgx_fleet_item *items, int32_t n, int normalized, mgx_s
         const bool multi_ok = h->multi && h->multi_small && !any_chunks && !it.action_id && !h->inplace && !h->windowed &&
                               !(it.obs && (h->k.c.load_noise_std || h->k.c.pv_noise_std || h->k.c.grid_noise_std));
         fuse[j] = (!h->multi || multi_ok) && !h->rolling && !dev_counter(h) && h->n_shards <= 1 && !(it.obs && h->k.H > 0 && !h->k.obs_state_only);
+        // (the rows of an in-place item are written by the step kernel itself exactly when episode_step_begin leaves the restart in it)
+        epf[j] = ep_launch && h->inplace && !h->multi && !dev_counter(h) && h->n_shards <= 1 &&
+                 (!it.obs || h->k.H == 0 || h->k.obs_state_only);
+        if (epf[j] && h->k.final_obs && !it.obs)
+            return fail(MGX_ERR_INVALID, "mgx_fleet_step: item %d: mgx_set_final_obs is set but the step writes no observation", j);
         for (int32_t q = 0; q < j; q++)
             if (items[q].handle == it.handle) return fail(MGX_ERR_INVALID, "mgx_fleet_step: item %d steps the batch of item %d again", j, q);
         if (fuse[j]) fz[nf++] = j;
+        if (epf[j]) ez[ne++] = j;
     }
     bool chunk_done[64];                                    // window chunks that rode along with the step launch
     for (int32_t j = 0; j < n; j++) chunk_done[j] = false;
@@ -2099,7 +2111,7 @@ int mgx_fleet_step(const mgx_fleet_item *items, int32_t n, int normalized, mgx_s
                     if (wg > most) most = wg;
                 }
                 if (any_multi) fleet_step_kernel_vm<<<dim3((unsigned)most, (unsigned)nb), BLOCK, 0, st>>>(fv);
-                else fleet_step_kernel_v<<<dim3((unsigned)most, (unsigned)nb), BLOCK, 0, st>>>(fv);
+                else fleet_step_kernel_v<false><<<dim3((unsigned)most, (unsigned)nb), BLOCK, 0, st>>>(fv);
                 hipError_t ev = hipGetLastError();
                 if (ev != hipSuccess) return hip_fail(ev, "fleet_step_kernel_v launch");
                 continue;
@@ -2146,8 +2158,44 @@ int mgx_fleet_step(const mgx_fleet_item *items, int32_t n, int normalized, mgx_s
         }
         for (int32_t z = 0; z < nf; z++) advance(items[fz[z]].handle, 1, st);
     }
+    for (int32_t z0 = 0; z0 < ne; z0 += MGX_FLEET_MAX) {    // in-place episodes: the episode form, KArgs by value as in step_once
+        const int32_t nb = ne - z0 < MGX_FLEET_MAX ? ne - z0 : MGX_FLEET_MAX;
+        FleetArgsV fv;
+        fv.n = nb; fv.normalized = normalized; fv.pad0 = fv.pad1 = 0;
+        int32_t most = 0;
+        for (int32_t q = 0; q < nb; q++) {
+            const mgx_fleet_item &it = items[ez[z0 + q]];
+            mgx_handle *h = it.handle;
+            if (it.action_id) {                            // discrete item: the device copy of its priority-list table
+                PLWords tab;
+                if (int rc = encode_table(h, it.table, it.n_actions, &tab, "mgx_fleet_step")) return rc;
+                if (!(h->table_uploaded_valid && memcmp(&tab, &h->table_uploaded, sizeof(PLWords)) == 0)) {
+                    hipError_t e = hipSuccess;
+                    DeviceGuard on_device(h->device);
+                    if (!h->d_table) e = hipMalloc((void **)&h->d_table, sizeof(PLWords));
+                    if (e == hipSuccess) e = hipMemcpyAsync(h->d_table, &tab, sizeof(PLWords), hipMemcpyHostToDevice, st);
+                    if (e != hipSuccess) return hip_fail(e, "mgx_fleet_step: uploading the priority-list table");
+                    memcpy(&h->table_uploaded, &tab, sizeof(PLWords));
+                    h->table_uploaded_valid = true;
+                }
+            }
+            FleetBucket &B = fv.b[q];
+            B.k = h->k; B.k.g0 = 0; B.k.g1 = h->k.N;
+            if (B.k.obs_state_only == 1) B.k.final_obs = nullptr;  // rings: mgx_patch_windows saves the rows of the restarted grids
+            B.hd.tab = it.action_id ? h->d_table : nullptr; B.hd.n_grids = h->k.N; B.hd.t = h->t; B.hd.flags = h->flags;
+            B.hd.pad0 = 0; B.hd.pad1 = 0;
+            B.actions = it.action_id ? (const void *)it.action_id : it.actions;
+            B.reward = it.reward; B.done = it.done; B.obs = it.obs; B.log = it.log;
+            const int32_t wg = (int32_t)blocks_for(h->k.N);
+            if (wg > most) most = wg;
+        }
+        fleet_step_kernel_v<true><<<dim3((unsigned)most, (unsigned)nb), BLOCK, 0, st>>>(fv);
+        hipError_t ev = hipGetLastError();
+        if (ev != hipSuccess) return hip_fail(ev, "fleet_step_kernel_v<true> launch");
+        for (int32_t q = 0; q < nb; q++) advance(items[ez[z0 + q]].handle, 1, st);
+    }
     for (int32_t j = 0; j < n; j++) {                     // the items with kernels of their own
-        if (fuse[j]) continue;
+        if (fuse[j] || epf[j]) continue;
         const mgx_fleet_item &it = items[j];
         int rc;
         if (it.action_id)

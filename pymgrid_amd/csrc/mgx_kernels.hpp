@@ -1519,27 +1519,34 @@ static_assert(sizeof(FleetArgsV) <= 3840, "the kernarg segment holds 4 KB");
     const int normalized = fa.normalized; \
     const FleetBucket &B = *reinterpret_cast<const FleetBucket *>((const char *)mine);
 
-#define MGX_FLEET_V_DISCRETE(FV) case FV: { step_discrete_body<FV>(B.k, *hd.tab, (const int32_t *)B.actions, hd.t, nullptr, B.reward, B.done, B.obs, B.log, i); } break;
-#define MGX_FLEET_V_STEP(FV) case FV: { step_body<FV>(B.k, B.actions, hd.t, normalized, B.reward, B.done, B.obs, B.log, i); } break;
-#define MGX_FLEET_V_SWITCHES                                                                                                          \
+// EPV: the compile-time episode form of the bodies (false: lock-step; true: in-place per-grid episodes, step_body<F, true>)
+#define MGX_FLEET_V_DISCRETE(FV, EPV) case FV: { step_discrete_body<FV, EPV>(B.k, *hd.tab, (const int32_t *)B.actions, hd.t, nullptr, B.reward, B.done, B.obs, B.log, i); } break;
+#define MGX_FLEET_V_STEP(FV, EPV) case FV: { step_body<FV, EPV>(B.k, B.actions, hd.t, normalized, B.reward, B.done, B.obs, B.log, i); } break;
+#define MGX_FLEET_V_SWITCHES(EPV)                                                                                                     \
     if (hd.tab != nullptr) {                      /* a DiscreteMicrogridEnv batch: ids -> control -> run, in registers */            \
         switch (hd.flags) {                                                                                                           \
-            MGX_FLEET_V_DISCRETE(0) MGX_FLEET_V_DISCRETE(1) MGX_FLEET_V_DISCRETE(2) MGX_FLEET_V_DISCRETE(3) MGX_FLEET_V_DISCRETE(4)   \
-            MGX_FLEET_V_DISCRETE(5) MGX_FLEET_V_DISCRETE(6) MGX_FLEET_V_DISCRETE(7) MGX_FLEET_V_DISCRETE(14)                          \
-            default: { step_discrete_body<15>(B.k, *hd.tab, (const int32_t *)B.actions, hd.t, nullptr, B.reward, B.done, B.obs, B.log, i); } break; \
+            MGX_FLEET_V_DISCRETE(0, EPV) MGX_FLEET_V_DISCRETE(1, EPV) MGX_FLEET_V_DISCRETE(2, EPV) MGX_FLEET_V_DISCRETE(3, EPV)       \
+            MGX_FLEET_V_DISCRETE(4, EPV) MGX_FLEET_V_DISCRETE(5, EPV) MGX_FLEET_V_DISCRETE(6, EPV) MGX_FLEET_V_DISCRETE(7, EPV)       \
+            MGX_FLEET_V_DISCRETE(14, EPV)                                                                                             \
+            default: { step_discrete_body<15, EPV>(B.k, *hd.tab, (const int32_t *)B.actions, hd.t, nullptr, B.reward, B.done, B.obs, B.log, i); } break; \
         }                                                                                                                             \
         return;                                                                                                                       \
     }                                                                                                                                 \
     switch (hd.flags) {                                                                                                               \
-        MGX_FLEET_V_STEP(0) MGX_FLEET_V_STEP(1) MGX_FLEET_V_STEP(2) MGX_FLEET_V_STEP(3) MGX_FLEET_V_STEP(4)                           \
-        MGX_FLEET_V_STEP(5) MGX_FLEET_V_STEP(6) MGX_FLEET_V_STEP(7) MGX_FLEET_V_STEP(14)                                              \
-        default: { step_body<15>(B.k, B.actions, hd.t, normalized, B.reward, B.done, B.obs, B.log, i); } break;                       \
+        MGX_FLEET_V_STEP(0, EPV) MGX_FLEET_V_STEP(1, EPV) MGX_FLEET_V_STEP(2, EPV) MGX_FLEET_V_STEP(3, EPV) MGX_FLEET_V_STEP(4, EPV)   \
+        MGX_FLEET_V_STEP(5, EPV) MGX_FLEET_V_STEP(6, EPV) MGX_FLEET_V_STEP(7, EPV) MGX_FLEET_V_STEP(14, EPV)                          \
+        default: { step_body<15, EPV>(B.k, B.actions, hd.t, normalized, B.reward, B.done, B.obs, B.log, i); } break;                  \
     }
 
+// EP = false: lock-step buckets.  EP = true: buckets stepping in-place per-grid episodes (mgx_reset_episodes) with one module of every
+// kind -- every bucket of the launch reads its grids' own rows through KArgs.ep_off, writes the rows before a restart (final_obs) and
+// restarts finished grids itself (ar_*), as step_kernel<F, true> does for one batch: an auto-reset fleet step is ONE launch instead of
+// one per bucket.  Everything the episode form needs already travels in the bucket's KArgs (ep_off, ep_final, ar_*, final_obs, pm_pitch).
+template <bool EP>
 static __global__ __launch_bounds__(BLOCK) void fleet_step_kernel_v(const FleetArgsV fa)
 {
     MGX_FLEET_V_HEAD
-    MGX_FLEET_V_SWITCHES
+    MGX_FLEET_V_SWITCHES(EP)
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -1824,7 +1831,7 @@ __device__ inline void observe_row_multi(const KArgs &a, int64_t i, int32_t t, O
 }
 
 // One general-path step of grid i on the register form (at most MS modules of a kind), lock-step: what a bucket with several
-// modules of a kind runs inside the fleet's launch (fleet_step_kernel_v<true>, round 6) -- the `small` arm of step_multi_kernel
+// modules of a kind runs inside the fleet's launch (fleet_step_kernel_vm, round 6) -- the `small` arm of step_multi_kernel
 // without per-grid episodes.
 template <int F>
 __device__ __forceinline__ void step_multi_small_body(const KArgs &a, const void *__restrict__ actions, int32_t t, int normalized,
@@ -1867,7 +1874,7 @@ static __global__ __launch_bounds__(BLOCK) void fleet_step_kernel_vm(const Fleet
 #undef MGX_FLEET_V_MULTI
         return;
     }
-    MGX_FLEET_V_SWITCHES
+    MGX_FLEET_V_SWITCHES(false)
 }
 
 // EP: in-place per-grid episodes (the lock-step form carries none of it, as step_kernel<F, EP>)

@@ -683,6 +683,238 @@ class PerGridWindowEnv:
         return getattr(self.env, name)
 
 
+def bucket_seed(seed, k):
+    """The Philox seed of bucket ``k`` of a ``PerGridWindowFleet`` built with ``seed``: ``(seed + k * 0x9E3779B97F4A7C15) mod 2**64``.
+    Bucket 0 keeps ``seed`` itself; the odd stride maps distinct buckets to distinct seeds, so no two buckets share a draw stream."""
+    return (int(seed) + int(k) * 0x9E3779B97F4A7C15) & (2 ** 64 - 1)
+
+
+class PerGridWindowFleet:
+    """``PerGridWindowEnv`` over a fleet of mixed layouts (BASELINE config 5): per-grid random episodes, each grid restarted on its own
+    (``auto_reset=True``), for every architecture of the population behind one ``step()`` / ``reset()`` surface.
+
+    Bucket ``k`` behaves exactly like ``PerGridWindowEnv(batch_k, ..., seed=fleet.seeds[k])`` (``bucket_seed``): the same observations,
+    rewards, ``done`` flags, final observations, episode starts / lengths, per-grid step counters and module state, bit for bit.  With a
+    torch ``generator`` the buckets draw from it in bucket order, each as its own ``PerGridWindowEnv`` would.  A bucket that
+    ``PerGridWindowEnv`` refuses is refused here with the same exception.
+
+    A fleet step is ONE ``mgx_fleet_step`` call for the buckets with one module of every kind: in-place episodes share one launch of
+    the episode form of the fleet kernel (``fleet_step_kernel_v<true>``), gathered windows (``auto_reset=False``) share the lock-step
+    launch, and what cannot share a launch is stepped beside it inside the same call.  The per-bucket work behind a step (ring patches
+    of the restarted grids, restarts drawn by a torch generator) follows on the caller's stream.  Buckets with several modules of a
+    kind, and envs that need host work around every step (``raise_errors``, ``check_asserts``, ``log``, ``obs_views``), step through
+    their own ``PerGridWindowEnv.step`` in bucket order.
+
+    ``reset`` / ``step`` take and return lists with one entry per bucket; ``scatter`` puts a per-grid quantity back into fleet order.
+    """
+
+    def __init__(self, grids, device="cuda", trajectory_length=None, discrete=False, generator=None, auto_reset=False,
+                 final_observation=False, seed=0, native=None, **env_kwargs):
+        self.device = torch.device(device)
+        buckets = list(bucket_by_layout(grids).items())          # [(key, [indices])]
+        batches = [MicrogridBatch.from_grids([grids[i] for i in idx], device=device) for _, idx in buckets]
+        index = [torch.as_tensor(np.asarray(idx), device=self.device) for _, idx in buckets]
+        self._setup(batches, index, trajectory_length, discrete, generator, auto_reset, final_observation, seed, native, env_kwargs)
+
+    @classmethod
+    def from_batches(cls, batches, trajectory_length=None, discrete=False, generator=None, auto_reset=False, final_observation=False,
+                     seed=0, native=None, **env_kwargs):
+        """Fleet over ready-made ``MicrogridBatch`` objects (e.g. ``generator.generate_fleet``): bucket k owns fleet positions
+        [sum(n_0..n_{k-1}), ... + n_k)."""
+        self = cls.__new__(cls)
+        self.device = batches[0].device
+        index, start = [], 0
+        for b in batches:
+            n = b.layout.n_grids
+            index.append(torch.arange(start, start + n, device=self.device))
+            start += n
+        self._setup(batches, index, trajectory_length, discrete, generator, auto_reset, final_observation, seed, native, env_kwargs)
+        return self
+
+    def _setup(self, batches, index, trajectory_length, discrete, generator, auto_reset, final_observation, seed, native, env_kwargs):
+        self.seed = int(seed)
+        self.seeds = [bucket_seed(seed, k) for k in range(len(batches))]
+        self.envs = [PerGridWindowEnv(b, trajectory_length=trajectory_length, discrete=discrete, generator=generator, auto_reset=auto_reset,
+                                      final_observation=final_observation, seed=self.seeds[k], native=native, **env_kwargs)
+                     for k, b in enumerate(batches)]
+        self.index = index
+        self.buckets = [(b.layout, idx) for b, idx in zip(batches, index)]
+        self.n_grids = sum(b.layout.n_grids for b in batches)
+        # which buckets step through the fleet's mgx_fleet_step call (the others: their own PerGridWindowEnv.step)
+        self._in_call = [self._steps_in_call(pe) for pe in self.envs]
+        for pe, inc in zip(self.envs, self._in_call):
+            if inc:                               # stepped through mgx_fleet_step: no bound single-env step (mgx_env_bind) on its handle
+                pe.env._fast_ok = False
+                pe.env._rebind_fast()
+
+    @staticmethod
+    def _steps_in_call(pe):
+        env = pe.env
+        return not (env.layout.multi or env.raise_errors or getattr(env, "check_asserts", False) or env._keep_log or env._views
+                    or env.engine.n_shards != 1 or env.engine._dev_counter)
+
+    def __len__(self):
+        return self.n_grids
+
+    @property
+    def starts(self):
+        return [pe.starts for pe in self.envs]
+
+    @property
+    def lengths(self):
+        return [pe.lengths for pe in self.envs]
+
+    @property
+    def current_steps(self):
+        return [pe.env.current_steps for pe in self.envs]
+
+    def reset(self, starts=None, lengths=None):
+        """Every bucket's ``PerGridWindowEnv.reset``, in bucket order (``starts`` / ``lengths``: optional lists, one entry per bucket).
+        Without them every bucket draws its first episodes as its ``PerGridWindowEnv`` does: from the fleet's ``generator``, or from
+        torch's default generator when there is none."""
+        return [pe.reset(None if starts is None else starts[k], None if lengths is None else lengths[k])
+                for k, pe in enumerate(self.envs)]
+
+    def sample_action(self, generator=None):
+        return [pe.sample_action(generator=generator) for pe in self.envs]
+
+    def scatter(self, per_bucket):
+        """[tensor [n_b, ...] per bucket] -> one tensor [N, ...] in fleet order (as ``BucketedFleet.scatter``)."""
+        first = per_bucket[0]
+        out = torch.empty((self.n_grids,) + tuple(first.shape[1:]), dtype=first.dtype, device=first.device)
+        for idx, v in zip(self.index, per_bucket):
+            out[idx] = v
+        return out
+
+    def step(self, actions, normalized=True):
+        """actions: list with one entry per bucket (continuous controls [n_k, A] or priority-list ids [n_k]).  Returns
+        (obs_list, reward_list, done_list, info_list); ``info[k]["final_observation"]`` with ``final_observation=True``."""
+        n = len(self.envs)
+        items = (_lib.FleetItem * n)()
+        plans = [None] * n
+        used = []
+        for k, pe in enumerate(self.envs):
+            if not self._in_call[k]:
+                continue
+            it = items[len(used)]
+            plans[k] = self._before(pe, actions[k], it)
+            used.append(k)
+        if used:
+            e0 = self.envs[used[0]].env.engine
+            idx = e0._dev_index
+            if e0._only_device or torch.cuda.current_device() == idx:
+                rc = e0._lib.mgx_fleet_step(items, len(used), 1 if normalized else 0, _raw_stream(idx))
+            else:
+                with torch.cuda.device(idx):
+                    rc = e0._lib.mgx_fleet_step(items, len(used), 1 if normalized else 0, _raw_stream(idx))
+            if rc:
+                _lib.check(rc)
+        out = []
+        for k, pe in enumerate(self.envs):        # bucket order: a torch generator's draws come in the order of the twins' steps
+            if plans[k] is None:
+                out.append(pe.step(actions[k]) if isinstance(pe.env, DiscreteBatchedMicrogridEnv)
+                           else pe.step(actions[k], normalized=normalized))
+            else:
+                out.append(self._after(pe, plans[k]))
+        return tuple(list(x) for x in zip(*out))
+
+    # ---- one bucket's PerGridWindowEnv.step, around the fleet's C call ------------------------------------------------------------
+    def _before(self, pe, action, it):
+        """What ``PerGridWindowEnv.step`` / the env's ``step`` do before their launch, with the launch's arguments written into the
+        ``mgx_fleet_item`` ``it`` instead.  Returns what ``_after`` needs."""
+        import ctypes as C
+        env = pe.env
+        e = env.engine
+        final = None
+        path = "plain"
+        want_rows = env._observations
+        if pe.auto_reset:
+            if pe.native and pe._device_draws:
+                path = "ring" if env._ring is not None else "inline"
+                if pe.final_observation and (env._ring is not None or env._observations):
+                    final = pe._next_final_buf()
+                    e.set_final_obs(final)
+            else:
+                path = "host"
+                if want_rows and not pe.final_observation and env._ring is None:   # the rows come from the observe pass behind the restarts
+                    env._observations = False
+        try:
+            want_obs, out = env._obs_target()
+        finally:
+            env._observations = want_rows
+        dconst = env._lockstep_done()
+        out = out or {}
+        reward = out.get("reward")
+        if reward is None:
+            reward = e._empty(e.N)
+        done = None
+        if dconst is None:
+            done = out.get("done")
+            if done is None:
+                done = e._empty(e.N, dtype=torch.uint8)
+        obs = e._obs_buf(out.get("obs")) if want_obs else None
+        it.struct_size = C.sizeof(_lib.FleetItem)
+        it.handle = e._h.value
+        if isinstance(env, DiscreteBatchedMicrogridEnv):
+            a = action
+            if not (torch.is_tensor(a) and a.dtype == torch.int32 and a.is_contiguous() and a.device == e.device):
+                a = torch.as_tensor(np.asarray(a.cpu() if torch.is_tensor(a) else a), device=e.device).to(torch.int32).contiguous()
+            if a.shape != (e.N,):
+                raise ValueError(f"action_id must be an int32 tensor of shape ({e.N},) on {e.device}")
+            it.action_id = a.data_ptr()
+            it.table, it.n_actions = e._table_ptr(env._table)
+        else:
+            a = env.control_to_tensor(action).to(e.action_dtype) if isinstance(action, dict) else action
+            a = e._check_actions(a, ())
+            it.actions = None if a is None else a.data_ptr()
+        it.reward = reward.data_ptr()
+        it.done = None if done is None else done.data_ptr()
+        it.obs = None if obs is None else obs.data_ptr()
+        it.log = None
+        return path, final, a, obs, reward, done, dconst, want_rows
+
+    def _after(self, pe, plan):
+        """What ``PerGridWindowEnv.step`` / the env's ``step`` do after their launch: the host counter, the ring walk, the ring patches
+        of the restarted grids, a generator's restarts -- on the caller's stream, in bucket order."""
+        path, final, _, obs, reward, done, dconst, want_rows = plan
+        env = pe.env
+        e = env.engine
+        if e._t is not None:
+            e._t += 1                             # the host mirror of the handle's counter (mgx_fleet_step moved it)
+        obs = env._select_obs(env._obs_after(obs))
+        done = dconst if dconst is not None else done.view(torch.bool)
+        info = {}
+        if path == "ring":                        # the restarted grids' window columns in the rest of the ring
+            obs = env._rows_after_restart(done.view(torch.uint8), True)
+            if final is not None:
+                info["final_observation"] = env._select_obs(final)
+        elif path == "inline":
+            if final is not None:
+                info["final_observation"] = env._select_obs(final)
+        elif path == "host":
+            final = obs.clone() if (pe.final_observation and obs is not None) else None
+            if pe._device_draws:
+                if pe.lengths is None:
+                    pe.lengths = torch.full_like(pe.starts, pe.length if pe.length is not None else 0)
+                new_obs = env.reset_grids_random(done, pe.seed, pe.length or 0, lengths_out=pe.lengths)
+                pe.starts = e._window_start
+            else:
+                starts, lengths = pe.draw()
+                new_obs = env.reset_grids(done, starts, lengths, validate=False)
+                pe.starts = torch.where(done, starts, pe.starts)
+                if lengths is not None:
+                    pe.lengths = torch.where(done, lengths, pe.lengths)
+            if pe.final_observation:
+                info["final_observation"] = final
+            if new_obs is not None:
+                obs = new_obs
+        return obs, reward, done, info
+
+    def close(self):
+        for pe in self.envs:
+            pe.env.close()
+
+
 class StreamShards:
     """Independent shards of a fleet -- each a ``MicrogridBatch`` with its own engine -- driven on one HIP stream each and
     NOT joined between calls.
