@@ -512,6 +512,33 @@ int mgx_rollout_discrete(mgx_handle *h, const uint8_t *action_id, int per_step, 
                          int32_t n_actions, int32_t K, double *reward, uint8_t *done, double *soc_trace,
                          uint32_t *status_trace, double *ret_acc, double *log, mgx_stream stream);
 
+/* Per-grid episode statistics of mgx_rollout_episodes (device arrays, each may be NULL).  They are read, updated and written
+ * back, so they carry from one call to the next; the caller zeroes them when it resets.  Per step of grid i, in step order and
+ * in plain fp64 (a host loop over the per-step rewards reproduces them bit for bit):
+ *     ret_running[i] += reward
+ *     if this step is the last one of the grid's episode (counter == ep_final[i] - 1):
+ *         ret_last[i] = ret_running[i];  ret_sum[i] += ret_running[i];  episodes[i] += 1;  ret_running[i] = 0
+ * A grid that is not restarted (mgx_set_auto_reset off) walks on with done = 1; it is counted once, when it crosses its end. */
+typedef struct mgx_episode_stats {
+    double *ret_running;   /* [N] return of the episode in progress */
+    double *ret_sum;       /* [N] sum of the returns of the episodes finished so far, added in the order they finish */
+    double *ret_last;      /* [N] return of the most recently finished episode */
+    int32_t *episodes;     /* [N] number of episodes finished */
+} mgx_episode_stats;
+
+/* The fused discrete roll-out over per-grid IN-PLACE episodes (mgx_reset_episodes): K steps in one launch, every grid reading the
+ * rows of its own episode and -- with mgx_set_auto_reset -- restarting inside the launch whenever a step ends its episode, with
+ * the draw, the offsets and the start / length / t0 arrays exactly as K calls of mgx_step_discrete would leave them.  action_id /
+ * per_step / table as in mgx_rollout_discrete; reward / done (bytes) / soc_trace / status_trace [K, N] and `stats` (the struct
+ * pointer too) may be NULL.  No observations and no balance log are written.  The counter moves by K.
+ * MGX_ERR_INVALID: the handle does not step in-place episodes.  MGX_ERR_UNSUPPORTED: several modules of a kind, shards, device-counter
+ * mode, `done` as bit sets, mgx_set_final_obs set.  Nothing is launched when the call is refused.
+ * An ADDITION to ABI 9 that leaves MGX_ABI_MINOR at 3: consumers find it by name (dlsym); mgx_step_k, mgx_rollout_discrete and
+ * mgx_rollout_lists keep refusing handles in this mode. */
+int mgx_rollout_episodes(mgx_handle *h, const uint8_t *action_id, int per_step, const int32_t *table, int32_t n_actions,
+                         int32_t K, double *reward, uint8_t *done, double *soc_trace, uint32_t *status_trace,
+                         const mgx_episode_stats *stats, mgx_stream stream);
+
 /* raise_errors=True (BaseMicrogridModule.__init__, base_module.py:40; as_source / as_sink, :213-224,265-270; _raise_error,
  * :79-93): the reference refuses a request a module cannot meet with a ValueError instead of clipping it.  mgx_step always
  * clips; mgx_check_step is its DRY RUN -- the same arithmetic on a register copy of the state, nothing stored, the counter

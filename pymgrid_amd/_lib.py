@@ -13,9 +13,10 @@ import sys
 _PKG = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_PKG)
 LIB_PATH = os.environ.get("MGX_LIB") or os.path.join(_PKG, "libmgx.so")   # MGX_LIB: A/B kernel variants
-SOURCES = [os.path.join(_PKG, "csrc", f) for f in ("mgx_abi.hip", "mgx_fused.hip", "mgx_kernels.hpp", "mgx_core.hpp")] + \
+SOURCES = [os.path.join(_PKG, "csrc", f) for f in ("mgx_abi.hip", "mgx_fused.hip", "mgx_kernels.hpp", "mgx_core.hpp", "mgx_episodes.hip")] + \
           [os.path.join(_ROOT, "include", "mgx.h")]
 FUSED_PARTS = 6            # MGX_FUSED_PARTS: slices of mgx_fused.hip (the K-step kernels), compiled in parallel
+EPISODE_PARTS = 2          # MGX_EPISODE_PARTS: slices of mgx_episodes.hip (the roll-out over in-place episodes)
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-fPIC"]
 
@@ -124,6 +125,11 @@ class EnvSlot(C.Structure):
     _fields_ = [("reward", C.c_void_p), ("done", C.c_void_p), ("obs", C.c_void_p), ("log", C.c_void_p)]
 
 
+class EpisodeStats(C.Structure):
+    """mgx_episode_stats (include/mgx.h): the per-grid statistics ``mgx_rollout_episodes`` carries (device arrays, each may be NULL)."""
+    _fields_ = [("ret_running", C.c_void_p), ("ret_sum", C.c_void_p), ("ret_last", C.c_void_p), ("episodes", C.c_void_p)]
+
+
 ENV_MAX_SLOTS = 128        # MGX_ENV_MAX_SLOTS
 
 
@@ -179,6 +185,9 @@ SYMBOLS = {
                                     C.c_void_p, C.c_void_p, C.c_void_p]),
     "mgx_rollout_discrete": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, c_i32_p, C.c_int32, C.c_int32, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # (an addition that leaves ABI_MINOR at 3: found by name)
+    "mgx_rollout_episodes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, c_i32_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.POINTER(EpisodeStats), C.c_void_p]),
     "mgx_metrics": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "mgx_reset_windows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -267,10 +276,12 @@ def _build(LIB_PATH, extra_defs, verbose, objtag, force=True, abi_only=False):
             os.makedirs(objdir, exist_ok=True)
             # translation units: the host side + small kernels, and the slices of the K-step kernels -- compiled in parallel
             units = [(SOURCES[0], [], os.path.join(objdir, "mgx_abi.o"))] + \
-                    [(SOURCES[1], [f"-DMGX_FUSED_PART={p}"], os.path.join(objdir, f"mgx_fused_{p}.o")) for p in range(FUSED_PARTS)]
+                    [(SOURCES[1], [f"-DMGX_FUSED_PART={p}"], os.path.join(objdir, f"mgx_fused_{p}.o")) for p in range(FUSED_PARTS)] + \
+                    [(SOURCES[4], [f"-DMGX_EPISODE_PART={p}"], os.path.join(objdir, f"mgx_episodes_{p}.o")) for p in range(EPISODE_PARTS)]
             if abi_only:
                 base = os.path.join(_PKG, "csrc", "_build")
-                fused = [os.path.join(base, f"mgx_fused_{p}.o") for p in range(FUSED_PARTS)]
+                fused = [os.path.join(base, f"mgx_fused_{p}.o") for p in range(FUSED_PARTS)] + \
+                        [os.path.join(base, f"mgx_episodes_{p}.o") for p in range(EPISODE_PARTS)]
                 if not all(os.path.exists(f) for f in fused):
                     raise FileNotFoundError("abi_only variants link the product build's mgx_fused objects: build() first")
                 units = units[:1]

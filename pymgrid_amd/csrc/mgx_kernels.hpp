@@ -649,6 +649,26 @@ bool launch_step_k_p0(const FusedLaunch &L); bool launch_step_k_p1(const FusedLa
 bool launch_step_k_p3(const FusedLaunch &L); bool launch_step_k_p4(const FusedLaunch &L);
 bool launch_rollout_p0(const FusedLaunch &L); bool launch_rollout_p1(const FusedLaunch &L); bool launch_rollout_p2(const FusedLaunch &L);
 bool launch_rollout_p3(const FusedLaunch &L); bool launch_rollout_p4(const FusedLaunch &L);
+// mgx_rollout_episodes: the episode form of the discrete roll-out (rollout_episodes_kernel, mgx_episodes.hip -- translation
+// units of its own, so that the lock-step kernels above are compiled exactly as before)
+enum : int { EP_SRC_FACT = 0, EP_SRC_GRID_MAJOR = 1, EP_SRC_GATHER = 2 };    // where a lane finds the rows of its series
+struct EpisodeLaunch {
+    int flags;                       // layout (template parameter F)
+    int src;                         // EP_SRC_*
+    bool per_step;
+    unsigned blocks;
+    int32_t gpb;
+    hipStream_t stream;
+    const KArgs *k;
+    const KArgs *k_dev;              // the handle's device copy of *k (what a restart reads)
+    const PLWords *tab;
+    const uint8_t *ids;              // list ids [K, N] or [N]
+    int32_t t, K;
+    FusedOut out;                    // (ret_acc and log stay NULL)
+    mgx_episode_stats stats;
+};
+constexpr int MGX_EPISODE_PARTS = 2;
+bool launch_rollout_episodes_p0(const EpisodeLaunch &L); bool launch_rollout_episodes_p1(const EpisodeLaunch &L);
 
 // ------------------------------------------------------------------------------------------------------
 // Observation of the current state (reset(), or after step_k).

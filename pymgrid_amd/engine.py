@@ -699,6 +699,53 @@ class StepEngine:
             self._t += K
         return res
 
+    EPISODE_STATS = (("ret_running", torch.float64), ("ret_sum", torch.float64), ("ret_last", torch.float64),
+                     ("episodes", torch.int32))
+
+    def rollout_episodes(self, action_id, table, K, reward=True, done=False, soc_trace=False, status_trace=False, stats=None,
+                         out=None):
+        """K fused discrete steps of a handle in in-place episodes (``reset_episodes``): every grid walks its own episode and --
+        with ``set_auto_reset`` -- restarts inside the launch, as K calls of ``step_discrete`` would leave it
+        (``mgx_rollout_episodes``).  ``action_id`` uint8 [K, N] or [N]; ``stats``: a dict with any of ``ret_running`` /
+        ``ret_sum`` / ``ret_last`` (float64 [N]) and ``episodes`` (int32 [N]), updated in place.  Returns the requested [K, N]
+        outputs."""
+        out = out or {}
+        K = int(K)
+        if action_id.dtype != torch.uint8 or action_id.device != self.device or not action_id.is_contiguous() \
+                or tuple(action_id.shape) not in ((K, self.N), (self.N,)):
+            raise ValueError(f"action_id must be a contiguous uint8 tensor [{K}, {self.N}] or [{self.N}] on {self.device}")
+        per_step = int(action_id.dim() == 2)
+        stats = stats or {}
+        unknown = set(stats) - {n for n, _ in self.EPISODE_STATS}
+        if unknown:
+            raise ValueError(f"unknown episode statistics {sorted(unknown)}")
+        st = _lib.EpisodeStats()
+        for name, dtype in self.EPISODE_STATS:
+            t = stats.get(name)
+            if t is not None and (t.dtype != dtype or t.device != self.device or not t.is_contiguous() or tuple(t.shape) != (self.N,)):
+                raise ValueError(f"stats[{name!r}] must be a contiguous {dtype} tensor [{self.N}] on {self.device}")
+            setattr(st, name, _ptr(t))
+        tptr, n_lists = self._table_ptr(table)
+        res = {}
+
+        def buf(name, want, *shape, dtype=torch.float64):
+            if not want:
+                return None
+            t = out.get(name)
+            if t is None:
+                t = self._empty(*shape, dtype=dtype)
+            res[name] = t
+            return t
+        r = buf("reward", reward, K, self.N)
+        d = buf("done", done, K, self.N, dtype=torch.uint8)
+        s = buf("soc_trace", soc_trace and self.layout.has_battery, K, self.N)
+        g = buf("status_trace", status_trace and self.layout.has_genset, K, self.N, dtype=torch.int32)
+        self._call(self._lib.mgx_rollout_episodes, _ptr(action_id), per_step, tptr, n_lists, K, _ptr(r), _ptr(d), _ptr(s), _ptr(g),
+                   C.byref(st))
+        if self._t is not None:
+            self._t += K
+        return res
+
     def rollout_lists(self, action_id, lists, K, reward=True, done=False, soc_trace=False, status_trace=False, ret_acc=None,
                       log=False, out=None):
         """K fused discrete steps with priority lists over module instances (``mgx_rollout_lists``; every layout).

@@ -578,6 +578,7 @@ class PerGridWindowEnv:
         self.starts = self.lengths = None
         self._final_bufs = None
         self._final_pos = 0
+        self.episode_stats = None          # rollout(): the per-grid episode statistics (zeroed by reset())
 
     def draw(self):
         """(starts, lengths): FixedLengthStochasticTrajectory / StochasticTrajectory draws, one per grid."""
@@ -608,6 +609,9 @@ class PerGridWindowEnv:
         max_len = self.length if self.lengths is None else int(self.lengths.max().item())
         if max_len is None:
             raise ValueError("lengths are required when the env was built without a trajectory_length")
+        if self.episode_stats is not None:
+            for v in self.episode_stats.values():
+                v.zero_()
         if self.auto_reset:      # the rings must hold the longest episode any LATER restart can draw
             L = self.full.layout
             max_len = self.length if self.length is not None else L.final_step - L.initial_step
@@ -670,6 +674,72 @@ class PerGridWindowEnv:
         if self.final_observation:
             info = dict(info, final_observation=final)
         return (new_obs if new_obs is not None else obs), reward, done, info
+
+    def _rollout_refusal(self):
+        """Why ``rollout`` is not offered on this env (None: it is)."""
+        env = self.env
+        if not isinstance(env, DiscreteBatchedMicrogridEnv):
+            return "discrete=False: the fused roll-out expands priority-list ids (continuous action streams take single steps)"
+        if not self.auto_reset:
+            return "auto_reset=False: equal-length windows step in lock-step (engine.rollout_discrete)"
+        if self.generator is not None:
+            return "a torch generator: its draws are made on the host between steps"
+        if self.full.layout.multi:
+            return "several modules of a kind per grid: single steps (the fused kernel holds one module of every kind)"
+        if env.raise_errors:
+            return "raise_errors=True: every step is preceded by its dry run"
+        if env.check_asserts:
+            return "check_asserts=True: every step is preceded by its dry run"
+        if env._keep_log:
+            return "log=True: the roll-out writes no balance log"
+        if env._views:
+            return "obs_views=True: observation views follow single steps"
+        if self.final_observation:
+            return "final_observation=True: the roll-out writes no observations"
+        if not (self.native and self._device_draws):
+            return "native=False: the roll-out steps in-place episodes"
+        return None
+
+    def rollout(self, action_id, K=None, reward=True, done=False, soc_trace=False, status_trace=False, out=None):
+        """K steps in ONE launch (``mgx_rollout_episodes``) for ``discrete=True, auto_reset=True`` with device draws and one module
+        of every kind: ``action_id`` holds priority-list ids, ``[K, N]`` (one per step) or ``[N]`` (one fixed list per grid, ``K``
+        given).  Every grid walks its episodes and restarts inside the launch exactly as K calls of ``step`` would make it; the
+        call returns the requested ``[K, N]`` tensors (``reward``, ``done``, ``soc_trace``, ``status_trace``), keeps ``starts`` /
+        ``lengths`` / ``current_steps`` current and carries the per-grid statistics ``episode_stats`` (``ret_running``,
+        ``ret_sum``, ``ret_last``, ``episodes``; zeroed by ``reset()``).  Afterwards the env stands where K steps would have left
+        it: the next ``step`` returns the rows its single-stepped twin returns."""
+        why = self._rollout_refusal()
+        if why is not None:
+            raise ValueError(f"PerGridWindowEnv.rollout is not offered with {why}")
+        if self.starts is None:
+            raise RuntimeError("rollout() before reset()")
+        env = self.env
+        e = env.engine
+        dev = self.full.device
+        if not torch.is_tensor(action_id):
+            action_id = torch.as_tensor(np.asarray(action_id), device=dev)
+        ids = action_id.to(device=dev, dtype=torch.uint8).contiguous()
+        if ids.dim() == 2:
+            if K is not None and int(K) != ids.shape[0]:
+                raise ValueError(f"action_id holds {ids.shape[0]} steps, K = {K}")
+            K = ids.shape[0]
+        elif K is None:
+            raise ValueError("one fixed id per grid: K (the number of steps) is required")
+        if self.episode_stats is None:
+            self.episode_stats = {name: torch.zeros(e.N, dtype=dtype, device=dev) for name, dtype in e.EPISODE_STATS}
+        env._unbind_fast()
+        try:
+            if env._ring is not None:
+                e.prefetch_wait()          # (a refill ahead of the counter reads the row offsets the launch rewrites)
+            res = e.rollout_episodes(ids, env._table, int(K), reward=reward, done=done, soc_trace=soc_trace,
+                                     status_trace=status_trace, stats=self.episode_stats, out=out)
+            if env._ring is not None:      # the observation rings: primed again at the grids' current rows, as after a reset
+                env._refill()
+        finally:
+            env._rebind_fast()
+        if "done" in res:
+            res["done"] = res["done"].view(torch.bool)
+        return res
 
     def _next_final_buf(self):
         """One of FINAL_BUFFERS rotating [N, D] buffers for ``info["final_observation"]`` (valid for FINAL_BUFFERS - 1 further steps)."""
@@ -817,6 +887,18 @@ class PerGridWindowFleet:
             else:
                 out.append(self._after(pe, plans[k]))
         return tuple(list(x) for x in zip(*out))
+
+    def rollout(self, action_ids, K=None, **kw):
+        """``PerGridWindowEnv.rollout`` of every bucket, one launch each, in bucket order (``action_ids``: one entry per bucket,
+        ``[K, n_k]`` or ``[n_k]``; keyword arguments as there).  Bucket k is left exactly as its twin's ``rollout`` leaves it; a bucket
+        its twin refuses is refused with the same ValueError before anything is launched.  Returns one dict per bucket."""
+        if len(action_ids) != len(self.envs):
+            raise ValueError(f"action_ids holds {len(action_ids)} entries, the fleet {len(self.envs)} buckets")
+        for k, pe in enumerate(self.envs):
+            why = pe._rollout_refusal()
+            if why is not None:
+                raise ValueError(f"PerGridWindowEnv.rollout is not offered with {why}")
+        return [pe.rollout(a, K, **kw) for pe, a in zip(self.envs, action_ids)]
 
     # ---- one bucket's PerGridWindowEnv.step, around the fleet's C call ------------------------------------------------------------
     def _before(self, pe, action, it):

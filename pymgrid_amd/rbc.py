@@ -118,8 +118,16 @@ class RuleBasedControl:
 
     def __init__(self, env, priority_list=None, remove_redundant_gensets=True):
         from .envs import BatchedMicrogridEnv
+        from .hetero import PerGridWindowEnv
+        # a PerGridWindowEnv (per-grid random episodes with automatic restarts): run_episodes() deploys the lists across restarts
+        self.episodes_env = None
+        if isinstance(env, PerGridWindowEnv):
+            why = env._rollout_refusal()
+            if why is not None:
+                raise ValueError(f"RuleBasedControl over per-grid episodes is not offered with {why}")
+            self.episodes_env, env = env, env.env
         if not isinstance(env, BatchedMicrogridEnv):
-            raise TypeError("env must be a (Discrete)BatchedMicrogridEnv")
+            raise TypeError("env must be a (Discrete)BatchedMicrogridEnv or a PerGridWindowEnv")
         self.env, self.engine, self.batch, self.layout = env, env.engine, env.batch, env.layout
         L = self.layout
         self._instances = L.n_genset > 1 or L.n_battery > 1 or L.n_grid > 1
@@ -222,6 +230,35 @@ class RuleBasedControl:
             if saved is not None:
                 self.batch.load_state(saved)
             self.env._after_external_steps()              # the env's observation rings follow the counter again
+
+    def run_episodes(self, steps, chunk=512, reward=False, done=False, soc_trace=False, status_trace=False, reset=True):
+        """The priority lists deployed for ``steps`` steps over per-grid random episodes (``RuleBasedControl(PerGridWindowEnv(...,
+        discrete=True, auto_reset=True))``): every grid restarts on its own whenever its episode ends, inside the fused launches
+        (``mgx_rollout_episodes``, ``chunk`` steps each).  ``reset=True`` draws the first episodes (and zeroes the statistics)
+        first.  Returns ``episode_return_sum`` / ``episode_return_last`` / ``episodes`` / ``return_running`` ([N]: the env's
+        ``episode_stats``, which carry on into a later call with ``reset=False``) and the per-step outputs asked for ([steps, N])."""
+        pe = self.episodes_env
+        if pe is None:
+            raise TypeError("run_episodes needs RuleBasedControl(PerGridWindowEnv(..., discrete=True, auto_reset=True)); "
+                            "run() is the lock-step episode")
+        if reset:
+            pe.reset()
+        parts = {}
+        left = int(steps)
+        while left > 0:
+            k = min(int(chunk), left)
+            out = pe.rollout(self._ids_dev, k, reward=reward, done=done, soc_trace=soc_trace, status_trace=status_trace)
+            for name, v in out.items():
+                parts.setdefault(name, []).append(v)
+            left -= k
+        res = {name: torch.cat(v) for name, v in parts.items()}
+        if pe.episode_stats is None:              # (steps == 0)
+            pe.episode_stats = {name: torch.zeros(self.layout.n_grids, dtype=dtype, device=self.batch.device)
+                                for name, dtype in self.engine.EPISODE_STATS}
+        st = pe.episode_stats
+        res.update(episode_return_sum=st["ret_sum"], episode_return_last=st["ret_last"], episodes=st["episodes"],
+                   return_running=st["ret_running"])
+        return res
 
     def _run(self, total, chunk, log, soc_trace, reward):
         L = self.layout
