@@ -539,6 +539,22 @@ int mgx_rollout_episodes(mgx_handle *h, const uint8_t *action_id, int per_step, 
                          int32_t K, double *reward, uint8_t *done, double *soc_trace, uint32_t *status_trace,
                          const mgx_episode_stats *stats, mgx_stream stream);
 
+/* The fused CONTINUOUS K-step over per-grid IN-PLACE episodes (mgx_reset_episodes): K consecutive Microgrid.run(control, normalized)
+ * steps (microgrid.py:227-325) in one launch, every grid on the rows of its own FixedLengthStochasticTrajectory /
+ * StochasticTrajectory episode (trajectory/stochastic.py) and -- with mgx_set_auto_reset -- restarting inside the launch whenever a
+ * step ends its episode, with the draw, the offsets and the start / length / t0 arrays exactly as K calls of mgx_step would leave
+ * them.  actions [K, N, A] in the handle's action format (mgx_set_action_format; may be NULL for a layout without a controllable
+ * module, A = 0): row k belongs to step k of the call, whatever episode a grid is in.  `normalized` and the reward shaper as in
+ * mgx_step.  reward / done (bytes) / soc_trace / status_trace [K, N] and `stats` (the struct pointer too; the statistics of
+ * mgx_rollout_episodes, by the same rule) may be NULL.  No observations and no balance log are written.  The counter moves by K.
+ * MGX_ERR_INVALID: NULL handle / actions, K <= 0, the handle does not step in-place episodes (lock-step: mgx_step_k).
+ * MGX_ERR_UNSUPPORTED: several modules of a kind, shards, device-counter mode, `done` as bit sets with done != NULL,
+ * mgx_set_final_obs set.  MGX_ERR_RANGE: the counter would leave its range.  Nothing is launched when the call is refused.
+ * An ADDITION to ABI 9 that leaves MGX_ABI_MINOR at 3: consumers find it by name (dlsym); mgx_step_k keeps refusing handles in
+ * this mode. */
+int mgx_step_k_episodes(mgx_handle *h, const void *actions, int32_t K, int normalized, double *reward, uint8_t *done,
+                        double *soc_trace, uint32_t *status_trace, const mgx_episode_stats *stats, mgx_stream stream);
+
 /* raise_errors=True (BaseMicrogridModule.__init__, base_module.py:40; as_source / as_sink, :213-224,265-270; _raise_error,
  * :79-93): the reference refuses a request a module cannot meet with a ValueError instead of clipping it.  mgx_step always
  * clips; mgx_check_step is its DRY RUN -- the same arithmetic on a register copy of the state, nothing stored, the counter

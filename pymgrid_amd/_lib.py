@@ -13,10 +13,12 @@ import sys
 _PKG = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_PKG)
 LIB_PATH = os.environ.get("MGX_LIB") or os.path.join(_PKG, "libmgx.so")   # MGX_LIB: A/B kernel variants
-SOURCES = [os.path.join(_PKG, "csrc", f) for f in ("mgx_abi.hip", "mgx_fused.hip", "mgx_kernels.hpp", "mgx_core.hpp", "mgx_episodes.hip")] + \
+SOURCES = [os.path.join(_PKG, "csrc", f) for f in ("mgx_abi.hip", "mgx_fused.hip", "mgx_kernels.hpp", "mgx_core.hpp", "mgx_episodes.hip",
+                                                      "mgx_step_episodes.hip")] + \
           [os.path.join(_ROOT, "include", "mgx.h")]
 FUSED_PARTS = 6            # MGX_FUSED_PARTS: slices of mgx_fused.hip (the K-step kernels), compiled in parallel
 EPISODE_PARTS = 2          # MGX_EPISODE_PARTS: slices of mgx_episodes.hip (the roll-out over in-place episodes)
+STEP_EPISODE_PARTS = 2     # MGX_STEP_EPISODE_PARTS: slices of mgx_step_episodes.hip (the continuous K-step over in-place episodes)
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-fPIC"]
 
@@ -188,6 +190,8 @@ SYMBOLS = {
     # (an addition that leaves ABI_MINOR at 3: found by name)
     "mgx_rollout_episodes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, c_i32_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.POINTER(EpisodeStats), C.c_void_p]),
+    "mgx_step_k_episodes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.POINTER(EpisodeStats), C.c_void_p]),
     "mgx_metrics": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "mgx_reset_windows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -277,11 +281,13 @@ def _build(LIB_PATH, extra_defs, verbose, objtag, force=True, abi_only=False):
             # translation units: the host side + small kernels, and the slices of the K-step kernels -- compiled in parallel
             units = [(SOURCES[0], [], os.path.join(objdir, "mgx_abi.o"))] + \
                     [(SOURCES[1], [f"-DMGX_FUSED_PART={p}"], os.path.join(objdir, f"mgx_fused_{p}.o")) for p in range(FUSED_PARTS)] + \
-                    [(SOURCES[4], [f"-DMGX_EPISODE_PART={p}"], os.path.join(objdir, f"mgx_episodes_{p}.o")) for p in range(EPISODE_PARTS)]
+                    [(SOURCES[4], [f"-DMGX_EPISODE_PART={p}"], os.path.join(objdir, f"mgx_episodes_{p}.o")) for p in range(EPISODE_PARTS)] + \
+                    [(SOURCES[5], [f"-DMGX_STEP_EPISODE_PART={p}"], os.path.join(objdir, f"mgx_step_episodes_{p}.o")) for p in range(STEP_EPISODE_PARTS)]
             if abi_only:
                 base = os.path.join(_PKG, "csrc", "_build")
                 fused = [os.path.join(base, f"mgx_fused_{p}.o") for p in range(FUSED_PARTS)] + \
-                        [os.path.join(base, f"mgx_episodes_{p}.o") for p in range(EPISODE_PARTS)]
+                        [os.path.join(base, f"mgx_episodes_{p}.o") for p in range(EPISODE_PARTS)] + \
+                        [os.path.join(base, f"mgx_step_episodes_{p}.o") for p in range(STEP_EPISODE_PARTS)]
                 if not all(os.path.exists(f) for f in fused):
                     raise FileNotFoundError("abi_only variants link the product build's mgx_fused objects: build() first")
                 units = units[:1]

@@ -2017,6 +2017,47 @@ int mgx_rollout_episodes(mgx_handle *h, const uint8_t *action_id, int per_step, 
     return MGX_OK;
 }
 
+// The continuous K-step over in-place episodes: one launch of step_k_episodes_kernel (mgx_step_episodes.hip), every check before it.
+int mgx_step_k_episodes(mgx_handle *h, const void *actions, int32_t K, int normalized, double *reward, uint8_t *done,
+                        double *soc_trace, uint32_t *status_trace, const mgx_episode_stats *stats, mgx_stream stream)
+{
+    g_err[0] = 0;
+    if (!h || (h->action_dim > 0 && !actions)) return fail(MGX_ERR_INVALID, "mgx_step_k_episodes: NULL argument");
+    if (K <= 0) return fail(MGX_ERR_INVALID, "mgx_step_k_episodes: K must be positive");
+    if (h->multi) return fail(MGX_ERR_UNSUPPORTED, "mgx_step_k_episodes: needs exactly one module of every kind per grid "
+                                                    "(several: single steps, mgx_step)");
+    if (h->n_shards > 1) return fail(MGX_ERR_UNSUPPORTED, "mgx_step_k_episodes: not offered while the handle steps in shards");
+    if (dev_counter(h)) return fail(MGX_ERR_UNSUPPORTED, "mgx_step_k_episodes: not offered in device-counter mode");
+    if (!h->inplace || !h->k.ep_off || !h->k.ep_final)
+        return fail(MGX_ERR_INVALID, "mgx_step_k_episodes: the handle is not stepping in-place episodes (mgx_reset_episodes); "
+                                     "lock-step episodes: mgx_step_k");
+    if (h->k.done_bits && done) return fail(MGX_ERR_UNSUPPORTED, "mgx_step_k_episodes: `done` is written as bytes (mgx_set_done_format)");
+    if (h->k.final_obs) return fail(MGX_ERR_UNSUPPORTED, "mgx_step_k_episodes: mgx_set_final_obs is set but the call writes no observations");
+    if (h->t < 0 || (int64_t)h->t + K > step_limit(h))
+        return fail(MGX_ERR_RANGE, "mgx_step_k_episodes: steps [%d, %d) leave the counter's range", h->t, h->t + K);
+    StepEpisodeLaunch L;
+    L.flags = h->flags;
+    L.src = factorised(h->k.c) ? EP_SRC_FACT : (h->k.pm_pitch ? EP_SRC_GRID_MAJOR : EP_SRC_GATHER);
+    if (L.src == EP_SRC_FACT && !h->k.pm_pitch)
+        return fail(MGX_ERR_INVALID, "mgx_step_k_episodes: the handle holds no profile-major base tables");
+    L.act_f32 = h->k.act_f32 != 0;
+    L.gpb = fused_grids_per_block(h, h->k.N);
+    L.blocks = (unsigned)((h->k.N + L.gpb - 1) / L.gpb);
+    L.stream = (hipStream_t)stream;
+    // what a restart reads (the draw's arguments, the episode arrays) comes from the handle's device copy of the KArgs
+    if (int rc = sync_device_kargs(h, L.stream, "mgx_step_k_episodes: uploading the kernel arguments")) return rc;
+    L.k = &h->k; L.k_dev = h->d_kargs; L.actions = actions;
+    L.t = h->t; L.K = K; L.normalized = normalized;
+    L.out = FusedOut{reward, done, soc_trace, status_trace, nullptr, nullptr};
+    L.stats = stats ? *stats : mgx_episode_stats{nullptr, nullptr, nullptr, nullptr};
+    if (!(launch_step_k_episodes_p0(L) || launch_step_k_episodes_p1(L)))
+        return fail(MGX_ERR_UNSUPPORTED, "mgx_step_k_episodes: no kernel for layout flags %d", h->flags);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, "step_k_episodes_kernel launch");
+    advance(h, K, L.stream);
+    return MGX_OK;
+}
+
 int mgx_rollout_lists(mgx_handle *h, const int32_t *action_id, int per_step, const int32_t *lists, int32_t n_lists, int32_t list_len,
                       int32_t K, double *reward, uint8_t *done, double *soc_trace, uint32_t *status_trace, double *ret_acc,
                       double *log, mgx_stream stream)

@@ -669,6 +669,25 @@ struct EpisodeLaunch {
 };
 constexpr int MGX_EPISODE_PARTS = 2;
 bool launch_rollout_episodes_p0(const EpisodeLaunch &L); bool launch_rollout_episodes_p1(const EpisodeLaunch &L);
+// mgx_step_k_episodes: the continuous K-step over in-place episodes (step_k_episodes_kernel, mgx_step_episodes.hip -- again
+// translation units of its own)
+struct StepEpisodeLaunch {
+    int flags;                       // layout (template parameter F)
+    int src;                         // EP_SRC_*
+    bool act_f32;
+    unsigned blocks;
+    int32_t gpb;
+    hipStream_t stream;
+    const KArgs *k;
+    const KArgs *k_dev;              // the handle's device copy of *k (what a restart reads)
+    const void *actions;             // controls [K, N, A] in the handle's action format
+    int32_t t, K;
+    int normalized;
+    FusedOut out;                    // (ret_acc and log stay NULL)
+    mgx_episode_stats stats;
+};
+constexpr int MGX_STEP_EPISODE_PARTS = 2;
+bool launch_step_k_episodes_p0(const StepEpisodeLaunch &L); bool launch_step_k_episodes_p1(const StepEpisodeLaunch &L);
 
 // ------------------------------------------------------------------------------------------------------
 // Observation of the current state (reset(), or after step_k).

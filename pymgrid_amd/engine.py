@@ -746,6 +746,45 @@ class StepEngine:
             self._t += K
         return res
 
+    def step_k_episodes(self, actions, normalized=True, reward=True, done=False, soc_trace=False, status_trace=False, stats=None,
+                        out=None):
+        """K fused continuous steps (actions [K, N, A]) of a handle in in-place episodes (``reset_episodes``): every grid walks its
+        own episode and -- with ``set_auto_reset`` -- restarts inside the launch, as K calls of ``step`` would leave it
+        (``mgx_step_k_episodes``).  Row k of ``actions`` belongs to step k whatever episode a grid is in; ``stats`` as for
+        ``rollout_episodes``.  Returns the requested [K, N] outputs."""
+        out = out or {}
+        K = int(actions.shape[0]) if actions is not None else int(out["K"])
+        actions = self._check_actions(actions, (K,))
+        stats = stats or {}
+        unknown = set(stats) - {n for n, _ in self.EPISODE_STATS}
+        if unknown:
+            raise ValueError(f"unknown episode statistics {sorted(unknown)}")
+        st = _lib.EpisodeStats()
+        for name, dtype in self.EPISODE_STATS:
+            t = stats.get(name)
+            if t is not None and (t.dtype != dtype or t.device != self.device or not t.is_contiguous() or tuple(t.shape) != (self.N,)):
+                raise ValueError(f"stats[{name!r}] must be a contiguous {dtype} tensor [{self.N}] on {self.device}")
+            setattr(st, name, _ptr(t))
+        res = {}
+
+        def buf(name, want, *shape, dtype=torch.float64):
+            if not want:
+                return None
+            t = out.get(name)
+            if t is None:
+                t = self._empty(*shape, dtype=dtype)
+            res[name] = t
+            return t
+        r = buf("reward", reward, K, self.N)
+        d = buf("done", done, K, self.N, dtype=torch.uint8)
+        s = buf("soc_trace", soc_trace and self.layout.has_battery, K, self.N)
+        g = buf("status_trace", status_trace and self.layout.has_genset, K, self.N, dtype=torch.int32)
+        self._call(self._lib.mgx_step_k_episodes, _ptr(actions), K, 1 if normalized else 0, _ptr(r), _ptr(d), _ptr(s), _ptr(g),
+                   C.byref(st))
+        if self._t is not None:
+            self._t += K
+        return res
+
     def rollout_lists(self, action_id, lists, K, reward=True, done=False, soc_trace=False, status_trace=False, ret_acc=None,
                       log=False, out=None):
         """K fused discrete steps with priority lists over module instances (``mgx_rollout_lists``; every layout).

@@ -578,7 +578,7 @@ class PerGridWindowEnv:
         self.starts = self.lengths = None
         self._final_bufs = None
         self._final_pos = 0
-        self.episode_stats = None          # rollout(): the per-grid episode statistics (zeroed by reset())
+        self.episode_stats = None          # rollout() / step_k(): the per-grid episode statistics (zeroed by reset())
 
     def draw(self):
         """(starts, lengths): FixedLengthStochasticTrajectory / StochasticTrajectory draws, one per grid."""
@@ -679,7 +679,7 @@ class PerGridWindowEnv:
         """Why ``rollout`` is not offered on this env (None: it is)."""
         env = self.env
         if not isinstance(env, DiscreteBatchedMicrogridEnv):
-            return "discrete=False: the fused roll-out expands priority-list ids (continuous action streams take single steps)"
+            return "discrete=False: the fused roll-out expands priority-list ids (continuous action streams: use step_k)"
         if not self.auto_reset:
             return "auto_reset=False: equal-length windows step in lock-step (engine.rollout_discrete)"
         if self.generator is not None:
@@ -733,6 +733,63 @@ class PerGridWindowEnv:
                 e.prefetch_wait()          # (a refill ahead of the counter reads the row offsets the launch rewrites)
             res = e.rollout_episodes(ids, env._table, int(K), reward=reward, done=done, soc_trace=soc_trace,
                                      status_trace=status_trace, stats=self.episode_stats, out=out)
+            if env._ring is not None:      # the observation rings: primed again at the grids' current rows, as after a reset
+                env._refill()
+        finally:
+            env._rebind_fast()
+        if "done" in res:
+            res["done"] = res["done"].view(torch.bool)
+        return res
+
+    def _step_k_refusal(self):
+        """Why ``step_k`` is not offered on this env (None: it is)."""
+        env = self.env
+        if isinstance(env, DiscreteBatchedMicrogridEnv):
+            return "discrete=True: priority-list ids are expanded in the kernel (use rollout)"
+        if not self.auto_reset:
+            return "auto_reset=False: equal-length windows step in lock-step (engine.step_k)"
+        if self.generator is not None:
+            return "a torch generator: its draws are made on the host between steps"
+        if self.full.layout.multi:
+            return "several modules of a kind per grid: single steps (the fused kernel holds one module of every kind)"
+        if env.raise_errors:
+            return "raise_errors=True: every step is preceded by its dry run"
+        if env._keep_log:
+            return "log=True: the fused step writes no balance log"
+        if env._views:
+            return "obs_views=True: observation views follow single steps"
+        if self.final_observation:
+            return "final_observation=True: the fused step writes no observations"
+        if not (self.native and self._device_draws):
+            return "native=False: the fused step walks in-place episodes"
+        return None
+
+    def step_k(self, actions, normalized=True, reward=True, done=False, soc_trace=False, status_trace=False, out=None):
+        """K continuous steps in ONE launch (``mgx_step_k_episodes``) for ``discrete=False, auto_reset=True`` with device draws and one
+        module of every kind: ``actions`` ``[K, N, A]`` of the env's ``action_dtype`` (columns ``layout.action_names``), row k the
+        control of step k whatever episode a grid is in.  Every grid walks its episodes and restarts inside the launch exactly as K
+        calls of ``step(actions[k], normalized)`` would make it; the call returns the requested ``[K, N]`` tensors (``reward``,
+        ``done``, ``soc_trace``, ``status_trace``), keeps ``starts`` / ``lengths`` / ``current_steps`` current and carries the
+        per-grid statistics ``episode_stats`` (``ret_running``, ``ret_sum``, ``ret_last``, ``episodes``; zeroed by ``reset()``).
+        Afterwards the env stands where K steps would have left it: the next ``step`` returns the rows its single-stepped twin returns."""
+        why = self._step_k_refusal()
+        if why is not None:
+            raise ValueError(f"PerGridWindowEnv.step_k is not offered with {why}")
+        if self.starts is None:
+            raise RuntimeError("step_k() before reset()")
+        env = self.env
+        e = env.engine
+        if not torch.is_tensor(actions) or actions.dim() != 3:
+            raise ValueError(f"actions must be a {e.action_dtype} tensor of shape (K, {e.N}, {e.action_dim}) on {e.device}")
+        e._check_actions(actions, (int(actions.shape[0]),))
+        if self.episode_stats is None:
+            self.episode_stats = {name: torch.zeros(e.N, dtype=dtype, device=e.device) for name, dtype in e.EPISODE_STATS}
+        env._unbind_fast()
+        try:
+            if env._ring is not None:
+                e.prefetch_wait()          # (a refill ahead of the counter reads the row offsets the launch rewrites)
+            res = e.step_k_episodes(actions, normalized=normalized, reward=reward, done=done, soc_trace=soc_trace,
+                                    status_trace=status_trace, stats=self.episode_stats, out=out)
             if env._ring is not None:      # the observation rings: primed again at the grids' current rows, as after a reset
                 env._refill()
         finally:
@@ -899,6 +956,21 @@ class PerGridWindowFleet:
             if why is not None:
                 raise ValueError(f"PerGridWindowEnv.rollout is not offered with {why}")
         return [pe.rollout(a, K, **kw) for pe, a in zip(self.envs, action_ids)]
+
+    def step_k(self, actions_list, **kw):
+        """``PerGridWindowEnv.step_k`` of every bucket, one launch each, in bucket order (``actions_list``: one ``[K, n_k, A_k]`` tensor
+        per bucket; keyword arguments as there).  Bucket k is left exactly as its twin's ``step_k`` leaves it; a bucket its twin
+        refuses is refused with the same ValueError before anything is launched.  Returns one dict per bucket."""
+        if len(actions_list) != len(self.envs):
+            raise ValueError(f"actions_list holds {len(actions_list)} entries, the fleet {len(self.envs)} buckets")
+        for pe, a in zip(self.envs, actions_list):
+            why = pe._step_k_refusal()
+            if why is not None:
+                raise ValueError(f"PerGridWindowEnv.step_k is not offered with {why}")
+            if not torch.is_tensor(a) or a.dim() != 3:
+                raise ValueError("every entry of actions_list must be a [K, n_k, A_k] tensor")
+            pe.env.engine._check_actions(a, (int(a.shape[0]),))
+        return [pe.step_k(a, **kw) for pe, a in zip(self.envs, actions_list)]
 
     # ---- one bucket's PerGridWindowEnv.step, around the fleet's C call ------------------------------------------------------------
     def _before(self, pe, action, it):
