@@ -555,6 +555,44 @@ int mgx_rollout_episodes(mgx_handle *h, const uint8_t *action_id, int per_step, 
 int mgx_step_k_episodes(mgx_handle *h, const void *actions, int32_t K, int normalized, double *reward, uint8_t *done,
                         double *soc_trace, uint32_t *status_trace, const mgx_episode_stats *stats, mgx_stream stream);
 
+/* The observation rows of a fused launch over in-place episodes (mgx_rollout_episodes_rows, mgx_step_k_episodes_rows): whole
+ * H = 0 rows [K, N, D] in the handle's observation format (mgx_set_obs_format), D = mgx_obs_dim.  Each pointer may be NULL.
+ *     obs[k, i, :]        the observation step k returned for grid i: the post-step state over the series row the grid stands on
+ *                         after the step -- the first row of its new episode where the step restarted it (what `obs` of K calls
+ *                         of mgx_step holds, one after the other)
+ *     final_obs[k, i, :]  written ONLY where step k restarted grid i (mgx_set_auto_reset on, done[k, i] set): the row before the
+ *                         restart, what mgx_set_final_obs receives from a single step.  Every other entry keeps the caller's bytes. */
+typedef struct mgx_episode_rows {
+    int32_t struct_size;   /* = sizeof(mgx_episode_rows) */
+    int32_t reserved;
+    void *obs;             /* [K, N, D] in the handle's observation format, or NULL */
+    void *final_obs;       /* [K, N, D], written only where a grid restarts at step k, or NULL */
+} mgx_episode_rows;
+
+/* mgx_rollout_episodes + the observation every step returned (MicrogridEnv.step's observation, envs/base/base.py:169-209) and the
+ * last observation of every episode that ends inside the launch, before the restart replaces it with the reset observation
+ * (Microgrid.reset, microgrid.py:205-225): one launch of a kernel of its own (rollout_episodes_rows_kernel).  Every argument but
+ * `rows` as in mgx_rollout_episodes, everything that call leaves (state, counter, episode arrays, statistics, the [K, N] outputs)
+ * is left bit for bit the same; a row equals the row of the single step bit for bit.  rows == NULL, or both of its pointers NULL:
+ * the call IS mgx_rollout_episodes (forwarded; the rows kernel is not launched).
+ * MGX_ERR_INVALID: NULL handle, rows->struct_size != sizeof(mgx_episode_rows), and what mgx_rollout_episodes refuses so.
+ * MGX_ERR_UNSUPPORTED: a forecast horizon (H != 0), an observation mode other than whole rows (mgx_set_obs_mode), mgx_set_final_obs
+ * set (its per-step [N, D] buffer has no meaning across K steps), and what mgx_rollout_episodes refuses so.  MGX_ERR_RANGE as
+ * mgx_rollout_episodes.  Nothing is launched when the call is refused.
+ * An ADDITION to ABI 9 that leaves MGX_ABI_MINOR at 3: consumers find it by name (dlsym). */
+int mgx_rollout_episodes_rows(mgx_handle *h, const uint8_t *action_id, int per_step, const int32_t *table, int32_t n_actions,
+                              int32_t K, double *reward, uint8_t *done, double *soc_trace, uint32_t *status_trace,
+                              const mgx_episode_stats *stats, const mgx_episode_rows *rows, mgx_stream stream);
+
+/* mgx_step_k_episodes + the observation every step returned (MicrogridEnv.step's observation, envs/base/base.py:169-209) and the
+ * last observation of every episode that ends inside the launch (before Microgrid.reset, microgrid.py:205-225, replaces it): one
+ * launch of step_k_episodes_rows_kernel.  Every argument but `rows` as in mgx_step_k_episodes; forwarding, results and refusals
+ * by the rules of mgx_rollout_episodes_rows, with mgx_step_k_episodes in the place of mgx_rollout_episodes.
+ * An ADDITION to ABI 9 that leaves MGX_ABI_MINOR at 3: consumers find it by name (dlsym). */
+int mgx_step_k_episodes_rows(mgx_handle *h, const void *actions, int32_t K, int normalized, double *reward, uint8_t *done,
+                             double *soc_trace, uint32_t *status_trace, const mgx_episode_stats *stats,
+                             const mgx_episode_rows *rows, mgx_stream stream);
+
 /* raise_errors=True (BaseMicrogridModule.__init__, base_module.py:40; as_source / as_sink, :213-224,265-270; _raise_error,
  * :79-93): the reference refuses a request a module cannot meet with a ValueError instead of clipping it.  mgx_step always
  * clips; mgx_check_step is its DRY RUN -- the same arithmetic on a register copy of the state, nothing stored, the counter

@@ -15,10 +15,13 @@ _ROOT = os.path.dirname(_PKG)
 LIB_PATH = os.environ.get("MGX_LIB") or os.path.join(_PKG, "libmgx.so")   # MGX_LIB: A/B kernel variants
 SOURCES = [os.path.join(_PKG, "csrc", f) for f in ("mgx_abi.hip", "mgx_fused.hip", "mgx_kernels.hpp", "mgx_core.hpp", "mgx_episodes.hip",
                                                       "mgx_step_episodes.hip")] + \
-          [os.path.join(_ROOT, "include", "mgx.h")]
+          [os.path.join(_ROOT, "include", "mgx.h")] + \
+          [os.path.join(_PKG, "csrc", f) for f in ("mgx_episode_rows.hip", "mgx_step_episode_rows.hip", "mgx_episode_rows.hpp")]
 FUSED_PARTS = 6            # MGX_FUSED_PARTS: slices of mgx_fused.hip (the K-step kernels), compiled in parallel
 EPISODE_PARTS = 2          # MGX_EPISODE_PARTS: slices of mgx_episodes.hip (the roll-out over in-place episodes)
 STEP_EPISODE_PARTS = 2     # MGX_STEP_EPISODE_PARTS: slices of mgx_step_episodes.hip (the continuous K-step over in-place episodes)
+EPISODE_ROWS_PARTS = 2     # MGX_EPISODE_ROWS_PARTS: slices of mgx_episode_rows.hip (the roll-out over in-place episodes with rows)
+STEP_EPISODE_ROWS_PARTS = 2    # MGX_STEP_EPISODE_ROWS_PARTS: slices of mgx_step_episode_rows.hip (the continuous twin)
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-fPIC"]
 
@@ -127,6 +130,12 @@ class EnvSlot(C.Structure):
     _fields_ = [("reward", C.c_void_p), ("done", C.c_void_p), ("obs", C.c_void_p), ("log", C.c_void_p)]
 
 
+class EpisodeRows(C.Structure):
+    """mgx_episode_rows (include/mgx.h): the observation rows ``mgx_rollout_episodes_rows`` / ``mgx_step_k_episodes_rows`` write
+    ([K, N, D] device arrays in the handle's observation format, each may be NULL)."""
+    _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32), ("obs", C.c_void_p), ("final_obs", C.c_void_p)]
+
+
 class EpisodeStats(C.Structure):
     """mgx_episode_stats (include/mgx.h): the per-grid statistics ``mgx_rollout_episodes`` carries (device arrays, each may be NULL)."""
     _fields_ = [("ret_running", C.c_void_p), ("ret_sum", C.c_void_p), ("ret_last", C.c_void_p), ("episodes", C.c_void_p)]
@@ -192,6 +201,10 @@ SYMBOLS = {
                                        C.c_void_p, C.c_void_p, C.POINTER(EpisodeStats), C.c_void_p]),
     "mgx_step_k_episodes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.POINTER(EpisodeStats), C.c_void_p]),
+    "mgx_rollout_episodes_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, c_i32_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.POINTER(EpisodeStats), C.POINTER(EpisodeRows), C.c_void_p]),
+    "mgx_step_k_episodes_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.POINTER(EpisodeStats), C.POINTER(EpisodeRows), C.c_void_p]),
     "mgx_metrics": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "mgx_reset_windows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -282,12 +295,17 @@ def _build(LIB_PATH, extra_defs, verbose, objtag, force=True, abi_only=False):
             units = [(SOURCES[0], [], os.path.join(objdir, "mgx_abi.o"))] + \
                     [(SOURCES[1], [f"-DMGX_FUSED_PART={p}"], os.path.join(objdir, f"mgx_fused_{p}.o")) for p in range(FUSED_PARTS)] + \
                     [(SOURCES[4], [f"-DMGX_EPISODE_PART={p}"], os.path.join(objdir, f"mgx_episodes_{p}.o")) for p in range(EPISODE_PARTS)] + \
-                    [(SOURCES[5], [f"-DMGX_STEP_EPISODE_PART={p}"], os.path.join(objdir, f"mgx_step_episodes_{p}.o")) for p in range(STEP_EPISODE_PARTS)]
+                    [(SOURCES[5], [f"-DMGX_STEP_EPISODE_PART={p}"], os.path.join(objdir, f"mgx_step_episodes_{p}.o")) for p in range(STEP_EPISODE_PARTS)] + \
+                    [(SOURCES[7], [f"-DMGX_EPISODE_ROWS_PART={p}"], os.path.join(objdir, f"mgx_episode_rows_{p}.o")) for p in range(EPISODE_ROWS_PARTS)] + \
+                    [(SOURCES[8], [f"-DMGX_STEP_EPISODE_ROWS_PART={p}"], os.path.join(objdir, f"mgx_step_episode_rows_{p}.o"))
+                     for p in range(STEP_EPISODE_ROWS_PARTS)]
             if abi_only:
                 base = os.path.join(_PKG, "csrc", "_build")
                 fused = [os.path.join(base, f"mgx_fused_{p}.o") for p in range(FUSED_PARTS)] + \
                         [os.path.join(base, f"mgx_episodes_{p}.o") for p in range(EPISODE_PARTS)] + \
-                        [os.path.join(base, f"mgx_step_episodes_{p}.o") for p in range(STEP_EPISODE_PARTS)]
+                        [os.path.join(base, f"mgx_step_episodes_{p}.o") for p in range(STEP_EPISODE_PARTS)] + \
+                        [os.path.join(base, f"mgx_episode_rows_{p}.o") for p in range(EPISODE_ROWS_PARTS)] + \
+                        [os.path.join(base, f"mgx_step_episode_rows_{p}.o") for p in range(STEP_EPISODE_ROWS_PARTS)]
                 if not all(os.path.exists(f) for f in fused):
                     raise FileNotFoundError("abi_only variants link the product build's mgx_fused objects: build() first")
                 units = units[:1]

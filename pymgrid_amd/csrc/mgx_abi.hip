@@ -4,6 +4,7 @@
 //   hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -c mgx_abi.hip ; ... -c -DMGX_FUSED_PART=p mgx_fused.hip (p = 0..4)
 //   hipcc --offload-arch=gfx950 -fPIC -shared *.o -o libmgx.so
 #include "mgx_kernels.hpp"
+#include "mgx_episode_rows.hpp"
 
 #include <cstdarg>
 #include <cstdio>
@@ -1973,32 +1974,53 @@ int mgx_rollout_discrete(mgx_handle *h, const uint8_t *action_id, int per_step, 
     return MGX_OK;
 }
 
-// The roll-out over in-place episodes: one launch of rollout_episodes_kernel (mgx_episodes.hip), every check before it.
-int mgx_rollout_episodes(mgx_handle *h, const uint8_t *action_id, int per_step, const int32_t *table, int32_t n_actions,
-                         int32_t K, double *reward, uint8_t *done, double *soc_trace, uint32_t *status_trace,
-                         const mgx_episode_stats *stats, mgx_stream stream)
+// What the fused launches over in-place episodes refuse, the plain calls and the ones with rows alike (`fn`: the call, for the message)
+static int episodes_launch_refusal(mgx_handle *h, int32_t K, const uint8_t *done, const char *fn, const char *lockstep, const char *single)
 {
-    g_err[0] = 0;
-    if (!h || !action_id || !table) return fail(MGX_ERR_INVALID, "mgx_rollout_episodes: NULL argument");
-    if (K <= 0) return fail(MGX_ERR_INVALID, "mgx_rollout_episodes: K must be positive");
-    if (h->multi) return fail(MGX_ERR_UNSUPPORTED, "mgx_rollout_episodes: needs exactly one module of every kind per grid "
-                                                    "(several: single steps, mgx_step_lists)");
-    if (h->n_shards > 1) return fail(MGX_ERR_UNSUPPORTED, "mgx_rollout_episodes: not offered while the handle steps in shards");
-    if (dev_counter(h)) return fail(MGX_ERR_UNSUPPORTED, "mgx_rollout_episodes: not offered in device-counter mode");
+    if (K <= 0) return fail(MGX_ERR_INVALID, "%s: K must be positive", fn);
+    if (h->multi) return fail(MGX_ERR_UNSUPPORTED, "%s: needs exactly one module of every kind per grid (several: single steps, %s)", fn, single);
+    if (h->n_shards > 1) return fail(MGX_ERR_UNSUPPORTED, "%s: not offered while the handle steps in shards", fn);
+    if (dev_counter(h)) return fail(MGX_ERR_UNSUPPORTED, "%s: not offered in device-counter mode", fn);
     if (!h->inplace || !h->k.ep_off || !h->k.ep_final)
-        return fail(MGX_ERR_INVALID, "mgx_rollout_episodes: the handle is not stepping in-place episodes (mgx_reset_episodes); "
-                                     "lock-step episodes: mgx_rollout_discrete");
-    if (h->k.done_bits && done) return fail(MGX_ERR_UNSUPPORTED, "mgx_rollout_episodes: `done` is written as bytes (mgx_set_done_format)");
-    if (h->k.final_obs) return fail(MGX_ERR_UNSUPPORTED, "mgx_rollout_episodes: mgx_set_final_obs is set but the call writes no observations");
+        return fail(MGX_ERR_INVALID, "%s: the handle is not stepping in-place episodes (mgx_reset_episodes); lock-step episodes: %s", fn, lockstep);
+    if (h->k.done_bits && done) return fail(MGX_ERR_UNSUPPORTED, "%s: `done` is written as bytes (mgx_set_done_format)", fn);
+    return MGX_OK;
+}
+
+// ... and what the calls with rows refuse on top (before anything is launched)
+static int episode_rows_refusal(mgx_handle *h, const mgx_episode_rows *rows, const char *fn)
+{
+    if (rows->struct_size != (int32_t)sizeof(mgx_episode_rows))
+        return fail(MGX_ERR_INVALID, "%s: rows->struct_size is %d, sizeof(mgx_episode_rows) is %d", fn, rows->struct_size, (int)sizeof(mgx_episode_rows));
+    if (h->k.H != 0) return fail(MGX_ERR_UNSUPPORTED, "%s: rows inside the launch are whole H = 0 rows (the handle has a forecast horizon of %d)", fn, h->k.H);
+    if (h->k.obs_state_only) return fail(MGX_ERR_UNSUPPORTED, "%s: rows inside the launch are whole rows (mgx_set_obs_mode is state-only)", fn);
+    if (h->k.final_obs) return fail(MGX_ERR_UNSUPPORTED, "%s: mgx_set_final_obs is set; its [N, D] buffer has no meaning across K steps "
+                                                          "(rows->final_obs receives the rows before the restarts)", fn);
+    return MGX_OK;
+}
+
+// The roll-out over in-place episodes: one launch of rollout_episodes_kernel (mgx_episodes.hip) or -- rows != NULL -- of
+// rollout_episodes_rows_kernel (mgx_episode_rows.hip), every check before it.
+static int rollout_episodes_impl(mgx_handle *h, const uint8_t *action_id, int per_step, const int32_t *table, int32_t n_actions,
+                                 int32_t K, double *reward, uint8_t *done, double *soc_trace, uint32_t *status_trace,
+                                 const mgx_episode_stats *stats, const mgx_episode_rows *rows, mgx_stream stream, const char *fn)
+{
+    if (!h || !action_id || !table) return fail(MGX_ERR_INVALID, "%s: NULL argument", fn);
+    if (int rc = episodes_launch_refusal(h, K, done, fn, "mgx_rollout_discrete", "mgx_step_lists")) return rc;
+    if (rows) {
+        if (int rc = episode_rows_refusal(h, rows, fn)) return rc;
+    } else if (h->k.final_obs) {
+        return fail(MGX_ERR_UNSUPPORTED, "%s: mgx_set_final_obs is set but the call writes no observations", fn);
+    }
     if (h->t < 0 || (int64_t)h->t + K > step_limit(h))
-        return fail(MGX_ERR_RANGE, "mgx_rollout_episodes: steps [%d, %d) leave the counter's range", h->t, h->t + K);
+        return fail(MGX_ERR_RANGE, "%s: steps [%d, %d) leave the counter's range", fn, h->t, h->t + K);
     PLWords tab;
-    if (int rc = encode_table(h, table, n_actions, &tab, "mgx_rollout_episodes")) return rc;
+    if (int rc = encode_table(h, table, n_actions, &tab, fn)) return rc;
     EpisodeLaunch L;
     L.flags = h->flags;
     L.src = factorised(h->k.c) ? EP_SRC_FACT : (h->k.pm_pitch ? EP_SRC_GRID_MAJOR : EP_SRC_GATHER);
     if (L.src == EP_SRC_FACT && !h->k.pm_pitch)
-        return fail(MGX_ERR_INVALID, "mgx_rollout_episodes: the handle holds no profile-major base tables");
+        return fail(MGX_ERR_INVALID, "%s: the handle holds no profile-major base tables", fn);
     L.per_step = per_step != 0;
     L.gpb = fused_grids_per_block(h, h->k.N);
     L.blocks = (unsigned)((h->k.N + L.gpb - 1) / L.gpb);
@@ -2009,37 +2031,60 @@ int mgx_rollout_episodes(mgx_handle *h, const uint8_t *action_id, int per_step, 
     L.t = h->t; L.K = K;
     L.out = FusedOut{reward, done, soc_trace, status_trace, nullptr, nullptr};
     L.stats = stats ? *stats : mgx_episode_stats{nullptr, nullptr, nullptr, nullptr};
-    if (!(launch_rollout_episodes_p0(L) || launch_rollout_episodes_p1(L)))
-        return fail(MGX_ERR_UNSUPPORTED, "mgx_rollout_episodes: no kernel for layout flags %d", h->flags);
+    if (rows) {
+        const EpisodeRowsLaunch R{L, rows->obs, rows->final_obs};
+        if (!(launch_rollout_episodes_rows_p0(R) || launch_rollout_episodes_rows_p1(R)))
+            return fail(MGX_ERR_UNSUPPORTED, "%s: no kernel for layout flags %d", fn, h->flags);
+    } else if (!(launch_rollout_episodes_p0(L) || launch_rollout_episodes_p1(L)))
+        return fail(MGX_ERR_UNSUPPORTED, "%s: no kernel for layout flags %d", fn, h->flags);
     hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "rollout_episodes_kernel launch");
+    if (e != hipSuccess) return hip_fail(e, rows ? "rollout_episodes_rows_kernel launch" : "rollout_episodes_kernel launch");
     advance(h, K, L.stream);
     return MGX_OK;
 }
 
-// The continuous K-step over in-place episodes: one launch of step_k_episodes_kernel (mgx_step_episodes.hip), every check before it.
-int mgx_step_k_episodes(mgx_handle *h, const void *actions, int32_t K, int normalized, double *reward, uint8_t *done,
-                        double *soc_trace, uint32_t *status_trace, const mgx_episode_stats *stats, mgx_stream stream)
+int mgx_rollout_episodes(mgx_handle *h, const uint8_t *action_id, int per_step, const int32_t *table, int32_t n_actions,
+                         int32_t K, double *reward, uint8_t *done, double *soc_trace, uint32_t *status_trace,
+                         const mgx_episode_stats *stats, mgx_stream stream)
 {
     g_err[0] = 0;
-    if (!h || (h->action_dim > 0 && !actions)) return fail(MGX_ERR_INVALID, "mgx_step_k_episodes: NULL argument");
-    if (K <= 0) return fail(MGX_ERR_INVALID, "mgx_step_k_episodes: K must be positive");
-    if (h->multi) return fail(MGX_ERR_UNSUPPORTED, "mgx_step_k_episodes: needs exactly one module of every kind per grid "
-                                                    "(several: single steps, mgx_step)");
-    if (h->n_shards > 1) return fail(MGX_ERR_UNSUPPORTED, "mgx_step_k_episodes: not offered while the handle steps in shards");
-    if (dev_counter(h)) return fail(MGX_ERR_UNSUPPORTED, "mgx_step_k_episodes: not offered in device-counter mode");
-    if (!h->inplace || !h->k.ep_off || !h->k.ep_final)
-        return fail(MGX_ERR_INVALID, "mgx_step_k_episodes: the handle is not stepping in-place episodes (mgx_reset_episodes); "
-                                     "lock-step episodes: mgx_step_k");
-    if (h->k.done_bits && done) return fail(MGX_ERR_UNSUPPORTED, "mgx_step_k_episodes: `done` is written as bytes (mgx_set_done_format)");
-    if (h->k.final_obs) return fail(MGX_ERR_UNSUPPORTED, "mgx_step_k_episodes: mgx_set_final_obs is set but the call writes no observations");
+    return rollout_episodes_impl(h, action_id, per_step, table, n_actions, K, reward, done, soc_trace, status_trace, stats, nullptr, stream,
+                                 "mgx_rollout_episodes");
+}
+
+// a launch that wants no rows never runs the rows kernel: it is the plain call
+int mgx_rollout_episodes_rows(mgx_handle *h, const uint8_t *action_id, int per_step, const int32_t *table, int32_t n_actions,
+                              int32_t K, double *reward, uint8_t *done, double *soc_trace, uint32_t *status_trace,
+                              const mgx_episode_stats *stats, const mgx_episode_rows *rows, mgx_stream stream)
+{
+    g_err[0] = 0;
+    if (!h) return fail(MGX_ERR_INVALID, "mgx_rollout_episodes_rows: NULL argument");
+    if (!rows || (!rows->obs && !rows->final_obs))
+        return mgx_rollout_episodes(h, action_id, per_step, table, n_actions, K, reward, done, soc_trace, status_trace, stats, stream);
+    return rollout_episodes_impl(h, action_id, per_step, table, n_actions, K, reward, done, soc_trace, status_trace, stats, rows, stream,
+                                 "mgx_rollout_episodes_rows");
+}
+
+// The continuous K-step over in-place episodes: one launch of step_k_episodes_kernel (mgx_step_episodes.hip) or -- rows != NULL --
+// of step_k_episodes_rows_kernel (mgx_step_episode_rows.hip), every check before it.
+static int step_k_episodes_impl(mgx_handle *h, const void *actions, int32_t K, int normalized, double *reward, uint8_t *done,
+                                double *soc_trace, uint32_t *status_trace, const mgx_episode_stats *stats,
+                                const mgx_episode_rows *rows, mgx_stream stream, const char *fn)
+{
+    if (!h || (h->action_dim > 0 && !actions)) return fail(MGX_ERR_INVALID, "%s: NULL argument", fn);
+    if (int rc = episodes_launch_refusal(h, K, done, fn, "mgx_step_k", "mgx_step")) return rc;
+    if (rows) {
+        if (int rc = episode_rows_refusal(h, rows, fn)) return rc;
+    } else if (h->k.final_obs) {
+        return fail(MGX_ERR_UNSUPPORTED, "%s: mgx_set_final_obs is set but the call writes no observations", fn);
+    }
     if (h->t < 0 || (int64_t)h->t + K > step_limit(h))
-        return fail(MGX_ERR_RANGE, "mgx_step_k_episodes: steps [%d, %d) leave the counter's range", h->t, h->t + K);
+        return fail(MGX_ERR_RANGE, "%s: steps [%d, %d) leave the counter's range", fn, h->t, h->t + K);
     StepEpisodeLaunch L;
     L.flags = h->flags;
     L.src = factorised(h->k.c) ? EP_SRC_FACT : (h->k.pm_pitch ? EP_SRC_GRID_MAJOR : EP_SRC_GATHER);
     if (L.src == EP_SRC_FACT && !h->k.pm_pitch)
-        return fail(MGX_ERR_INVALID, "mgx_step_k_episodes: the handle holds no profile-major base tables");
+        return fail(MGX_ERR_INVALID, "%s: the handle holds no profile-major base tables", fn);
     L.act_f32 = h->k.act_f32 != 0;
     L.gpb = fused_grids_per_block(h, h->k.N);
     L.blocks = (unsigned)((h->k.N + L.gpb - 1) / L.gpb);
@@ -2050,12 +2095,34 @@ int mgx_step_k_episodes(mgx_handle *h, const void *actions, int32_t K, int norma
     L.t = h->t; L.K = K; L.normalized = normalized;
     L.out = FusedOut{reward, done, soc_trace, status_trace, nullptr, nullptr};
     L.stats = stats ? *stats : mgx_episode_stats{nullptr, nullptr, nullptr, nullptr};
-    if (!(launch_step_k_episodes_p0(L) || launch_step_k_episodes_p1(L)))
-        return fail(MGX_ERR_UNSUPPORTED, "mgx_step_k_episodes: no kernel for layout flags %d", h->flags);
+    if (rows) {
+        const StepEpisodeRowsLaunch R{L, rows->obs, rows->final_obs};
+        if (!(launch_step_k_episodes_rows_p0(R) || launch_step_k_episodes_rows_p1(R)))
+            return fail(MGX_ERR_UNSUPPORTED, "%s: no kernel for layout flags %d", fn, h->flags);
+    } else if (!(launch_step_k_episodes_p0(L) || launch_step_k_episodes_p1(L)))
+        return fail(MGX_ERR_UNSUPPORTED, "%s: no kernel for layout flags %d", fn, h->flags);
     hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "step_k_episodes_kernel launch");
+    if (e != hipSuccess) return hip_fail(e, rows ? "step_k_episodes_rows_kernel launch" : "step_k_episodes_kernel launch");
     advance(h, K, L.stream);
     return MGX_OK;
+}
+
+int mgx_step_k_episodes(mgx_handle *h, const void *actions, int32_t K, int normalized, double *reward, uint8_t *done,
+                        double *soc_trace, uint32_t *status_trace, const mgx_episode_stats *stats, mgx_stream stream)
+{
+    g_err[0] = 0;
+    return step_k_episodes_impl(h, actions, K, normalized, reward, done, soc_trace, status_trace, stats, nullptr, stream, "mgx_step_k_episodes");
+}
+
+int mgx_step_k_episodes_rows(mgx_handle *h, const void *actions, int32_t K, int normalized, double *reward, uint8_t *done,
+                             double *soc_trace, uint32_t *status_trace, const mgx_episode_stats *stats,
+                             const mgx_episode_rows *rows, mgx_stream stream)
+{
+    g_err[0] = 0;
+    if (!h) return fail(MGX_ERR_INVALID, "mgx_step_k_episodes_rows: NULL argument");
+    if (!rows || (!rows->obs && !rows->final_obs))
+        return mgx_step_k_episodes(h, actions, K, normalized, reward, done, soc_trace, status_trace, stats, stream);
+    return step_k_episodes_impl(h, actions, K, normalized, reward, done, soc_trace, status_trace, stats, rows, stream, "mgx_step_k_episodes_rows");
 }
 
 int mgx_rollout_lists(mgx_handle *h, const int32_t *action_id, int per_step, const int32_t *lists, int32_t n_lists, int32_t list_len,

@@ -1,0 +1,189 @@
+// mgx_episode_rows.hip -- the fused discrete roll-out over per-grid in-place episodes WITH observation rows
+// (mgx_rollout_episodes_rows): rollout_episodes_kernel (mgx_episodes.hip) + per step the H = 0 row the step returned and, where a
+// grid restarts, the row before the restart.  Translation units of their own (MGX_EPISODE_ROWS_PARTS slices of the layouts):
+//   hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -c -DMGX_EPISODE_ROWS_PART=p mgx_episode_rows.hip -o mgx_episode_rows_p.o
+// so every other kernel comes out of the compiler exactly as it did without this file.
+#include "mgx_episode_rows.hpp"
+
+#ifndef MGX_EPISODE_ROWS_PART
+#error "compile with -DMGX_EPISODE_ROWS_PART=<0..MGX_EPISODE_ROWS_PARTS-1>"
+#endif
+
+// layouts (template parameter F) of each slice; together: 0..7, 14, 15 (MGX_DISPATCH_F in mgx_abi.hip)
+#if MGX_EPISODE_ROWS_PART == 0
+#define MGX_PART_FLAGS(X) X(0) X(1) X(2) X(3) X(4) X(5)
+#elif MGX_EPISODE_ROWS_PART == 1
+#define MGX_PART_FLAGS(X) X(6) X(7) X(14) X(15)
+#else
+#error "MGX_EPISODE_ROWS_PART out of range"
+#endif
+
+#define MGX_CAT2(a, b) a##b
+#define MGX_CAT(a, b) MGX_CAT2(a, b)
+
+namespace mgx {
+
+// Template parameters, ring, statistics and restart as rollout_episodes_kernel.  What the rows add, per step k (counter t = t0 + k,
+// row offset `off` before the step):
+//   final_obs[k, i, :]   only where the step restarts grid i: the row of series row t + 1 + off with the post-step state -- the row
+//                        episode_tail writes through mgx_set_final_obs.  After the rotation ring slot 0 holds exactly that series
+//                        row, until the restart branch reads the slots again.
+//   obs[k, i, :]         the row of series row t + 1 + off_new: ring slot 0 again, under the offset the restart left.
+// Hence the ring here reaches ONE row further than the plain kernel's: row t0 + K (the row after the last step, and the first row
+// of an episode that starts at step K - 1) is fetched too -- guards `<= K` where the plain kernel has `< K`.  episode_row clamps
+// every row to the series, so the extra fetch stays inside it.  The id ring keeps its guard: there is no id row K.
+// SoC is formed every step (the row shows it).
+// Scalar registers: rollout_episodes_kernel leaves five of them free.  So the arguments come as ONE struct and whatever is not
+// needed inside the loop is read late, through late_kernargs: the statistics' addresses for the write-back, the device copy of the
+// KArgs and final_obs inside the restart branch; the row's column bases travel packed in one word (RolloutRowsArgs.desc) that is
+// kept opaque inside the loop, or its seven fields would be hoisted into seven registers again.
+template <int F, int U, bool PER_STEP, int SRC>
+__global__ __launch_bounds__(BLOCK_K) void rollout_episodes_rows_kernel(const RolloutRowsArgs g)
+{
+    static_assert(U <= 8, "the id ring is one 64-bit register");
+    const KArgs &a = g.a;
+    const PLWords &tab = g.tab;
+    const uint8_t *__restrict__ ids = g.ids;
+    const int32_t t0 = g.t0, K = g.K, gpb = g.gpb;
+    const FusedOut &out = g.out;
+    const mgx_episode_stats &es = g.es;
+    void *__restrict__ obs = g.obs;
+    const bool want_final = g.final_obs != nullptr;
+    uint32_t desc = g.desc;
+    const auto *late = late_kernargs<RolloutRowsArgs>();
+    const int64_t i = (int64_t)blockIdx.x * gpb + threadIdx.x;
+    __shared__ uint32_t word_of_id[PER_STEP ? BLOCK_K : 1];
+    // one wave-private tile per wave for the rows of a step (store_episode_row)
+    __shared__ __attribute__((aligned(16))) double row_tiles[MGX_EPISODE_ROWS_TILE ? (BLOCK_K / 64) * 64 * ROW_TILE_MAX_D : 1];
+    if constexpr (PER_STEP) {
+        static_assert(BLOCK_K == 256, "one thread per id byte");
+        word_of_id[threadIdx.x] = pl_select(tab, (int32_t)threadIdx.x);
+        __syncthreads();                                        // (the only barrier: before any lane leaves)
+    }
+    if ((int32_t)threadIdx.x >= gpb || i >= a.N) return;
+    double *tile = row_tiles + (MGX_EPISODE_ROWS_TILE ? (threadIdx.x >> 6) * (64 * ROW_TILE_MAX_D) : 0);
+    const int64_t N = a.N;
+    const uint32_t i32 = (uint32_t)i;
+    Params p; State s; Derived d;
+    load_state<F>(a.c, i, false, s);
+    load_params<F>(a.c, i, p);
+    derive<F>(p, d);
+    const bool gen_instant = genset_wave_is_instant<F>(p, s);
+    const bool ar_on = a.ar_mode != 0;
+    int32_t off = a.ep_off[i], fin = a.ep_final[i];
+    uint32_t word = PER_STEP ? 0u : pl_select(tab, ids[i]);
+    GridFactors f;
+    f.lr = 0.0; f.pr = 0.0; f.lp = 0u; f.pp = 0u; f.cp = 0u; f.pat = 0u;
+    if constexpr (SRC == EP_SRC_FACT) load_factors<F>(a.c, i, f);
+    RowBounds<F> rb;
+    load_row_bounds<F>(a.c, N, i, rb);
+    double run = es.ret_running ? es.ret_running[i] : 0.0;
+    double sum = es.ret_sum ? es.ret_sum[i] : 0.0;
+    double last = es.ret_last ? es.ret_last[i] : 0.0;
+    int32_t eps = es.episodes ? es.episodes[i] : 0;
+    {
+        const bool GI = gen_instant;
+        RowSlot ring[U];
+        uint64_t idq = 0;                 // PER_STEP: the id bytes of the U ring slots
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            if (u <= K) fetch_row_slot<F, SRC>(a, f, i, t0 + u, off, ring[u]);
+            if constexpr (PER_STEP) { if (u < K) idq |= (uint64_t)(ids + (int64_t)u * N)[i32] << (8 * u); }
+        }
+        uint32_t word_next = 0u;
+        if constexpr (PER_STEP) word_next = word_of_id[idq & 0xffu];
+        int64_t o64 = i;
+        int64_t r64 = i * row_desc_dim(desc);      // element offset of row (k, i) of obs / final_obs
+#pragma nounroll
+        for (int32_t k = 0; k < K; k++) {
+            const int32_t t = t0 + k;
+            asm volatile("" : "+s"(desc));             // (opaque: the fields are taken out where a row is built, every step)
+            Inputs in;
+            widen_row_slot<F, SRC>(a, f, ring[0], t, off, in);
+#pragma unroll
+            for (int u = 0; u + 1 < U; u++) ring[u] = ring[u + 1];
+            if constexpr (PER_STEP) {
+                word = word_next;
+                idq >>= 8;
+                word_next = word_of_id[idq & 0xffu];            // (the coming step's; beyond the last step: unused)
+                if (k + U < K) idq |= (uint64_t)(ids + (int64_t)(k + U) * N)[i32] << (8 * (U - 1));
+            } else {
+                asm volatile("" : "+v"(word));                  // (the list decoding stays inside the loop: rollout_episodes_kernel)
+            }
+            double bat_q;
+            uint32_t xv = 0u;
+            populate_core<F, false>(p, s, word, in, bat_q, 0.0 + -1 * in.load, in.pv, GI, &xv);
+            Outputs o;
+            step_core<F, true>(p, d, s, in, false, true, GI, o, bat_q);
+            const double r = shaped_reward<F>(a.shaper, o);
+            const bool dn = t >= fin - 1;                       // done_at(a, i, t)
+            if (out.reward) out.reward[o64] = r;
+            if (out.done) out.done[o64] = (uint8_t)dn;
+            if constexpr (F & F_BATTERY) { if (out.soc_trace) out.soc_trace[o64] = s.soc; }
+            if constexpr (F & F_GENSET) { if (out.status_trace) out.status_trace[o64] = s.status; }
+            o64 += N;
+            run += r;
+            if (t == fin - 1) { last = run; sum += run; eps += 1; run = 0.0; }
+            if (ar_on && dn) {
+                const KArgs *__restrict__ a_dev = late->a_dev;
+                if (want_final) {                               // the row of the episode that ends here: slot 0, still the old rows
+                    Inputs inf;
+                    widen_row_slot<F, SRC>(a, f, ring[0], t + 1, off, inf);
+                    store_final_row<F>(a_dev, a.T, desc, late->final_obs, r64, i, t + 1 + off, inf, rb, p, s);
+                }
+                // (the arguments of the draw out of the handle's device copy of the KArgs, read here, in the branch)
+                off = episode_auto_restart(*a_dev, i, t, off, true);
+                fin = a_dev->ep_final[i];
+                // slot v now stands for step k + 1 + v: all of them again, at the rows of the new episode
+#pragma unroll
+                for (int v = 0; v < U; v++)
+                    if (k + 1 + v <= K) fetch_row_slot<F, SRC>(a, f, i, t + 1 + v, off, ring[v]);
+            } else if (k + U <= K) {
+                fetch_row_slot<F, SRC>(a, f, i, t + U, off, ring[U - 1]);
+            }
+            if (obs) {
+                Inputs inn;
+                widen_row_slot<F, SRC>(a, f, ring[0], t + 1, off, inn);
+                store_episode_row<F>(late->a_dev, a.T, desc, obs, r64, i, t + 1 + off, inn, rb, p, s, tile);
+            }
+            r64 += N * row_desc_dim(desc);
+        }
+    }
+    store_state<F>(late->a_dev->c, i, s);     // (the same columns; their addresses need no scalar registers across the loop)
+    // (the statistics' addresses a second time, from the kernarg segment: the first copies ended their lives before the loop)
+    if (double *q = late->es.ret_running) q[i] = run;
+    if (double *q = late->es.ret_sum) q[i] = sum;
+    if (double *q = late->es.ret_last) q[i] = last;
+    if (int32_t *q = late->es.episodes) q[i] = eps;
+}
+
+template <int F>
+static void rollout_episodes_rows_dispatch(const EpisodeRowsLaunch &R)
+{
+    const EpisodeLaunch &L = R.e;
+    // ring depth as rollout_episodes_kernel's
+    const RolloutRowsArgs g{*L.k, *L.tab, L.ids, L.t, L.K, L.out, L.stats, L.gpb, pack_row_desc(*L.k), L.k_dev, R.obs, R.final_obs};
+#define MGX_EPISODES(PS, SRC) rollout_episodes_rows_kernel<F, (F & F_GRID) ? 4 : MGX_RING_ROLLOUT, PS, SRC><<<L.blocks, BLOCK_K, 0, L.stream>>>(g)
+    if (L.per_step) {
+        if (L.src == EP_SRC_FACT) MGX_EPISODES(true, EP_SRC_FACT);
+        else if (L.src == EP_SRC_GRID_MAJOR) MGX_EPISODES(true, EP_SRC_GRID_MAJOR);
+        else MGX_EPISODES(true, EP_SRC_GATHER);
+    } else {
+        if (L.src == EP_SRC_FACT) MGX_EPISODES(false, EP_SRC_FACT);
+        else if (L.src == EP_SRC_GRID_MAJOR) MGX_EPISODES(false, EP_SRC_GRID_MAJOR);
+        else MGX_EPISODES(false, EP_SRC_GATHER);
+    }
+#undef MGX_EPISODES
+}
+
+bool MGX_CAT(launch_rollout_episodes_rows_p, MGX_EPISODE_ROWS_PART)(const EpisodeRowsLaunch &R)
+{
+    switch (R.e.flags) {
+#define X(FV) case FV: rollout_episodes_rows_dispatch<FV>(R); return true;
+        MGX_PART_FLAGS(X)
+#undef X
+        default: return false;
+    }
+}
+
+}  // namespace mgx

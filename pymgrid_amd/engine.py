@@ -702,13 +702,38 @@ class StepEngine:
     EPISODE_STATS = (("ret_running", torch.float64), ("ret_sum", torch.float64), ("ret_last", torch.float64),
                      ("episodes", torch.int32))
 
+    def _episode_rows(self, res, out, K, obs, final_obs):
+        """The ``mgx_episode_rows`` of a fused episode launch (None: no rows asked for -- the plain call): ``obs`` / ``final_obs``
+        [K, N, obs_dim] in ``obs_dtype``, taken from ``out`` or allocated (``final_obs`` zero-filled: only the entries of the grids a
+        step restarts are written)."""
+        if not (obs or final_obs):
+            return None
+        rows = _lib.EpisodeRows()
+        rows.struct_size = C.sizeof(_lib.EpisodeRows)
+        shape = (K, self.N, self.obs_dim)
+        for name, want in (("obs", obs), ("final_obs", final_obs)):
+            if not want:
+                continue
+            t = out.get(name)
+            if t is None:
+                t = self._empty(*shape, dtype=self.obs_dtype)
+                if name == "final_obs":
+                    t.zero_()
+            elif t.dtype != self.obs_dtype or t.device != self.device or not t.is_contiguous() or tuple(t.shape) != shape:
+                raise ValueError(f"out[{name!r}] must be a contiguous {self.obs_dtype} tensor {list(shape)} on {self.device}")
+            res[name] = t
+            setattr(rows, name, _ptr(t))
+        return rows
+
     def rollout_episodes(self, action_id, table, K, reward=True, done=False, soc_trace=False, status_trace=False, stats=None,
-                         out=None):
+                         out=None, obs=False, final_obs=False):
         """K fused discrete steps of a handle in in-place episodes (``reset_episodes``): every grid walks its own episode and --
         with ``set_auto_reset`` -- restarts inside the launch, as K calls of ``step_discrete`` would leave it
         (``mgx_rollout_episodes``).  ``action_id`` uint8 [K, N] or [N]; ``stats``: a dict with any of ``ret_running`` /
         ``ret_sum`` / ``ret_last`` (float64 [N]) and ``episodes`` (int32 [N]), updated in place.  Returns the requested [K, N]
-        outputs."""
+        outputs.  ``obs`` / ``final_obs`` (``mgx_rollout_episodes_rows``; no forecast horizon): also ``[K, N, obs_dim]`` rows in
+        ``obs_dtype`` -- ``obs[k]`` the observation step k returned, ``final_obs[k]`` the rows before a restart, written only for the
+        grids step k restarts (an allocated ``final_obs`` is zero-filled; pass a tensor through ``out=`` to choose the filling)."""
         out = out or {}
         K = int(K)
         if action_id.dtype != torch.uint8 or action_id.device != self.device or not action_id.is_contiguous() \
@@ -740,18 +765,24 @@ class StepEngine:
         d = buf("done", done, K, self.N, dtype=torch.uint8)
         s = buf("soc_trace", soc_trace and self.layout.has_battery, K, self.N)
         g = buf("status_trace", status_trace and self.layout.has_genset, K, self.N, dtype=torch.int32)
-        self._call(self._lib.mgx_rollout_episodes, _ptr(action_id), per_step, tptr, n_lists, K, _ptr(r), _ptr(d), _ptr(s), _ptr(g),
-                   C.byref(st))
+        rows = self._episode_rows(res, out, K, obs, final_obs)
+        if rows is None:
+            self._call(self._lib.mgx_rollout_episodes, _ptr(action_id), per_step, tptr, n_lists, K, _ptr(r), _ptr(d), _ptr(s), _ptr(g),
+                       C.byref(st))
+        else:
+            self._call(self._lib.mgx_rollout_episodes_rows, _ptr(action_id), per_step, tptr, n_lists, K, _ptr(r), _ptr(d), _ptr(s),
+                       _ptr(g), C.byref(st), C.byref(rows))
         if self._t is not None:
             self._t += K
         return res
 
     def step_k_episodes(self, actions, normalized=True, reward=True, done=False, soc_trace=False, status_trace=False, stats=None,
-                        out=None):
+                        out=None, obs=False, final_obs=False):
         """K fused continuous steps (actions [K, N, A]) of a handle in in-place episodes (``reset_episodes``): every grid walks its
         own episode and -- with ``set_auto_reset`` -- restarts inside the launch, as K calls of ``step`` would leave it
         (``mgx_step_k_episodes``).  Row k of ``actions`` belongs to step k whatever episode a grid is in; ``stats`` as for
-        ``rollout_episodes``.  Returns the requested [K, N] outputs."""
+        ``rollout_episodes``.  Returns the requested [K, N] outputs; ``obs`` / ``final_obs`` as for ``rollout_episodes``
+        (``mgx_step_k_episodes_rows``)."""
         out = out or {}
         K = int(actions.shape[0]) if actions is not None else int(out["K"])
         actions = self._check_actions(actions, (K,))
@@ -779,8 +810,13 @@ class StepEngine:
         d = buf("done", done, K, self.N, dtype=torch.uint8)
         s = buf("soc_trace", soc_trace and self.layout.has_battery, K, self.N)
         g = buf("status_trace", status_trace and self.layout.has_genset, K, self.N, dtype=torch.int32)
-        self._call(self._lib.mgx_step_k_episodes, _ptr(actions), K, 1 if normalized else 0, _ptr(r), _ptr(d), _ptr(s), _ptr(g),
-                   C.byref(st))
+        rows = self._episode_rows(res, out, K, obs, final_obs)
+        if rows is None:
+            self._call(self._lib.mgx_step_k_episodes, _ptr(actions), K, 1 if normalized else 0, _ptr(r), _ptr(d), _ptr(s), _ptr(g),
+                       C.byref(st))
+        else:
+            self._call(self._lib.mgx_step_k_episodes_rows, _ptr(actions), K, 1 if normalized else 0, _ptr(r), _ptr(d), _ptr(s), _ptr(g),
+                       C.byref(st), C.byref(rows))
         if self._t is not None:
             self._t += K
         return res

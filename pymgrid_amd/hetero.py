@@ -700,17 +700,37 @@ class PerGridWindowEnv:
             return "native=False: the roll-out steps in-place episodes"
         return None
 
-    def rollout(self, action_id, K=None, reward=True, done=False, soc_trace=False, status_trace=False, out=None):
+    def _rows_refusal(self):
+        """Why ``rollout`` / ``step_k`` write no observation rows on this env (None: they do)."""
+        if self.full.layout.horizon:
+            return (f"horizon={self.full.layout.horizon}: the rows written inside the launch are whole rows without a forecast "
+                    "(rows with a horizon: single steps)")
+        if self.env.observation_keys is not None:
+            return "observation_keys: the launch writes whole rows (select the columns from them, or take single steps)"
+        return None
+
+    def rollout(self, action_id, K=None, reward=True, done=False, soc_trace=False, status_trace=False, out=None,
+                observations=False, final_observations=False):
         """K steps in ONE launch (``mgx_rollout_episodes``) for ``discrete=True, auto_reset=True`` with device draws and one module
         of every kind: ``action_id`` holds priority-list ids, ``[K, N]`` (one per step) or ``[N]`` (one fixed list per grid, ``K``
         given).  Every grid walks its episodes and restarts inside the launch exactly as K calls of ``step`` would make it; the
         call returns the requested ``[K, N]`` tensors (``reward``, ``done``, ``soc_trace``, ``status_trace``), keeps ``starts`` /
         ``lengths`` / ``current_steps`` current and carries the per-grid statistics ``episode_stats`` (``ret_running``,
         ``ret_sum``, ``ret_last``, ``episodes``; zeroed by ``reset()``).  Afterwards the env stands where K steps would have left
-        it: the next ``step`` returns the rows its single-stepped twin returns."""
+        it: the next ``step`` returns the rows its single-stepped twin returns.
+
+        ``observations=True`` / ``final_observations=True`` (no forecast horizon, no ``observation_keys``): the launch also writes
+        ``obs`` / ``final_obs`` ``[K, N, obs_dim]`` in the env's ``obs_dtype`` (``mgx_rollout_episodes_rows``) -- ``obs[k]`` is the
+        observation ``step`` k would have returned, so ``obs[-1]`` is the one the next ``step`` builds on; ``final_obs[k][done[k]]``
+        are the rows ``info["final_observation"][done]`` of a ``final_observation=True`` env would have held at step k, the
+        other entries are not written (zeros when the call allocates the tensor; pass your own through ``out=``)."""
         why = self._rollout_refusal()
         if why is not None:
             raise ValueError(f"PerGridWindowEnv.rollout is not offered with {why}")
+        if observations or final_observations:
+            why = self._rows_refusal()
+            if why is not None:
+                raise ValueError(f"PerGridWindowEnv.rollout writes no observations with {why}")
         if self.starts is None:
             raise RuntimeError("rollout() before reset()")
         env = self.env
@@ -732,7 +752,8 @@ class PerGridWindowEnv:
             if env._ring is not None:
                 e.prefetch_wait()          # (a refill ahead of the counter reads the row offsets the launch rewrites)
             res = e.rollout_episodes(ids, env._table, int(K), reward=reward, done=done, soc_trace=soc_trace,
-                                     status_trace=status_trace, stats=self.episode_stats, out=out)
+                                     status_trace=status_trace, stats=self.episode_stats, out=out, obs=bool(observations),
+                                     final_obs=bool(final_observations))
             if env._ring is not None:      # the observation rings: primed again at the grids' current rows, as after a reset
                 env._refill()
         finally:
@@ -764,17 +785,24 @@ class PerGridWindowEnv:
             return "native=False: the fused step walks in-place episodes"
         return None
 
-    def step_k(self, actions, normalized=True, reward=True, done=False, soc_trace=False, status_trace=False, out=None):
+    def step_k(self, actions, normalized=True, reward=True, done=False, soc_trace=False, status_trace=False, out=None,
+               observations=False, final_observations=False):
         """K continuous steps in ONE launch (``mgx_step_k_episodes``) for ``discrete=False, auto_reset=True`` with device draws and one
         module of every kind: ``actions`` ``[K, N, A]`` of the env's ``action_dtype`` (columns ``layout.action_names``), row k the
         control of step k whatever episode a grid is in.  Every grid walks its episodes and restarts inside the launch exactly as K
         calls of ``step(actions[k], normalized)`` would make it; the call returns the requested ``[K, N]`` tensors (``reward``,
         ``done``, ``soc_trace``, ``status_trace``), keeps ``starts`` / ``lengths`` / ``current_steps`` current and carries the
         per-grid statistics ``episode_stats`` (``ret_running``, ``ret_sum``, ``ret_last``, ``episodes``; zeroed by ``reset()``).
-        Afterwards the env stands where K steps would have left it: the next ``step`` returns the rows its single-stepped twin returns."""
+        Afterwards the env stands where K steps would have left it: the next ``step`` returns the rows its single-stepped twin returns.
+        ``observations`` / ``final_observations``: the rows ``obs`` / ``final_obs`` ``[K, N, obs_dim]`` as for ``rollout``
+        (``mgx_step_k_episodes_rows``)."""
         why = self._step_k_refusal()
         if why is not None:
             raise ValueError(f"PerGridWindowEnv.step_k is not offered with {why}")
+        if observations or final_observations:
+            why = self._rows_refusal()
+            if why is not None:
+                raise ValueError(f"PerGridWindowEnv.step_k writes no observations with {why}")
         if self.starts is None:
             raise RuntimeError("step_k() before reset()")
         env = self.env
@@ -789,7 +817,8 @@ class PerGridWindowEnv:
             if env._ring is not None:
                 e.prefetch_wait()          # (a refill ahead of the counter reads the row offsets the launch rewrites)
             res = e.step_k_episodes(actions, normalized=normalized, reward=reward, done=done, soc_trace=soc_trace,
-                                    status_trace=status_trace, stats=self.episode_stats, out=out)
+                                    status_trace=status_trace, stats=self.episode_stats, out=out, obs=bool(observations),
+                                    final_obs=bool(final_observations))
             if env._ring is not None:      # the observation rings: primed again at the grids' current rows, as after a reset
                 env._refill()
         finally:
@@ -947,26 +976,37 @@ class PerGridWindowFleet:
 
     def rollout(self, action_ids, K=None, **kw):
         """``PerGridWindowEnv.rollout`` of every bucket, one launch each, in bucket order (``action_ids``: one entry per bucket,
-        ``[K, n_k]`` or ``[n_k]``; keyword arguments as there).  Bucket k is left exactly as its twin's ``rollout`` leaves it; a bucket
-        its twin refuses is refused with the same ValueError before anything is launched.  Returns one dict per bucket."""
+        ``[K, n_k]`` or ``[n_k]``; keyword arguments as there, ``observations=True`` / ``final_observations=True`` included: every
+        bucket's dict then holds its own ``obs`` / ``final_obs`` ``[K, n_k, obs_dim_k]``).  Bucket k is left exactly as its twin's
+        ``rollout`` leaves it; a bucket its twin refuses is refused with the same ValueError before anything is launched.  Returns one
+        dict per bucket."""
         if len(action_ids) != len(self.envs):
             raise ValueError(f"action_ids holds {len(action_ids)} entries, the fleet {len(self.envs)} buckets")
+        want_rows = kw.get("observations") or kw.get("final_observations")
         for k, pe in enumerate(self.envs):
             why = pe._rollout_refusal()
             if why is not None:
                 raise ValueError(f"PerGridWindowEnv.rollout is not offered with {why}")
+            why = pe._rows_refusal() if want_rows else None
+            if why is not None:
+                raise ValueError(f"PerGridWindowEnv.rollout writes no observations with {why}")
         return [pe.rollout(a, K, **kw) for pe, a in zip(self.envs, action_ids)]
 
     def step_k(self, actions_list, **kw):
         """``PerGridWindowEnv.step_k`` of every bucket, one launch each, in bucket order (``actions_list``: one ``[K, n_k, A_k]`` tensor
-        per bucket; keyword arguments as there).  Bucket k is left exactly as its twin's ``step_k`` leaves it; a bucket its twin
-        refuses is refused with the same ValueError before anything is launched.  Returns one dict per bucket."""
+        per bucket; keyword arguments as there, ``observations=True`` / ``final_observations=True`` included).  Bucket k is left
+        exactly as its twin's ``step_k`` leaves it; a bucket its twin refuses is refused with the same ValueError before anything is
+        launched.  Returns one dict per bucket."""
         if len(actions_list) != len(self.envs):
             raise ValueError(f"actions_list holds {len(actions_list)} entries, the fleet {len(self.envs)} buckets")
+        want_rows = kw.get("observations") or kw.get("final_observations")
         for pe, a in zip(self.envs, actions_list):
             why = pe._step_k_refusal()
             if why is not None:
                 raise ValueError(f"PerGridWindowEnv.step_k is not offered with {why}")
+            why = pe._rows_refusal() if want_rows else None
+            if why is not None:
+                raise ValueError(f"PerGridWindowEnv.step_k writes no observations with {why}")
             if not torch.is_tensor(a) or a.dim() != 3:
                 raise ValueError("every entry of actions_list must be a [K, n_k, A_k] tensor")
             pe.env.engine._check_actions(a, (int(a.shape[0]),))

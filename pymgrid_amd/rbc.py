@@ -231,12 +231,16 @@ class RuleBasedControl:
                 self.batch.load_state(saved)
             self.env._after_external_steps()              # the env's observation rings follow the counter again
 
-    def run_episodes(self, steps, chunk=512, reward=False, done=False, soc_trace=False, status_trace=False, reset=True):
+    def run_episodes(self, steps, chunk=512, reward=False, done=False, soc_trace=False, status_trace=False, reset=True,
+                     observations=False, final_observations=False):
         """The priority lists deployed for ``steps`` steps over per-grid random episodes (``RuleBasedControl(PerGridWindowEnv(...,
         discrete=True, auto_reset=True))``): every grid restarts on its own whenever its episode ends, inside the fused launches
         (``mgx_rollout_episodes``, ``chunk`` steps each).  ``reset=True`` draws the first episodes (and zeroes the statistics)
         first.  Returns ``episode_return_sum`` / ``episode_return_last`` / ``episodes`` / ``return_running`` ([N]: the env's
-        ``episode_stats``, which carry on into a later call with ``reset=False``) and the per-step outputs asked for ([steps, N])."""
+        ``episode_stats``, which carry on into a later call with ``reset=False``) and the per-step outputs asked for ([steps, N]).
+        ``observations`` / ``final_observations``: also ``obs`` / ``final_obs`` ``[steps, N, obs_dim]``, the rows of
+        ``PerGridWindowEnv.rollout`` (the observation every step returned; the rows before a restart where ``done`` is set, zeros
+        elsewhere) -- with ``done=True`` the (s, a, r, s', done) tuples of the expert."""
         pe = self.episodes_env
         if pe is None:
             raise TypeError("run_episodes needs RuleBasedControl(PerGridWindowEnv(..., discrete=True, auto_reset=True)); "
@@ -247,7 +251,8 @@ class RuleBasedControl:
         left = int(steps)
         while left > 0:
             k = min(int(chunk), left)
-            out = pe.rollout(self._ids_dev, k, reward=reward, done=done, soc_trace=soc_trace, status_trace=status_trace)
+            out = pe.rollout(self._ids_dev, k, reward=reward, done=done, soc_trace=soc_trace, status_trace=status_trace,
+                             observations=observations, final_observations=final_observations)
             for name, v in out.items():
                 parts.setdefault(name, []).append(v)
             left -= k
