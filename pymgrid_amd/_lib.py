@@ -13,15 +13,19 @@ import sys
 _PKG = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_PKG)
 LIB_PATH = os.environ.get("MGX_LIB") or os.path.join(_PKG, "libmgx.so")   # MGX_LIB: A/B kernel variants
-SOURCES = [os.path.join(_PKG, "csrc", f) for f in ("mgx_abi.hip", "mgx_fused.hip", "mgx_kernels.hpp", "mgx_core.hpp", "mgx_episodes.hip",
-                                                      "mgx_step_episodes.hip")] + \
-          [os.path.join(_ROOT, "include", "mgx.h")] + \
-          [os.path.join(_PKG, "csrc", f) for f in ("mgx_episode_rows.hip", "mgx_step_episode_rows.hip", "mgx_episode_rows.hpp")]
-FUSED_PARTS = 6            # MGX_FUSED_PARTS: slices of mgx_fused.hip (the K-step kernels), compiled in parallel
-EPISODE_PARTS = 2          # MGX_EPISODE_PARTS: slices of mgx_episodes.hip (the roll-out over in-place episodes)
-STEP_EPISODE_PARTS = 2     # MGX_STEP_EPISODE_PARTS: slices of mgx_step_episodes.hip (the continuous K-step over in-place episodes)
-EPISODE_ROWS_PARTS = 2     # MGX_EPISODE_ROWS_PARTS: slices of mgx_episode_rows.hip (the roll-out over in-place episodes with rows)
-STEP_EPISODE_ROWS_PARTS = 2    # MGX_STEP_EPISODE_ROWS_PARTS: slices of mgx_step_episode_rows.hip (the continuous twin)
+# the translation units of libmgx.so: (file under csrc/, the -D macro that selects one of its slices or None, slices) -- the slices
+# of a file hold the kernels of different layouts and are compiled in parallel into <file>_<p>.o (a file without slices: <file>.o)
+UNITS = (
+    ("mgx_abi.hip", None, 1),                                           # the host side + the small kernels
+    ("mgx_fused.hip", "MGX_FUSED_PART", 6),                             # MGX_FUSED_PARTS: the K-step kernels
+    ("mgx_episodes.hip", "MGX_EPISODE_PART", 2),                        # MGX_EPISODE_PARTS: the roll-out over in-place episodes,
+    ("mgx_step_episodes.hip", "MGX_STEP_EPISODE_PART", 2),              # ... the continuous K-step over them,
+    ("mgx_episode_rows.hip", "MGX_EPISODE_ROWS_PART", 2),               # ... the roll-out with observation rows
+    ("mgx_step_episode_rows.hip", "MGX_STEP_EPISODE_ROWS_PART", 2),     # ... and its continuous twin
+)
+# everything a built library is stamped with (source_hash): a file missing here would leave a stale libmgx.so looking current
+SOURCES = [os.path.join(_PKG, "csrc", f) for f in [u[0] for u in UNITS] + ["mgx_kernels.hpp", "mgx_core.hpp", "mgx_episode_rows.hpp"]] + \
+          [os.path.join(_ROOT, "include", "mgx.h")]
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-fPIC"]
 
@@ -277,6 +281,12 @@ def build(force=False, verbose=False, defs=(), lib_path=None, abi_only=False):
     return _build(LIB_PATH, [], verbose, "", force)
 
 
+def _units(objdir):
+    """[(source, its -D flag if any, object file in ``objdir``)] of every translation unit of UNITS, mgx_abi.hip first."""
+    return [(os.path.join(_PKG, "csrc", f), [f"-D{macro}={p}"] if macro else [], os.path.join(objdir, f[:-4] + (f"_{p}.o" if macro else ".o")))
+            for f, macro, parts in UNITS for p in range(parts)]
+
+
 def _build(LIB_PATH, extra_defs, verbose, objtag, force=True, abi_only=False):
     # several ranks may get here at once (torchrun): serialise on a lock file, compile to a temporary name and
     # rename atomically so that nobody ever dlopens a half-written library
@@ -291,21 +301,9 @@ def _build(LIB_PATH, extra_defs, verbose, objtag, force=True, abi_only=False):
             tmp = f"{LIB_PATH}.{os.getpid()}.tmp"
             objdir = os.path.join(_PKG, "csrc", "_build" + ("_" + objtag if objtag else ""))
             os.makedirs(objdir, exist_ok=True)
-            # translation units: the host side + small kernels, and the slices of the K-step kernels -- compiled in parallel
-            units = [(SOURCES[0], [], os.path.join(objdir, "mgx_abi.o"))] + \
-                    [(SOURCES[1], [f"-DMGX_FUSED_PART={p}"], os.path.join(objdir, f"mgx_fused_{p}.o")) for p in range(FUSED_PARTS)] + \
-                    [(SOURCES[4], [f"-DMGX_EPISODE_PART={p}"], os.path.join(objdir, f"mgx_episodes_{p}.o")) for p in range(EPISODE_PARTS)] + \
-                    [(SOURCES[5], [f"-DMGX_STEP_EPISODE_PART={p}"], os.path.join(objdir, f"mgx_step_episodes_{p}.o")) for p in range(STEP_EPISODE_PARTS)] + \
-                    [(SOURCES[7], [f"-DMGX_EPISODE_ROWS_PART={p}"], os.path.join(objdir, f"mgx_episode_rows_{p}.o")) for p in range(EPISODE_ROWS_PARTS)] + \
-                    [(SOURCES[8], [f"-DMGX_STEP_EPISODE_ROWS_PART={p}"], os.path.join(objdir, f"mgx_step_episode_rows_{p}.o"))
-                     for p in range(STEP_EPISODE_ROWS_PARTS)]
+            units = _units(objdir)
             if abi_only:
-                base = os.path.join(_PKG, "csrc", "_build")
-                fused = [os.path.join(base, f"mgx_fused_{p}.o") for p in range(FUSED_PARTS)] + \
-                        [os.path.join(base, f"mgx_episodes_{p}.o") for p in range(EPISODE_PARTS)] + \
-                        [os.path.join(base, f"mgx_step_episodes_{p}.o") for p in range(STEP_EPISODE_PARTS)] + \
-                        [os.path.join(base, f"mgx_episode_rows_{p}.o") for p in range(EPISODE_ROWS_PARTS)] + \
-                        [os.path.join(base, f"mgx_step_episode_rows_{p}.o") for p in range(STEP_EPISODE_ROWS_PARTS)]
+                fused = [obj for _, _, obj in _units(os.path.join(_PKG, "csrc", "_build"))[1:]]
                 if not all(os.path.exists(f) for f in fused):
                     raise FileNotFoundError("abi_only variants link the product build's mgx_fused objects: build() first")
                 units = units[:1]

@@ -1999,14 +1999,14 @@ static int episode_rows_refusal(mgx_handle *h, const mgx_episode_rows *rows, con
     return MGX_OK;
 }
 
-// The roll-out over in-place episodes: one launch of rollout_episodes_kernel (mgx_episodes.hip) or -- rows != NULL -- of
-// rollout_episodes_rows_kernel (mgx_episode_rows.hip), every check before it.
-static int rollout_episodes_impl(mgx_handle *h, const uint8_t *action_id, int per_step, const int32_t *table, int32_t n_actions,
-                                 int32_t K, double *reward, uint8_t *done, double *soc_trace, uint32_t *status_trace,
-                                 const mgx_episode_stats *stats, const mgx_episode_rows *rows, mgx_stream stream, const char *fn)
+// What the four calls share before their launch: every refusal, the counter's range, the roll-out's table (`table` NULL: the
+// K-step), where the rows come from, the launch shape and the upload of the KArgs.  R.e then lacks only the fields its call owns.
+static int prepare_episode_launch(mgx_handle *h, int32_t K, double *reward, uint8_t *done, double *soc_trace, uint32_t *status_trace,
+                                  const mgx_episode_stats *stats, const mgx_episode_rows *rows, mgx_stream stream, const char *fn,
+                                  const char *lockstep, const char *single, const int32_t *table, int32_t n_actions, PLWords *tab,
+                                  EpisodeRowsLaunch &R)
 {
-    if (!h || !action_id || !table) return fail(MGX_ERR_INVALID, "%s: NULL argument", fn);
-    if (int rc = episodes_launch_refusal(h, K, done, fn, "mgx_rollout_discrete", "mgx_step_lists")) return rc;
+    if (int rc = episodes_launch_refusal(h, K, done, fn, lockstep, single)) return rc;
     if (rows) {
         if (int rc = episode_rows_refusal(h, rows, fn)) return rc;
     } else if (h->k.final_obs) {
@@ -2014,33 +2014,54 @@ static int rollout_episodes_impl(mgx_handle *h, const uint8_t *action_id, int pe
     }
     if (h->t < 0 || (int64_t)h->t + K > step_limit(h))
         return fail(MGX_ERR_RANGE, "%s: steps [%d, %d) leave the counter's range", fn, h->t, h->t + K);
-    PLWords tab;
-    if (int rc = encode_table(h, table, n_actions, &tab, fn)) return rc;
-    EpisodeLaunch L;
+    if (table) {
+        if (int rc = encode_table(h, table, n_actions, tab, fn)) return rc;
+    }
+    EpisodeLaunch &L = R.e;
     L.flags = h->flags;
     L.src = factorised(h->k.c) ? EP_SRC_FACT : (h->k.pm_pitch ? EP_SRC_GRID_MAJOR : EP_SRC_GATHER);
     if (L.src == EP_SRC_FACT && !h->k.pm_pitch)
         return fail(MGX_ERR_INVALID, "%s: the handle holds no profile-major base tables", fn);
-    L.per_step = per_step != 0;
     L.gpb = fused_grids_per_block(h, h->k.N);
     L.blocks = (unsigned)((h->k.N + L.gpb - 1) / L.gpb);
     L.stream = (hipStream_t)stream;
     // what a restart reads (the draw's arguments, the episode arrays) comes from the handle's device copy of the KArgs
-    if (int rc = sync_device_kargs(h, L.stream, "mgx_rollout_episodes: uploading the kernel arguments")) return rc;
-    L.k = &h->k; L.k_dev = h->d_kargs; L.tab = &tab; L.ids = action_id;
+    char who[96];
+    snprintf(who, sizeof(who), "%s: uploading the kernel arguments", fn);
+    if (int rc = sync_device_kargs(h, L.stream, who)) return rc;
+    L.k = &h->k; L.k_dev = h->d_kargs;
     L.t = h->t; L.K = K;
     L.out = FusedOut{reward, done, soc_trace, status_trace, nullptr, nullptr};
     L.stats = stats ? *stats : mgx_episode_stats{nullptr, nullptr, nullptr, nullptr};
-    if (rows) {
-        const EpisodeRowsLaunch R{L, rows->obs, rows->final_obs};
-        if (!(launch_rollout_episodes_rows_p0(R) || launch_rollout_episodes_rows_p1(R)))
-            return fail(MGX_ERR_UNSUPPORTED, "%s: no kernel for layout flags %d", fn, h->flags);
-    } else if (!(launch_rollout_episodes_p0(L) || launch_rollout_episodes_p1(L)))
-        return fail(MGX_ERR_UNSUPPORTED, "%s: no kernel for layout flags %d", fn, h->flags);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, rows ? "rollout_episodes_rows_kernel launch" : "rollout_episodes_kernel launch");
-    advance(h, K, L.stream);
+    if (rows) { R.obs = rows->obs; R.final_obs = rows->final_obs; }
     return MGX_OK;
+}
+
+// ... and behind it (`launched`: a slice holds the kernel of the handle's layout and has launched it)
+static int finish_episode_launch(mgx_handle *h, const EpisodeLaunch &L, bool launched, const char *what, const char *fn)
+{
+    if (!launched) return fail(MGX_ERR_UNSUPPORTED, "%s: no kernel for layout flags %d", fn, h->flags);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, what);
+    advance(h, L.K, L.stream);
+    return MGX_OK;
+}
+
+// The roll-out over in-place episodes: one launch of rollout_episodes_kernel (mgx_episodes.hip) or -- rows != NULL -- of
+// rollout_episodes_rows_kernel (mgx_episode_rows.hip), every check before it.
+static int rollout_episodes_impl(mgx_handle *h, const uint8_t *action_id, int per_step, const int32_t *table, int32_t n_actions,
+                                 int32_t K, double *reward, uint8_t *done, double *soc_trace, uint32_t *status_trace,
+                                 const mgx_episode_stats *stats, const mgx_episode_rows *rows, mgx_stream stream, const char *fn)
+{
+    if (!h || !action_id || !table) return fail(MGX_ERR_INVALID, "%s: NULL argument", fn);
+    PLWords tab;
+    EpisodeRowsLaunch R{};
+    if (int rc = prepare_episode_launch(h, K, reward, done, soc_trace, status_trace, stats, rows, stream, fn, "mgx_rollout_discrete",
+                                        "mgx_step_lists", table, n_actions, &tab, R)) return rc;
+    R.e.per_step = per_step != 0; R.e.tab = &tab; R.e.ids = action_id;
+    const bool launched = rows ? launch_rollout_episodes_rows_p0(R) || launch_rollout_episodes_rows_p1(R)
+                               : launch_rollout_episodes_p0(R.e) || launch_rollout_episodes_p1(R.e);
+    return finish_episode_launch(h, R.e, launched, rows ? "rollout_episodes_rows_kernel launch" : "rollout_episodes_kernel launch", fn);
 }
 
 int mgx_rollout_episodes(mgx_handle *h, const uint8_t *action_id, int per_step, const int32_t *table, int32_t n_actions,
@@ -2072,39 +2093,13 @@ static int step_k_episodes_impl(mgx_handle *h, const void *actions, int32_t K, i
                                 const mgx_episode_rows *rows, mgx_stream stream, const char *fn)
 {
     if (!h || (h->action_dim > 0 && !actions)) return fail(MGX_ERR_INVALID, "%s: NULL argument", fn);
-    if (int rc = episodes_launch_refusal(h, K, done, fn, "mgx_step_k", "mgx_step")) return rc;
-    if (rows) {
-        if (int rc = episode_rows_refusal(h, rows, fn)) return rc;
-    } else if (h->k.final_obs) {
-        return fail(MGX_ERR_UNSUPPORTED, "%s: mgx_set_final_obs is set but the call writes no observations", fn);
-    }
-    if (h->t < 0 || (int64_t)h->t + K > step_limit(h))
-        return fail(MGX_ERR_RANGE, "%s: steps [%d, %d) leave the counter's range", fn, h->t, h->t + K);
-    StepEpisodeLaunch L;
-    L.flags = h->flags;
-    L.src = factorised(h->k.c) ? EP_SRC_FACT : (h->k.pm_pitch ? EP_SRC_GRID_MAJOR : EP_SRC_GATHER);
-    if (L.src == EP_SRC_FACT && !h->k.pm_pitch)
-        return fail(MGX_ERR_INVALID, "%s: the handle holds no profile-major base tables", fn);
-    L.act_f32 = h->k.act_f32 != 0;
-    L.gpb = fused_grids_per_block(h, h->k.N);
-    L.blocks = (unsigned)((h->k.N + L.gpb - 1) / L.gpb);
-    L.stream = (hipStream_t)stream;
-    // what a restart reads (the draw's arguments, the episode arrays) comes from the handle's device copy of the KArgs
-    if (int rc = sync_device_kargs(h, L.stream, "mgx_step_k_episodes: uploading the kernel arguments")) return rc;
-    L.k = &h->k; L.k_dev = h->d_kargs; L.actions = actions;
-    L.t = h->t; L.K = K; L.normalized = normalized;
-    L.out = FusedOut{reward, done, soc_trace, status_trace, nullptr, nullptr};
-    L.stats = stats ? *stats : mgx_episode_stats{nullptr, nullptr, nullptr, nullptr};
-    if (rows) {
-        const StepEpisodeRowsLaunch R{L, rows->obs, rows->final_obs};
-        if (!(launch_step_k_episodes_rows_p0(R) || launch_step_k_episodes_rows_p1(R)))
-            return fail(MGX_ERR_UNSUPPORTED, "%s: no kernel for layout flags %d", fn, h->flags);
-    } else if (!(launch_step_k_episodes_p0(L) || launch_step_k_episodes_p1(L)))
-        return fail(MGX_ERR_UNSUPPORTED, "%s: no kernel for layout flags %d", fn, h->flags);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, rows ? "step_k_episodes_rows_kernel launch" : "step_k_episodes_kernel launch");
-    advance(h, K, L.stream);
-    return MGX_OK;
+    EpisodeRowsLaunch R{};
+    if (int rc = prepare_episode_launch(h, K, reward, done, soc_trace, status_trace, stats, rows, stream, fn, "mgx_step_k", "mgx_step",
+                                        nullptr, 0, nullptr, R)) return rc;
+    R.e.actions = actions; R.e.act_f32 = h->k.act_f32 != 0; R.e.normalized = normalized;
+    const bool launched = rows ? launch_step_k_episodes_rows_p0(R) || launch_step_k_episodes_rows_p1(R)
+                               : launch_step_k_episodes_p0(R.e) || launch_step_k_episodes_p1(R.e);
+    return finish_episode_launch(h, R.e, launched, rows ? "step_k_episodes_rows_kernel launch" : "step_k_episodes_kernel launch", fn);
 }
 
 int mgx_step_k_episodes(mgx_handle *h, const void *actions, int32_t K, int normalized, double *reward, uint8_t *done,

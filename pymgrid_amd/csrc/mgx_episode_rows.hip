@@ -1,25 +1,16 @@
 // mgx_episode_rows.hip -- the fused discrete roll-out over per-grid in-place episodes WITH observation rows
 // (mgx_rollout_episodes_rows): rollout_episodes_kernel (mgx_episodes.hip) + per step the H = 0 row the step returned and, where a
-// grid restarts, the row before the restart.  Translation units of their own (MGX_EPISODE_ROWS_PARTS slices of the layouts):
+// grid restarts, the row before the restart.  Translation units of their own (MGX_EPISODE_PARTS slices of the layouts):
 //   hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -c -DMGX_EPISODE_ROWS_PART=p mgx_episode_rows.hip -o mgx_episode_rows_p.o
 // so every other kernel comes out of the compiler exactly as it did without this file.
 #include "mgx_episode_rows.hpp"
 
 #ifndef MGX_EPISODE_ROWS_PART
-#error "compile with -DMGX_EPISODE_ROWS_PART=<0..MGX_EPISODE_ROWS_PARTS-1>"
+#error "compile with -DMGX_EPISODE_ROWS_PART=<0..MGX_EPISODE_PARTS-1>"
 #endif
 
-// layouts (template parameter F) of each slice; together: 0..7, 14, 15 (MGX_DISPATCH_F in mgx_abi.hip)
-#if MGX_EPISODE_ROWS_PART == 0
-#define MGX_PART_FLAGS(X) X(0) X(1) X(2) X(3) X(4) X(5)
-#elif MGX_EPISODE_ROWS_PART == 1
-#define MGX_PART_FLAGS(X) X(6) X(7) X(14) X(15)
-#else
-#error "MGX_EPISODE_ROWS_PART out of range"
-#endif
-
-#define MGX_CAT2(a, b) a##b
-#define MGX_CAT(a, b) MGX_CAT2(a, b)
+// layouts (template parameter F) of this slice: MGX_EPISODE_FLAGS_<part> (mgx_kernels.hpp)
+#define MGX_PART_FLAGS MGX_CAT(MGX_EPISODE_FLAGS_, MGX_EPISODE_ROWS_PART)
 
 namespace mgx {
 

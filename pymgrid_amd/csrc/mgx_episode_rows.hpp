@@ -248,16 +248,10 @@ struct StepRowsArgs {
 
 // ---- host side: what mgx_abi.hip hands the slices of the two translation units ----
 struct EpisodeRowsLaunch {
-    EpisodeLaunch e;                 // as for rollout_episodes_kernel
+    EpisodeLaunch e;                 // as for rollout_episodes_kernel / step_k_episodes_kernel
     void *obs, *final_obs;           // [K, N, D] in the handle's observation format; each may be NULL (not both)
 };
-constexpr int MGX_EPISODE_ROWS_PARTS = 2;
 bool launch_rollout_episodes_rows_p0(const EpisodeRowsLaunch &L); bool launch_rollout_episodes_rows_p1(const EpisodeRowsLaunch &L);
-struct StepEpisodeRowsLaunch {
-    StepEpisodeLaunch e;             // as for step_k_episodes_kernel
-    void *obs, *final_obs;
-};
-constexpr int MGX_STEP_EPISODE_ROWS_PARTS = 2;
-bool launch_step_k_episodes_rows_p0(const StepEpisodeRowsLaunch &L); bool launch_step_k_episodes_rows_p1(const StepEpisodeRowsLaunch &L);
+bool launch_step_k_episodes_rows_p0(const EpisodeRowsLaunch &L); bool launch_step_k_episodes_rows_p1(const EpisodeRowsLaunch &L);
 
 }  // namespace mgx

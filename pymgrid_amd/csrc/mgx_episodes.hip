@@ -9,17 +9,8 @@
 #error "compile with -DMGX_EPISODE_PART=<0..MGX_EPISODE_PARTS-1>"
 #endif
 
-// layouts (template parameter F) of each slice; together: 0..7, 14, 15 (MGX_DISPATCH_F in mgx_abi.hip)
-#if MGX_EPISODE_PART == 0
-#define MGX_PART_FLAGS(X) X(0) X(1) X(2) X(3) X(4) X(5)
-#elif MGX_EPISODE_PART == 1
-#define MGX_PART_FLAGS(X) X(6) X(7) X(14) X(15)
-#else
-#error "MGX_EPISODE_PART out of range"
-#endif
-
-#define MGX_CAT2(a, b) a##b
-#define MGX_CAT(a, b) MGX_CAT2(a, b)
+// layouts (template parameter F) of this slice: MGX_EPISODE_FLAGS_<part> (mgx_kernels.hpp)
+#define MGX_PART_FLAGS MGX_CAT(MGX_EPISODE_FLAGS_, MGX_EPISODE_PART)
 
 namespace mgx {
 

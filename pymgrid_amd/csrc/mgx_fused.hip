@@ -26,9 +26,6 @@
 #error "MGX_FUSED_PART out of range"
 #endif
 
-#define MGX_CAT2(a, b) a##b
-#define MGX_CAT(a, b) MGX_CAT2(a, b)
-
 #if MGX_FUSED_PART == 5
 // The general path's K-step launch with the instance counts fixed at compile time (step_k_multi_small_kernel<F, CountsCT<...>>):
 // (n_genset, n_battery, n_grid, n_load, n_pv) of the layouts that occur most; every other small layout takes the run-time-count

@@ -649,45 +649,37 @@ bool launch_step_k_p0(const FusedLaunch &L); bool launch_step_k_p1(const FusedLa
 bool launch_step_k_p3(const FusedLaunch &L); bool launch_step_k_p4(const FusedLaunch &L);
 bool launch_rollout_p0(const FusedLaunch &L); bool launch_rollout_p1(const FusedLaunch &L); bool launch_rollout_p2(const FusedLaunch &L);
 bool launch_rollout_p3(const FusedLaunch &L); bool launch_rollout_p4(const FusedLaunch &L);
-// mgx_rollout_episodes: the episode form of the discrete roll-out (rollout_episodes_kernel, mgx_episodes.hip -- translation
-// units of its own, so that the lock-step kernels above are compiled exactly as before)
+// The fused launches over in-place episodes: mgx_rollout_episodes (rollout_episodes_kernel, mgx_episodes.hip) and its continuous twin
+// mgx_step_k_episodes (step_k_episodes_kernel, mgx_step_episodes.hip) -- translation units of their own, so that the lock-step kernels
+// above are compiled exactly as before.  One descriptor serves both: a call fills the fields of its kind and leaves the others unset.
 enum : int { EP_SRC_FACT = 0, EP_SRC_GRID_MAJOR = 1, EP_SRC_GATHER = 2 };    // where a lane finds the rows of its series
 struct EpisodeLaunch {
     int flags;                       // layout (template parameter F)
     int src;                         // EP_SRC_*
-    bool per_step;
     unsigned blocks;
     int32_t gpb;
     hipStream_t stream;
     const KArgs *k;
     const KArgs *k_dev;              // the handle's device copy of *k (what a restart reads)
-    const PLWords *tab;
-    const uint8_t *ids;              // list ids [K, N] or [N]
+    bool per_step;                   // roll-out: ids [K, N] (else [N])
+    const PLWords *tab;              // roll-out: priority-list table
+    const uint8_t *ids;              // roll-out: list ids
+    const void *actions;             // K-step: controls [K, N, A] in the handle's action format
+    bool act_f32;                    // K-step: the controls are float32
+    int normalized;                  // K-step
     int32_t t, K;
     FusedOut out;                    // (ret_acc and log stay NULL)
     mgx_episode_stats stats;
 };
+// Each of the four translation units (those two and their forms with rows, mgx_episode_rows.hpp) is compiled in MGX_EPISODE_PARTS
+// slices of the layouts (template parameter F); together: 0..7, 14, 15 (MGX_DISPATCH_F in mgx_abi.hip)
 constexpr int MGX_EPISODE_PARTS = 2;
+#define MGX_EPISODE_FLAGS_0(X) X(0) X(1) X(2) X(3) X(4) X(5)
+#define MGX_EPISODE_FLAGS_1(X) X(6) X(7) X(14) X(15)
+#define MGX_CAT2(a, b) a##b
+#define MGX_CAT(a, b) MGX_CAT2(a, b)
 bool launch_rollout_episodes_p0(const EpisodeLaunch &L); bool launch_rollout_episodes_p1(const EpisodeLaunch &L);
-// mgx_step_k_episodes: the continuous K-step over in-place episodes (step_k_episodes_kernel, mgx_step_episodes.hip -- again
-// translation units of its own)
-struct StepEpisodeLaunch {
-    int flags;                       // layout (template parameter F)
-    int src;                         // EP_SRC_*
-    bool act_f32;
-    unsigned blocks;
-    int32_t gpb;
-    hipStream_t stream;
-    const KArgs *k;
-    const KArgs *k_dev;              // the handle's device copy of *k (what a restart reads)
-    const void *actions;             // controls [K, N, A] in the handle's action format
-    int32_t t, K;
-    int normalized;
-    FusedOut out;                    // (ret_acc and log stay NULL)
-    mgx_episode_stats stats;
-};
-constexpr int MGX_STEP_EPISODE_PARTS = 2;
-bool launch_step_k_episodes_p0(const StepEpisodeLaunch &L); bool launch_step_k_episodes_p1(const StepEpisodeLaunch &L);
+bool launch_step_k_episodes_p0(const EpisodeLaunch &L); bool launch_step_k_episodes_p1(const EpisodeLaunch &L);
 
 // ------------------------------------------------------------------------------------------------------
 // Observation of the current state (reset(), or after step_k).

@@ -1,31 +1,22 @@
 // mgx_step_episode_rows.hip -- the fused continuous K-step over per-grid in-place episodes WITH observation rows
 // (mgx_step_k_episodes_rows): step_k_episodes_kernel (mgx_step_episodes.hip) + per step the H = 0 row the step returned and, where
 // a grid restarts, the row before the restart.  The continuous twin of rollout_episodes_rows_kernel (mgx_episode_rows.hip).
-// Translation units of their own (MGX_STEP_EPISODE_ROWS_PARTS slices of the layouts):
+// Translation units of their own (MGX_EPISODE_PARTS slices of the layouts):
 //   hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -c -DMGX_STEP_EPISODE_ROWS_PART=p mgx_step_episode_rows.hip -o mgx_step_episode_rows_p.o
 // so every other kernel comes out of the compiler exactly as it did without this file.
 #include "mgx_episode_rows.hpp"
 
 #ifndef MGX_STEP_EPISODE_ROWS_PART
-#error "compile with -DMGX_STEP_EPISODE_ROWS_PART=<0..MGX_STEP_EPISODE_ROWS_PARTS-1>"
+#error "compile with -DMGX_STEP_EPISODE_ROWS_PART=<0..MGX_EPISODE_PARTS-1>"
 #endif
 
-// layouts (template parameter F) of each slice; together: 0..7, 14, 15 (MGX_DISPATCH_F in mgx_abi.hip)
-#if MGX_STEP_EPISODE_ROWS_PART == 0
-#define MGX_PART_FLAGS(X) X(0) X(1) X(2) X(3) X(4) X(5)
-#elif MGX_STEP_EPISODE_ROWS_PART == 1
-#define MGX_PART_FLAGS(X) X(6) X(7) X(14) X(15)
-#else
-#error "MGX_STEP_EPISODE_ROWS_PART out of range"
-#endif
+// layouts (template parameter F) of this slice: MGX_EPISODE_FLAGS_<part> (mgx_kernels.hpp)
+#define MGX_PART_FLAGS MGX_CAT(MGX_EPISODE_FLAGS_, MGX_STEP_EPISODE_ROWS_PART)
 
 // depth of the action ring (steps of control loads in flight), as step_k_episodes_kernel's
 #ifndef MGX_RING_STEP_EPISODES
 #define MGX_RING_STEP_EPISODES 4
 #endif
-
-#define MGX_CAT2(a, b) a##b
-#define MGX_CAT(a, b) MGX_CAT2(a, b)
 
 namespace mgx {
 
@@ -146,9 +137,9 @@ __global__ __launch_bounds__(BLOCK_K) void step_k_episodes_rows_kernel(const Ste
 }
 
 template <int F, typename AT>
-static void step_k_episodes_rows_dispatch(const StepEpisodeRowsLaunch &R)
+static void step_k_episodes_rows_dispatch(const EpisodeRowsLaunch &R)
 {
-    const StepEpisodeLaunch &L = R.e;
+    const EpisodeLaunch &L = R.e;
     // row ring as rollout_episodes_kernel's: a slot of a layout with a GridModule holds up to six values (depth 4), else two (depth 8)
     const StepRowsArgs g{*L.k, L.actions, L.t, L.K, L.normalized, L.gpb, L.out, L.stats, pack_row_desc(*L.k), L.k_dev, R.obs, R.final_obs};
 #define MGX_STEP_EPISODES(SRC) step_k_episodes_rows_kernel<F, (F & F_GRID) ? 4 : MGX_RING_ROLLOUT, MGX_RING_STEP_EPISODES, AT, SRC><<<L.blocks, BLOCK_K, 0, L.stream>>>(g)
@@ -158,7 +149,7 @@ static void step_k_episodes_rows_dispatch(const StepEpisodeRowsLaunch &R)
 #undef MGX_STEP_EPISODES
 }
 
-bool MGX_CAT(launch_step_k_episodes_rows_p, MGX_STEP_EPISODE_ROWS_PART)(const StepEpisodeRowsLaunch &R)
+bool MGX_CAT(launch_step_k_episodes_rows_p, MGX_STEP_EPISODE_ROWS_PART)(const EpisodeRowsLaunch &R)
 {
     switch (R.e.flags) {
 #define X(FV) case FV: if (R.e.act_f32) step_k_episodes_rows_dispatch<FV, float>(R); else step_k_episodes_rows_dispatch<FV, double>(R); return true;

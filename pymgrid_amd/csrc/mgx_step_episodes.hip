@@ -1,31 +1,22 @@
 // mgx_step_episodes.hip -- the fused continuous K-step over per-grid in-place episodes (mgx_step_k_episodes): K steps of
 // Microgrid.run(control, normalized) per launch, the controls out of an action stream [K, N, A], every lane on the rows of its OWN
 // episode and restarting inside the launch.  The continuous twin of rollout_episodes_kernel (mgx_episodes.hip).
-// Translation units of their own (MGX_STEP_EPISODE_PARTS slices of the layouts, compiled in parallel like mgx_episodes.hip):
+// Translation units of their own (MGX_EPISODE_PARTS slices of the layouts, compiled in parallel like mgx_episodes.hip):
 //   hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -c -DMGX_STEP_EPISODE_PART=p mgx_step_episodes.hip -o mgx_step_episodes_p.o
 // so every other kernel comes out of the compiler exactly as it did without this file.
 #include "mgx_kernels.hpp"
 
 #ifndef MGX_STEP_EPISODE_PART
-#error "compile with -DMGX_STEP_EPISODE_PART=<0..MGX_STEP_EPISODE_PARTS-1>"
+#error "compile with -DMGX_STEP_EPISODE_PART=<0..MGX_EPISODE_PARTS-1>"
 #endif
 
-// layouts (template parameter F) of each slice; together: 0..7, 14, 15 (MGX_DISPATCH_F in mgx_abi.hip)
-#if MGX_STEP_EPISODE_PART == 0
-#define MGX_PART_FLAGS(X) X(0) X(1) X(2) X(3) X(4) X(5)
-#elif MGX_STEP_EPISODE_PART == 1
-#define MGX_PART_FLAGS(X) X(6) X(7) X(14) X(15)
-#else
-#error "MGX_STEP_EPISODE_PART out of range"
-#endif
+// layouts (template parameter F) of this slice: MGX_EPISODE_FLAGS_<part> (mgx_kernels.hpp)
+#define MGX_PART_FLAGS MGX_CAT(MGX_EPISODE_FLAGS_, MGX_STEP_EPISODE_PART)
 
 // depth of the action ring (steps of control loads in flight); the row ring's depth is the discrete kernel's
 #ifndef MGX_RING_STEP_EPISODES
 #define MGX_RING_STEP_EPISODES 4
 #endif
-
-#define MGX_CAT2(a, b) a##b
-#define MGX_CAT(a, b) MGX_CAT2(a, b)
 
 namespace mgx {
 
@@ -185,7 +176,7 @@ __global__ __launch_bounds__(BLOCK_K) void step_k_episodes_kernel(const KArgs a,
 }
 
 template <int F, typename AT>
-static void step_k_episodes_dispatch(const StepEpisodeLaunch &L)
+static void step_k_episodes_dispatch(const EpisodeLaunch &L)
 {
     // row ring as rollout_episodes_kernel's: a slot of a layout with a GridModule holds up to six values (depth 4), else two (depth 8)
 #define MGX_STEP_EPISODES(SRC) step_k_episodes_kernel<F, (F & F_GRID) ? 4 : MGX_RING_ROLLOUT, MGX_RING_STEP_EPISODES, AT, SRC><<<L.blocks, BLOCK_K, 0, L.stream>>>( \
@@ -196,7 +187,7 @@ static void step_k_episodes_dispatch(const StepEpisodeLaunch &L)
 #undef MGX_STEP_EPISODES
 }
 
-bool MGX_CAT(launch_step_k_episodes_p, MGX_STEP_EPISODE_PART)(const StepEpisodeLaunch &L)
+bool MGX_CAT(launch_step_k_episodes_p, MGX_STEP_EPISODE_PART)(const EpisodeLaunch &L)
 {
     switch (L.flags) {
 #define X(FV) case FV: if (L.act_f32) step_k_episodes_dispatch<FV, float>(L); else step_k_episodes_dispatch<FV, double>(L); return true;

@@ -564,32 +564,43 @@ class StepEngine:
             self._t += 1
         return obs, reward, done, log
 
+    def _fused_outputs(self, out, K, reward, done, soc_trace, status_trace, log=False, ret_acc=None, done_bits=False):
+        """The outputs of a fused K-step call: (result dict, reward, done, soc_trace, status_trace, log) -- each tensor taken from
+        ``out``, allocated, or None where it is not asked for (the traces also where the layout has no battery / genset).
+        ``done_bits``: the call honours ``set_done_format`` (bit sets [K, ceil(N / 16)] int16 instead of bytes [K, N])."""
+        N, res, bufs = self.N, {}, []
+        bits = done_bits and getattr(self, "_done_bits", False)
+        for name, want, shape, dtype in (
+                ("reward", reward, (K, N), torch.float64),
+                ("done", done, (K, (N + 15) // 16) if bits else (K, N), torch.int16 if bits else torch.uint8),
+                ("soc_trace", soc_trace and self.layout.has_battery, (K, N), torch.float64),
+                ("status_trace", status_trace and self.layout.has_genset, (K, N), torch.int32),
+                ("log", log, (K, self.log_dim, N), torch.float64)):
+            t = None
+            if want:
+                t = out.get(name)
+                if t is None:
+                    t = self._empty(*shape, dtype=dtype)
+                res[name] = t
+            bufs.append(t)
+        if ret_acc is not None:
+            res["ret_acc"] = ret_acc
+        return (res, *bufs)
+
+    def _check_ids(self, action_id, K, dtype):
+        """Priority-list ids of a fused call: [K, N] (an id per step) or [N] (one fixed list per grid)."""
+        if action_id.dtype != dtype or action_id.device != self.device or not action_id.is_contiguous() \
+                or tuple(action_id.shape) not in ((K, self.N), (self.N,)):
+            name = str(dtype).replace("torch.", "")
+            raise ValueError(f"action_id must be a contiguous {name} tensor [{K}, {self.N}] or [{self.N}] on {self.device}")
+
     def step_k(self, actions, normalized=True, reward=True, done=False, soc_trace=False, status_trace=False,
                ret_acc=None, log=False, out=None):
         """K fused steps (actions [K, N, A]).  Returns a dict of the requested [K, N] outputs."""
         out = out or {}
         K = int(actions.shape[0]) if actions is not None else int(out["K"])
         actions = self._check_actions(actions, (K,))
-        res = {}
-
-        def buf(name, want, *shape, dtype=torch.float64):
-            if not want:
-                return None
-            t = out.get(name)
-            if t is None:
-                t = self._empty(*shape, dtype=dtype)
-            res[name] = t
-            return t
-        r = buf("reward", reward, K, self.N)
-        if getattr(self, "_done_bits", False):
-            d = buf("done", done, K, (self.N + 15) // 16, dtype=torch.int16)
-        else:
-            d = buf("done", done, K, self.N, dtype=torch.uint8)
-        s = buf("soc_trace", soc_trace and self.layout.has_battery, K, self.N)
-        g = buf("status_trace", status_trace and self.layout.has_genset, K, self.N, dtype=torch.int32)
-        lg = buf("log", log, K, self.log_dim, self.N)
-        if ret_acc is not None:
-            res["ret_acc"] = ret_acc
+        res, r, d, s, g, lg = self._fused_outputs(out, K, reward, done, soc_trace, status_trace, log, ret_acc, done_bits=True)
         self._call(self._lib.mgx_step_k, _ptr(actions), K, 1 if normalized else 0, _ptr(r), _ptr(d), _ptr(s), _ptr(g),
                    _ptr(ret_acc), _ptr(lg))
         if self._t is not None:
@@ -668,31 +679,10 @@ class StepEngine:
         [N] (one fixed priority list per grid: rule-based control).  Returns the requested [K, N] outputs."""
         out = out or {}
         K = int(K)
-        if action_id.dtype != torch.uint8 or action_id.device != self.device or not action_id.is_contiguous() \
-                or tuple(action_id.shape) not in ((K, self.N), (self.N,)):
-            raise ValueError(f"action_id must be a contiguous uint8 tensor [{K}, {self.N}] or [{self.N}] on {self.device}")
+        self._check_ids(action_id, K, torch.uint8)
         per_step = int(action_id.dim() == 2)
         tptr, n_lists = self._table_ptr(table)
-        res = {}
-
-        def buf(name, want, *shape, dtype=torch.float64):
-            if not want:
-                return None
-            t = out.get(name)
-            if t is None:
-                t = self._empty(*shape, dtype=dtype)
-            res[name] = t
-            return t
-        r = buf("reward", reward, K, self.N)
-        if getattr(self, "_done_bits", False):
-            d = buf("done", done, K, (self.N + 15) // 16, dtype=torch.int16)
-        else:
-            d = buf("done", done, K, self.N, dtype=torch.uint8)
-        s = buf("soc_trace", soc_trace and self.layout.has_battery, K, self.N)
-        g = buf("status_trace", status_trace and self.layout.has_genset, K, self.N, dtype=torch.int32)
-        lg = buf("log", log, K, self.log_dim, self.N)
-        if ret_acc is not None:
-            res["ret_acc"] = ret_acc
+        res, r, d, s, g, lg = self._fused_outputs(out, K, reward, done, soc_trace, status_trace, log, ret_acc, done_bits=True)
         self._call(self._lib.mgx_rollout_discrete, _ptr(action_id), per_step, tptr,
                    n_lists, K, _ptr(r), _ptr(d), _ptr(s), _ptr(g), _ptr(ret_acc), _ptr(lg))
         if self._t is not None:
@@ -725,6 +715,30 @@ class StepEngine:
             setattr(rows, name, _ptr(t))
         return rows
 
+    def _episode_stats(self, stats):
+        """The ``mgx_episode_stats`` of a fused episode launch out of a dict with any of ``EPISODE_STATS`` (None: no statistics)."""
+        stats = stats or {}
+        unknown = set(stats) - {n for n, _ in self.EPISODE_STATS}
+        if unknown:
+            raise ValueError(f"unknown episode statistics {sorted(unknown)}")
+        st = _lib.EpisodeStats()
+        for name, dtype in self.EPISODE_STATS:
+            t = stats.get(name)
+            if t is not None and (t.dtype != dtype or t.device != self.device or not t.is_contiguous() or tuple(t.shape) != (self.N,)):
+                raise ValueError(f"stats[{name!r}] must be a contiguous {dtype} tensor [{self.N}] on {self.device}")
+            setattr(st, name, _ptr(t))
+        return st
+
+    def _launch_episodes(self, symbol, lead, K, res, bufs, st, out, obs, final_obs):
+        """The tail of the fused episode launches: ``symbol`` (its ``_rows`` form when observation rows are asked for) with the
+        call's own leading arguments ``lead``, then the four outputs, the statistics and the rows; K steps on."""
+        rows = self._episode_rows(res, out, K, obs, final_obs)
+        tail = (C.byref(st),) if rows is None else (C.byref(st), C.byref(rows))
+        self._call(getattr(self._lib, symbol if rows is None else symbol + "_rows"), *lead, *map(_ptr, bufs), *tail)
+        if self._t is not None:
+            self._t += K
+        return res
+
     def rollout_episodes(self, action_id, table, K, reward=True, done=False, soc_trace=False, status_trace=False, stats=None,
                          out=None, obs=False, final_obs=False):
         """K fused discrete steps of a handle in in-place episodes (``reset_episodes``): every grid walks its own episode and --
@@ -736,45 +750,13 @@ class StepEngine:
         grids step k restarts (an allocated ``final_obs`` is zero-filled; pass a tensor through ``out=`` to choose the filling)."""
         out = out or {}
         K = int(K)
-        if action_id.dtype != torch.uint8 or action_id.device != self.device or not action_id.is_contiguous() \
-                or tuple(action_id.shape) not in ((K, self.N), (self.N,)):
-            raise ValueError(f"action_id must be a contiguous uint8 tensor [{K}, {self.N}] or [{self.N}] on {self.device}")
+        self._check_ids(action_id, K, torch.uint8)
         per_step = int(action_id.dim() == 2)
-        stats = stats or {}
-        unknown = set(stats) - {n for n, _ in self.EPISODE_STATS}
-        if unknown:
-            raise ValueError(f"unknown episode statistics {sorted(unknown)}")
-        st = _lib.EpisodeStats()
-        for name, dtype in self.EPISODE_STATS:
-            t = stats.get(name)
-            if t is not None and (t.dtype != dtype or t.device != self.device or not t.is_contiguous() or tuple(t.shape) != (self.N,)):
-                raise ValueError(f"stats[{name!r}] must be a contiguous {dtype} tensor [{self.N}] on {self.device}")
-            setattr(st, name, _ptr(t))
+        st = self._episode_stats(stats)
         tptr, n_lists = self._table_ptr(table)
-        res = {}
-
-        def buf(name, want, *shape, dtype=torch.float64):
-            if not want:
-                return None
-            t = out.get(name)
-            if t is None:
-                t = self._empty(*shape, dtype=dtype)
-            res[name] = t
-            return t
-        r = buf("reward", reward, K, self.N)
-        d = buf("done", done, K, self.N, dtype=torch.uint8)
-        s = buf("soc_trace", soc_trace and self.layout.has_battery, K, self.N)
-        g = buf("status_trace", status_trace and self.layout.has_genset, K, self.N, dtype=torch.int32)
-        rows = self._episode_rows(res, out, K, obs, final_obs)
-        if rows is None:
-            self._call(self._lib.mgx_rollout_episodes, _ptr(action_id), per_step, tptr, n_lists, K, _ptr(r), _ptr(d), _ptr(s), _ptr(g),
-                       C.byref(st))
-        else:
-            self._call(self._lib.mgx_rollout_episodes_rows, _ptr(action_id), per_step, tptr, n_lists, K, _ptr(r), _ptr(d), _ptr(s),
-                       _ptr(g), C.byref(st), C.byref(rows))
-        if self._t is not None:
-            self._t += K
-        return res
+        res, r, d, s, g, _ = self._fused_outputs(out, K, reward, done, soc_trace, status_trace)
+        return self._launch_episodes("mgx_rollout_episodes", (_ptr(action_id), per_step, tptr, n_lists, K), K, res, (r, d, s, g), st, out,
+                                     obs, final_obs)
 
     def step_k_episodes(self, actions, normalized=True, reward=True, done=False, soc_trace=False, status_trace=False, stats=None,
                         out=None, obs=False, final_obs=False):
@@ -786,40 +768,10 @@ class StepEngine:
         out = out or {}
         K = int(actions.shape[0]) if actions is not None else int(out["K"])
         actions = self._check_actions(actions, (K,))
-        stats = stats or {}
-        unknown = set(stats) - {n for n, _ in self.EPISODE_STATS}
-        if unknown:
-            raise ValueError(f"unknown episode statistics {sorted(unknown)}")
-        st = _lib.EpisodeStats()
-        for name, dtype in self.EPISODE_STATS:
-            t = stats.get(name)
-            if t is not None and (t.dtype != dtype or t.device != self.device or not t.is_contiguous() or tuple(t.shape) != (self.N,)):
-                raise ValueError(f"stats[{name!r}] must be a contiguous {dtype} tensor [{self.N}] on {self.device}")
-            setattr(st, name, _ptr(t))
-        res = {}
-
-        def buf(name, want, *shape, dtype=torch.float64):
-            if not want:
-                return None
-            t = out.get(name)
-            if t is None:
-                t = self._empty(*shape, dtype=dtype)
-            res[name] = t
-            return t
-        r = buf("reward", reward, K, self.N)
-        d = buf("done", done, K, self.N, dtype=torch.uint8)
-        s = buf("soc_trace", soc_trace and self.layout.has_battery, K, self.N)
-        g = buf("status_trace", status_trace and self.layout.has_genset, K, self.N, dtype=torch.int32)
-        rows = self._episode_rows(res, out, K, obs, final_obs)
-        if rows is None:
-            self._call(self._lib.mgx_step_k_episodes, _ptr(actions), K, 1 if normalized else 0, _ptr(r), _ptr(d), _ptr(s), _ptr(g),
-                       C.byref(st))
-        else:
-            self._call(self._lib.mgx_step_k_episodes_rows, _ptr(actions), K, 1 if normalized else 0, _ptr(r), _ptr(d), _ptr(s), _ptr(g),
-                       C.byref(st), C.byref(rows))
-        if self._t is not None:
-            self._t += K
-        return res
+        st = self._episode_stats(stats)
+        res, r, d, s, g, _ = self._fused_outputs(out, K, reward, done, soc_trace, status_trace)
+        return self._launch_episodes("mgx_step_k_episodes", (_ptr(actions), K, 1 if normalized else 0), K, res, (r, d, s, g), st, out,
+                                     obs, final_obs)
 
     def rollout_lists(self, action_id, lists, K, reward=True, done=False, soc_trace=False, status_trace=False, ret_acc=None,
                       log=False, out=None):
@@ -827,29 +779,11 @@ class StepEngine:
         ``action_id`` int32 [K, N] (an id per step) or [N] (one fixed list per grid); ``lists`` as for ``expand_lists``."""
         out = out or {}
         K = int(K)
-        if action_id.dtype != torch.int32 or action_id.device != self.device or not action_id.is_contiguous() \
-                or tuple(action_id.shape) not in ((K, self.N), (self.N,)):
-            raise ValueError(f"action_id must be a contiguous int32 tensor [{K}, {self.N}] or [{self.N}] on {self.device}")
+        self._check_ids(action_id, K, torch.int32)
         if lists.dtype != torch.int32 or lists.dim() != 3 or lists.shape[2] != 3 or lists.device != self.device \
                 or not lists.is_contiguous():
             raise ValueError(f"lists must be a contiguous int32 tensor [n_lists, list_len, 3] on {self.device}")
-        res = {}
-
-        def buf(name, want, *shape, dtype=torch.float64):
-            if not want:
-                return None
-            t = out.get(name)
-            if t is None:
-                t = self._empty(*shape, dtype=dtype)
-            res[name] = t
-            return t
-        r = buf("reward", reward, K, self.N)
-        d = buf("done", done, K, self.N, dtype=torch.uint8)
-        s = buf("soc_trace", soc_trace and self.layout.has_battery, K, self.N)
-        g = buf("status_trace", status_trace and self.layout.has_genset, K, self.N, dtype=torch.int32)
-        lg = buf("log", log, K, self.log_dim, self.N)
-        if ret_acc is not None:
-            res["ret_acc"] = ret_acc
+        res, r, d, s, g, lg = self._fused_outputs(out, K, reward, done, soc_trace, status_trace, log, ret_acc)
         self._call(self._lib.mgx_rollout_lists, _ptr(action_id), int(action_id.dim() == 2), _ptr(lists), int(lists.shape[0]),
                    int(lists.shape[1]), K, _ptr(r), _ptr(d), _ptr(s), _ptr(g), _ptr(ret_acc), _ptr(lg))
         if self._t is not None:

@@ -675,30 +675,45 @@ class PerGridWindowEnv:
             info = dict(info, final_observation=final)
         return (new_obs if new_obs is not None else obs), reward, done, info
 
-    def _rollout_refusal(self):
-        """Why ``rollout`` is not offered on this env (None: it is)."""
-        env = self.env
-        if not isinstance(env, DiscreteBatchedMicrogridEnv):
-            return "discrete=False: the fused roll-out expands priority-list ids (continuous action streams: use step_k)"
+    # what differs between the two fused calls in _fused_refusal: the env class the call belongs to, its first line, the lock-step
+    # call auto_reset=False points to, whether check_asserts refuses (the continuous env has none) and the wording
+    _FUSED_KINDS = {
+        "rollout": dict(discrete=True, lockstep="engine.rollout_discrete", asserts=True, what="the roll-out", verb="steps",
+                        wrong_env="discrete=False: the fused roll-out expands priority-list ids (continuous action streams: use step_k)"),
+        "step_k": dict(discrete=False, lockstep="engine.step_k", asserts=False, what="the fused step", verb="walks",
+                       wrong_env="discrete=True: priority-list ids are expanded in the kernel (use rollout)"),
+    }
+
+    def _fused_refusal(self, kind):
+        """Why ``rollout`` / ``step_k`` (``kind``) is not offered on this env (None: it is)."""
+        env, k = self.env, self._FUSED_KINDS[kind]
+        if isinstance(env, DiscreteBatchedMicrogridEnv) != k["discrete"]:
+            return k["wrong_env"]
         if not self.auto_reset:
-            return "auto_reset=False: equal-length windows step in lock-step (engine.rollout_discrete)"
+            return f"auto_reset=False: equal-length windows step in lock-step ({k['lockstep']})"
         if self.generator is not None:
             return "a torch generator: its draws are made on the host between steps"
         if self.full.layout.multi:
             return "several modules of a kind per grid: single steps (the fused kernel holds one module of every kind)"
         if env.raise_errors:
             return "raise_errors=True: every step is preceded by its dry run"
-        if env.check_asserts:
+        if k["asserts"] and env.check_asserts:
             return "check_asserts=True: every step is preceded by its dry run"
         if env._keep_log:
-            return "log=True: the roll-out writes no balance log"
+            return f"log=True: {k['what']} writes no balance log"
         if env._views:
             return "obs_views=True: observation views follow single steps"
         if self.final_observation:
-            return "final_observation=True: the roll-out writes no observations"
+            return f"final_observation=True: {k['what']} writes no observations"
         if not (self.native and self._device_draws):
-            return "native=False: the roll-out steps in-place episodes"
+            return f"native=False: {k['what']} {k['verb']} in-place episodes"
         return None
+
+    def _rollout_refusal(self):
+        return self._fused_refusal("rollout")
+
+    def _step_k_refusal(self):
+        return self._fused_refusal("step_k")
 
     def _rows_refusal(self):
         """Why ``rollout`` / ``step_k`` write no observation rows on this env (None: they do)."""
@@ -708,6 +723,35 @@ class PerGridWindowEnv:
         if self.env.observation_keys is not None:
             return "observation_keys: the launch writes whole rows (select the columns from them, or take single steps)"
         return None
+
+    def _check_fused(self, kind, want_rows):
+        """Refuse ``rollout`` / ``step_k`` (``kind``) where this env does not offer it, or not with observation rows."""
+        why = self._fused_refusal(kind)
+        if why is not None:
+            raise ValueError(f"PerGridWindowEnv.{kind} is not offered with {why}")
+        why = self._rows_refusal() if want_rows else None
+        if why is not None:
+            raise ValueError(f"PerGridWindowEnv.{kind} writes no observations with {why}")
+
+    def _launch_fused(self, launch, observations, final_observations, **kw):
+        """What ``rollout`` and ``step_k`` share around their one engine call ``launch(**kw, stats=, obs=, final_obs=)``: the lazy
+        ``episode_stats``, the bound single-step path and the observation rings set aside and restored, ``done`` as bools."""
+        env = self.env
+        e = env.engine
+        if self.episode_stats is None:
+            self.episode_stats = {name: torch.zeros(e.N, dtype=dtype, device=e.device) for name, dtype in e.EPISODE_STATS}
+        env._unbind_fast()
+        try:
+            if env._ring is not None:
+                e.prefetch_wait()          # (a refill ahead of the counter reads the row offsets the launch rewrites)
+            res = launch(stats=self.episode_stats, obs=bool(observations), final_obs=bool(final_observations), **kw)
+            if env._ring is not None:      # the observation rings: primed again at the grids' current rows, as after a reset
+                env._refill()
+        finally:
+            env._rebind_fast()
+        if "done" in res:
+            res["done"] = res["done"].view(torch.bool)
+        return res
 
     def rollout(self, action_id, K=None, reward=True, done=False, soc_trace=False, status_trace=False, out=None,
                 observations=False, final_observations=False):
@@ -724,17 +768,10 @@ class PerGridWindowEnv:
         observation ``step`` k would have returned, so ``obs[-1]`` is the one the next ``step`` builds on; ``final_obs[k][done[k]]``
         are the rows ``info["final_observation"][done]`` of a ``final_observation=True`` env would have held at step k, the
         other entries are not written (zeros when the call allocates the tensor; pass your own through ``out=``)."""
-        why = self._rollout_refusal()
-        if why is not None:
-            raise ValueError(f"PerGridWindowEnv.rollout is not offered with {why}")
-        if observations or final_observations:
-            why = self._rows_refusal()
-            if why is not None:
-                raise ValueError(f"PerGridWindowEnv.rollout writes no observations with {why}")
+        self._check_fused("rollout", observations or final_observations)
         if self.starts is None:
             raise RuntimeError("rollout() before reset()")
         env = self.env
-        e = env.engine
         dev = self.full.device
         if not torch.is_tensor(action_id):
             action_id = torch.as_tensor(np.asarray(action_id), device=dev)
@@ -745,45 +782,8 @@ class PerGridWindowEnv:
             K = ids.shape[0]
         elif K is None:
             raise ValueError("one fixed id per grid: K (the number of steps) is required")
-        if self.episode_stats is None:
-            self.episode_stats = {name: torch.zeros(e.N, dtype=dtype, device=dev) for name, dtype in e.EPISODE_STATS}
-        env._unbind_fast()
-        try:
-            if env._ring is not None:
-                e.prefetch_wait()          # (a refill ahead of the counter reads the row offsets the launch rewrites)
-            res = e.rollout_episodes(ids, env._table, int(K), reward=reward, done=done, soc_trace=soc_trace,
-                                     status_trace=status_trace, stats=self.episode_stats, out=out, obs=bool(observations),
-                                     final_obs=bool(final_observations))
-            if env._ring is not None:      # the observation rings: primed again at the grids' current rows, as after a reset
-                env._refill()
-        finally:
-            env._rebind_fast()
-        if "done" in res:
-            res["done"] = res["done"].view(torch.bool)
-        return res
-
-    def _step_k_refusal(self):
-        """Why ``step_k`` is not offered on this env (None: it is)."""
-        env = self.env
-        if isinstance(env, DiscreteBatchedMicrogridEnv):
-            return "discrete=True: priority-list ids are expanded in the kernel (use rollout)"
-        if not self.auto_reset:
-            return "auto_reset=False: equal-length windows step in lock-step (engine.step_k)"
-        if self.generator is not None:
-            return "a torch generator: its draws are made on the host between steps"
-        if self.full.layout.multi:
-            return "several modules of a kind per grid: single steps (the fused kernel holds one module of every kind)"
-        if env.raise_errors:
-            return "raise_errors=True: every step is preceded by its dry run"
-        if env._keep_log:
-            return "log=True: the fused step writes no balance log"
-        if env._views:
-            return "obs_views=True: observation views follow single steps"
-        if self.final_observation:
-            return "final_observation=True: the fused step writes no observations"
-        if not (self.native and self._device_draws):
-            return "native=False: the fused step walks in-place episodes"
-        return None
+        return self._launch_fused(lambda **kw: env.engine.rollout_episodes(ids, env._table, int(K), **kw), observations,
+                                  final_observations, reward=reward, done=done, soc_trace=soc_trace, status_trace=status_trace, out=out)
 
     def step_k(self, actions, normalized=True, reward=True, done=False, soc_trace=False, status_trace=False, out=None,
                observations=False, final_observations=False):
@@ -796,36 +796,15 @@ class PerGridWindowEnv:
         Afterwards the env stands where K steps would have left it: the next ``step`` returns the rows its single-stepped twin returns.
         ``observations`` / ``final_observations``: the rows ``obs`` / ``final_obs`` ``[K, N, obs_dim]`` as for ``rollout``
         (``mgx_step_k_episodes_rows``)."""
-        why = self._step_k_refusal()
-        if why is not None:
-            raise ValueError(f"PerGridWindowEnv.step_k is not offered with {why}")
-        if observations or final_observations:
-            why = self._rows_refusal()
-            if why is not None:
-                raise ValueError(f"PerGridWindowEnv.step_k writes no observations with {why}")
+        self._check_fused("step_k", observations or final_observations)
         if self.starts is None:
             raise RuntimeError("step_k() before reset()")
-        env = self.env
-        e = env.engine
+        e = self.env.engine
         if not torch.is_tensor(actions) or actions.dim() != 3:
             raise ValueError(f"actions must be a {e.action_dtype} tensor of shape (K, {e.N}, {e.action_dim}) on {e.device}")
         e._check_actions(actions, (int(actions.shape[0]),))
-        if self.episode_stats is None:
-            self.episode_stats = {name: torch.zeros(e.N, dtype=dtype, device=e.device) for name, dtype in e.EPISODE_STATS}
-        env._unbind_fast()
-        try:
-            if env._ring is not None:
-                e.prefetch_wait()          # (a refill ahead of the counter reads the row offsets the launch rewrites)
-            res = e.step_k_episodes(actions, normalized=normalized, reward=reward, done=done, soc_trace=soc_trace,
-                                    status_trace=status_trace, stats=self.episode_stats, out=out, obs=bool(observations),
-                                    final_obs=bool(final_observations))
-            if env._ring is not None:      # the observation rings: primed again at the grids' current rows, as after a reset
-                env._refill()
-        finally:
-            env._rebind_fast()
-        if "done" in res:
-            res["done"] = res["done"].view(torch.bool)
-        return res
+        return self._launch_fused(lambda **kw: e.step_k_episodes(actions, normalized=normalized, **kw), observations, final_observations,
+                                  reward=reward, done=done, soc_trace=soc_trace, status_trace=status_trace, out=out)
 
     def _next_final_buf(self):
         """One of FINAL_BUFFERS rotating [N, D] buffers for ``info["final_observation"]`` (valid for FINAL_BUFFERS - 1 further steps)."""
@@ -974,22 +953,26 @@ class PerGridWindowFleet:
                 out.append(self._after(pe, plans[k]))
         return tuple(list(x) for x in zip(*out))
 
+    def _refuse_fused(self, kind, name, entries, kw):
+        """Refuse a fleet ``rollout`` / ``step_k`` (``kind``) before anything is launched: one entry of ``entries`` per bucket, every
+        bucket refused as its twin refuses it, and for ``step_k`` every bucket's actions as its engine takes them."""
+        if len(entries) != len(self.envs):
+            raise ValueError(f"{name} holds {len(entries)} entries, the fleet {len(self.envs)} buckets")
+        want_rows = kw.get("observations") or kw.get("final_observations")
+        for pe, a in zip(self.envs, entries):
+            pe._check_fused(kind, want_rows)
+            if kind == "step_k":
+                if not torch.is_tensor(a) or a.dim() != 3:
+                    raise ValueError(f"every entry of {name} must be a [K, n_k, A_k] tensor")
+                pe.env.engine._check_actions(a, (int(a.shape[0]),))
+
     def rollout(self, action_ids, K=None, **kw):
         """``PerGridWindowEnv.rollout`` of every bucket, one launch each, in bucket order (``action_ids``: one entry per bucket,
         ``[K, n_k]`` or ``[n_k]``; keyword arguments as there, ``observations=True`` / ``final_observations=True`` included: every
         bucket's dict then holds its own ``obs`` / ``final_obs`` ``[K, n_k, obs_dim_k]``).  Bucket k is left exactly as its twin's
         ``rollout`` leaves it; a bucket its twin refuses is refused with the same ValueError before anything is launched.  Returns one
         dict per bucket."""
-        if len(action_ids) != len(self.envs):
-            raise ValueError(f"action_ids holds {len(action_ids)} entries, the fleet {len(self.envs)} buckets")
-        want_rows = kw.get("observations") or kw.get("final_observations")
-        for k, pe in enumerate(self.envs):
-            why = pe._rollout_refusal()
-            if why is not None:
-                raise ValueError(f"PerGridWindowEnv.rollout is not offered with {why}")
-            why = pe._rows_refusal() if want_rows else None
-            if why is not None:
-                raise ValueError(f"PerGridWindowEnv.rollout writes no observations with {why}")
+        self._refuse_fused("rollout", "action_ids", action_ids, kw)
         return [pe.rollout(a, K, **kw) for pe, a in zip(self.envs, action_ids)]
 
     def step_k(self, actions_list, **kw):
@@ -997,19 +980,7 @@ class PerGridWindowFleet:
         per bucket; keyword arguments as there, ``observations=True`` / ``final_observations=True`` included).  Bucket k is left
         exactly as its twin's ``step_k`` leaves it; a bucket its twin refuses is refused with the same ValueError before anything is
         launched.  Returns one dict per bucket."""
-        if len(actions_list) != len(self.envs):
-            raise ValueError(f"actions_list holds {len(actions_list)} entries, the fleet {len(self.envs)} buckets")
-        want_rows = kw.get("observations") or kw.get("final_observations")
-        for pe, a in zip(self.envs, actions_list):
-            why = pe._step_k_refusal()
-            if why is not None:
-                raise ValueError(f"PerGridWindowEnv.step_k is not offered with {why}")
-            why = pe._rows_refusal() if want_rows else None
-            if why is not None:
-                raise ValueError(f"PerGridWindowEnv.step_k writes no observations with {why}")
-            if not torch.is_tensor(a) or a.dim() != 3:
-                raise ValueError("every entry of actions_list must be a [K, n_k, A_k] tensor")
-            pe.env.engine._check_actions(a, (int(a.shape[0]),))
+        self._refuse_fused("step_k", "actions_list", actions_list, kw)
         return [pe.step_k(a, **kw) for pe, a in zip(self.envs, actions_list)]
 
     # ---- one bucket's PerGridWindowEnv.step, around the fleet's C call ------------------------------------------------------------

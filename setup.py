@@ -1,8 +1,7 @@
 """pip install -e .   /   python setup.py build_hip
 
-Builds pymgrid_amd/libmgx.so in-tree with hipcc for gfx950 (the same recipe as __graft_entry__.build(): mgx_abi.hip + the
-slices of mgx_fused.hip, mgx_episodes.hip, mgx_step_episodes.hip, mgx_episode_rows.hip and mgx_step_episode_rows.hip compiled in
-parallel, pymgrid_amd/_lib.py) and packages it with the Python surface.  hipcc cross-compiles without a GPU."""
+Builds pymgrid_amd/libmgx.so in-tree with hipcc for gfx950 (the same recipe as __graft_entry__.build(): the translation units
+of ``UNITS`` in pymgrid_amd/_lib.py, compiled in parallel) and packages it with the Python surface.  hipcc cross-compiles without a GPU."""
 import importlib.util
 import os
 

@@ -33,6 +33,32 @@ def test_c_abi_exports_every_declared_symbol():
     assert tuple(names) == _lib.COLUMN_NAMES
 
 
+def test_every_source_is_hashed_and_every_hip_file_is_compiled_once():
+    """A file under csrc/ that ``_lib.SOURCES`` forgets is left out of ``source_hash()``: a stale libmgx.so would pass for current.
+    Every ``.hip`` is the file of exactly one entry of ``_lib.UNITS``, and ``_units`` compiles every entry."""
+    from pymgrid_amd import _lib
+    csrc = os.path.join(ROOT, "pymgrid_amd", "csrc")
+    on_disk = {os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith((".hip", ".hpp"))}      # (not _build*: directories)
+    on_disk.add(os.path.join(ROOT, "include", "mgx.h"))
+    assert all(os.path.isfile(f) for f in on_disk)
+    sources = {os.path.realpath(f) for f in _lib.SOURCES}
+    assert {os.path.realpath(f) for f in on_disk} == sources, {os.path.realpath(f) for f in on_disk} ^ sources
+    assert len(_lib.SOURCES) == len(sources)
+    hip = sorted(os.path.basename(f) for f in on_disk if f.endswith(".hip"))
+    assert sorted(u[0] for u in _lib.UNITS) == hip
+    units = _lib._units("objdir")
+    compiled = {}
+    for src, defs, obj in units:
+        compiled.setdefault(os.path.basename(src), []).append((tuple(defs), obj))
+    assert sorted(compiled) == hip
+    for f, macro, parts in _lib.UNITS:
+        assert parts >= 1 and (macro is not None or parts == 1)
+        assert len(compiled[f]) == parts
+        assert [d for d, _ in compiled[f]] == [((f"-D{macro}={p}",) if macro else ()) for p in range(parts)]
+    assert len({obj for _, _, obj in units}) == len(units)
+    assert os.path.basename(units[0][0]) == "mgx_abi.hip"          # (abi_only variants compile the first unit alone)
+
+
 def test_engine_fails_loudly_without_a_gpu(pymgrid25):
     """No silent CPU fallback: on a host without a HIP device creating an engine is an error."""
     from pymgrid_amd import MgxError, MicrogridBatch, StepEngine, _lib
