@@ -247,6 +247,45 @@ inline void advance(mgx_handle *h, int32_t k, hipStream_t st)
     h->counter_stream = st;      // device-counter mode: the stepping kernel itself advanced the counter (on this stream)
     h->t += k;
 }
+// the tail of a stepping call: its launch error `e` under the kernel's name, or the counter moves on
+inline int finish_step(mgx_handle *h, int32_t K, hipStream_t st, hipError_t e, const char *what)
+{
+    if (e != hipSuccess) return hip_fail(e, what);
+    advance(h, K, st);
+    return MGX_OK;
+}
+
+// the launch error of the calling thread under the kernel's name
+inline int launched(const char *what)
+{
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? MGX_OK : hip_fail(e, what);
+}
+
+// forecast noise depends on (step, horizon index): no two rows share a window
+inline bool noisy(const mgx_columns &c) { return c.load_noise_std || c.pv_noise_std || c.grid_noise_std; }
+// Who writes the observation rows of a step: the step kernel itself -- `obs` comes back -- where they hold no forecast columns (no
+// horizon, or the state columns only); else launch_observe behind it (nullptr).  H is never negative (mgx_create): H == 0 is !(H > 0).
+inline void *rows_inline(const mgx_handle *h, void *obs) { return (obs && (h->k.H == 0 || h->k.obs_state_only)) ? obs : nullptr; }
+// general path: the rows of noisy forecasters come from observe_multi_kernel behind the step (the step kernel carries no noise code)
+inline bool rows_need_noise_pass(const mgx_handle *h, const void *obs) { return obs && !h->k.obs_state_only && noisy(h->k.c); }
+// rings (state-only rows): mgx_patch_windows saves the rows of the restarted grids, the step kernel writes none before a restart
+inline void drop_ring_final_obs(KArgs &k) { if (k.obs_state_only == 1) k.final_obs = nullptr; }
+
+// May the call consume rows [t, t + K)?  (Device-counter mode: the kernels flag an overrun themselves.)  `span`: the wording of the
+// K-step calls, which they keep at K = 1.
+int check_rows(const mgx_handle *h, int32_t K, const char *who, bool span)
+{
+    if (dev_counter(h) || (h->t >= 0 && (int64_t)h->t + K <= step_limit(h))) return MGX_OK;
+    return span ? fail(MGX_ERR_RANGE, "%s: steps [%d, %d) leave the time series (length %d)", who, h->t, h->t + K, step_limit(h))
+                : fail(MGX_ERR_RANGE, "%s: step %d is outside the time series (length %d)", who, h->t, step_limit(h));
+}
+// the shape of a table of priority lists over module instances
+int check_lists(int32_t n_lists, int32_t list_len, const char *who)
+{
+    if (n_lists > 0 && list_len > 0 && list_len <= 3 * MGX_MAX_INSTANCES) return MGX_OK;
+    return fail(MGX_ERR_INVALID, "%s: need n_lists > 0 and list_len in [1, %d]", who, 3 * MGX_MAX_INSTANCES);
+}
 
 // The handle's device for the duration of a scope: streams, events and buffers the library creates lazily must live on
 // the device the batch is on, whatever the caller's current device happens to be.
@@ -338,6 +377,19 @@ static int32_t fused_grids_per_block(const mgx_handle *h, int64_t N)
     return best;
 }
 
+// The fused launch of shard [k.g0, k.g1) on stream `s`: shape, counter and outputs.  The call sets what it owns: the controls and
+// their format (mgx_step_k) or the priority-list table and the ids (mgx_rollout_discrete).
+static FusedLaunch fused_launch_for(const mgx_handle *h, const KArgs &k, hipStream_t s, const FusedOut &fo, int32_t K)
+{
+    FusedLaunch L;
+    L.flags = h->flags; L.act_f32 = false; L.rich = fo.log != nullptr || fo.status_trace != nullptr; L.fact = factorised(k.c); L.per_step = false;
+    L.gpb = fused_grids_per_block(h, k.g1 - k.g0);
+    L.blocks = (unsigned)((k.g1 - k.g0 + L.gpb - 1) / L.gpb);
+    L.stream = s; L.k = &k; L.actions = nullptr; L.tab = nullptr; L.ids = nullptr;
+    L.t = t_arg(h); L.K = K; L.normalized = 0; L.out = fo;
+    return L;
+}
+
 template <int F, bool NOISE, typename OT>
 static void launch_obs_rows_as(const KArgs &k, const WindowPlan &plan, int32_t t, void *obs, unsigned blocks, size_t lds, hipStream_t st)
 {
@@ -350,8 +402,7 @@ template <int F>
 static void launch_obs_rows(const KArgs &k, const WindowPlan &plan, int32_t t, void *obs, unsigned blocks, size_t lds,
                             hipStream_t st)
 {
-    const bool noise = k.c.load_noise_std || k.c.pv_noise_std || k.c.grid_noise_std;
-    if (noise) {
+    if (noisy(k.c)) {
         if (k.obs_f32) launch_obs_rows_as<F, true, float>(k, plan, t, obs, blocks, lds, st);
         else launch_obs_rows_as<F, true, double>(k, plan, t, obs, blocks, lds, st);
     } else {
@@ -360,19 +411,22 @@ static void launch_obs_rows(const KArgs &k, const WindowPlan &plan, int32_t t, v
     }
 }
 
-// the opt-in to more than 64 KB of dynamic LDS is a driver call: made once per kernel and device, not per launch
+// the opt-in to more than 64 KB of dynamic LDS is a driver call: made once per kernel (`opted_in` is the kernel's) and device, not per launch
+static void opt_in_160k_lds(const void *kernel, bool *opted_in)
+{
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    if (dev < 0 || dev >= MGX_MAX_DEVICES || !opted_in[dev]) {
+        (void)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        if (dev >= 0 && dev < MGX_MAX_DEVICES) opted_in[dev] = true;
+    }
+}
+
 template <int F, typename OT>
 static void launch_windows_kernel(const KArgs &k, const WindowsKPlan &plan, int32_t t, void *ring, unsigned blocks, size_t lds, hipStream_t st)
 {
     static bool opted_in[MGX_MAX_DEVICES] = {};
-    if (lds > 64 * 1024) {
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        if (dev < 0 || dev >= MGX_MAX_DEVICES || !opted_in[dev]) {
-            (void)hipFuncSetAttribute((const void *)obs_windows_k_kernel<F, OT>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (dev >= 0 && dev < MGX_MAX_DEVICES) opted_in[dev] = true;
-        }
-    }
+    if (lds > 64 * 1024) opt_in_160k_lds((const void *)obs_windows_k_kernel<F, OT>, opted_in);
     // Threads per refill workgroup (phase 1; phase 2 is always the first 256).  A refill that runs ALONE (the one a reset waits
     // for: with_state) takes all 1 024 -- 12 % faster (profiles/r05/exp_refill_threads.txt); one written AHEAD, beside the step
     // launches, stays at 256: the faster it runs the harder it leans on the memory system and the more the steps beside it pay
@@ -387,14 +441,7 @@ static void launch_windows_multi_kernel(const KArgs &k, const WindowsKPlan &plan
                                         hipStream_t st)
 {
     static bool opted_in[MGX_MAX_DEVICES] = {};
-    if (lds > 64 * 1024) {
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        if (dev < 0 || dev >= MGX_MAX_DEVICES || !opted_in[dev]) {
-            (void)hipFuncSetAttribute((const void *)obs_windows_k_multi_kernel<F, OT>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (dev >= 0 && dev < MGX_MAX_DEVICES) opted_in[dev] = true;
-        }
-    }
+    if (lds > 64 * 1024) opt_in_160k_lds((const void *)obs_windows_k_multi_kernel<F, OT>, opted_in);
     // 1 024 threads for phase 1 here, ahead or not: on the general path the refill -- not the chain of step launches -- sets the
     // pace of a Gym step with rows (1.15 ms per ring of 32 blocks against 0.3 ms of steps).  MGX_TUNE_WIN_THREADS overrides.
     const unsigned forced = (unsigned)tune(MGX_TUNE_WIN_THREADS);
@@ -410,7 +457,7 @@ static int launch_observe(const mgx_handle *h, int32_t t, void *obs, hipStream_t
         MGX_DISPATCH_F(h->flags, (observe_multi_kernel<F><<<multi_blocks(h->k.N), BLOCK_MULTI, 0, st>>>(h->k, t, obs)));
         return MGX_OK;
     }
-    if (h->k.H == 0 || h->k.obs_state_only) {
+    if (rows_inline(h, obs)) {                           // (the rows a step kernel writes, too: `obs` is never NULL here)
         MGX_DISPATCH_F(h->flags, (observe_kernel<F><<<blocks_for(h->k.N), BLOCK, 0, st>>>(h->k, t, obs)));
         return MGX_OK;
     }
@@ -672,8 +719,7 @@ int mgx_use_device_counter(mgx_handle *h, int enable, mgx_stream stream)
         h->k.t_dev = nullptr;
         if (c[1]) return fail(MGX_ERR_RANGE, "a replayed step ran past the end of the time series (length %d)", h->k.T);
     }
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? MGX_OK : hip_fail(e, "mgx_use_device_counter");
+    return launched("mgx_use_device_counter");
 }
 
 const char *mgx_log_name(const mgx_handle *h, int32_t col)
@@ -745,7 +791,7 @@ static int windows_plan(const mgx_handle *h, int32_t ahead, int32_t K, const voi
     if (h->multi && (h->rolling || h->inplace || factorised(h->k.c)))
         return fail(MGX_ERR_UNSUPPORTED, "%s: with several modules of a kind per grid the window prefetch is offered for lock-step "
                                          "counters (mgx_reset, mgx_reset_windows) over [T, n, N] series", who);
-    if (h->k.c.load_noise_std || h->k.c.pv_noise_std || h->k.c.grid_noise_std)
+    if (noisy(h->k.c))
         return fail(MGX_ERR_UNSUPPORTED, "%s: forecast noise depends on (step, horizon index), windows cannot be shared", who);
     if (h->k.obs_state_only == 2)
         return fail(MGX_ERR_UNSUPPORTED, "%s: the handle writes compact state rows (MGX_OBS_ROWS_STATE_COMPACT): the windows are "
@@ -830,16 +876,14 @@ static int launch_windows(mgx_handle *h, int32_t ahead, int32_t K, void *ring, h
         } else {
             MGX_DISPATCH_F(h->flags, (launch_windows_multi_kernel<F, double>(h->k, plan, t, ring, blocks, lds, st)));
         }
-        hipError_t em = hipGetLastError();
-        return em == hipSuccess ? MGX_OK : hip_fail(em, "obs_windows_k_multi_kernel launch");
+        return launched("obs_windows_k_multi_kernel launch");
     }
     if (h->k.obs_f32) {
         MGX_DISPATCH_F(h->flags, (launch_windows_kernel<F, float>(h->k, plan, t, ring, blocks, lds, st)));
     } else {
         MGX_DISPATCH_F(h->flags, (launch_windows_kernel<F, double>(h->k, plan, t, ring, blocks, lds, st)));
     }
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? MGX_OK : hip_fail(e, "obs_windows_k_kernel launch");
+    return launched("obs_windows_k_kernel launch");
 }
 
 int mgx_patch_windows(mgx_handle *h, const uint8_t *mask, int32_t K, void *ring, int32_t first_block, int32_t ahead,
@@ -866,8 +910,7 @@ int mgx_patch_windows(mgx_handle *h, const uint8_t *mask, int32_t K, void *ring,
         if (h->k.obs_f32) patch_windows_kernel<false, float><<<blocks, 64, lds, st>>>(h->k, mask, h->t + ahead, K, first_block, h->ring_pitch, (float *)ring, restarted);
         else patch_windows_kernel<false, double><<<blocks, 64, lds, st>>>(h->k, mask, h->t + ahead, K, first_block, h->ring_pitch, (double *)ring, restarted);
     }
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? MGX_OK : hip_fail(e, "patch_windows_kernel launch");
+    return launched("patch_windows_kernel launch");
 }
 
 int mgx_set_ring_pitch(mgx_handle *h, int32_t rows)
@@ -976,8 +1019,7 @@ int mgx_observe(mgx_handle *h, void *obs, mgx_stream stream)
     if (!h || !obs) return fail(MGX_ERR_INVALID, "mgx_observe: NULL argument");
     if (int rc = need_obs_bounds(h, "mgx_observe")) return rc;
     if (int rc = launch_observe(h, t_arg(h), obs, (hipStream_t)stream)) return rc;
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? MGX_OK : hip_fail(e, "observe launch");
+    return launched("observe launch");
 }
 
 int mgx_set_window(mgx_handle *h, int32_t initial_step, int32_t final_step)
@@ -1048,6 +1090,15 @@ static void leave_inplace(mgx_handle *h)
     }
 }
 
+// the full series and their window, remembered by a handle about to step per-grid windows (one that already does holds them)
+static void remember_full_series(mgx_handle *h)
+{
+    if (h->windowed) return;
+    h->full_load_ts = h->k.c.load_ts; h->full_pv_ts = h->k.c.pv_ts; h->full_grid_ts = h->k.c.grid_ts;
+    h->full_T = h->k.T; h->full_final = h->layout.final_step; h->full_initial = h->layout.initial_step;
+    h->full_window_lo = h->window_lo; h->full_window_hi = h->window_hi;
+}
+
 // back to the full series after a per-grid-window episode
 static void leave_windows(mgx_handle *h)
 {
@@ -1087,11 +1138,7 @@ int mgx_reset_windows(mgx_handle *h, const int32_t *start, const int32_t *length
     if (length && !final_rel) return fail(MGX_ERR_INVALID, "mgx_reset_windows: per-grid lengths need the final_rel buffer");
     if (h->k.t_dev) return fail(MGX_ERR_UNSUPPORTED, "mgx_reset_windows: not offered in device-counter mode");
     if (h->n_shards > 1) return fail(MGX_ERR_UNSUPPORTED, "mgx_reset_windows: not offered while the handle steps in shards");
-    if (!h->windowed) {
-        h->full_load_ts = h->k.c.load_ts; h->full_pv_ts = h->k.c.pv_ts; h->full_grid_ts = h->k.c.grid_ts;
-        h->full_T = h->k.T; h->full_final = h->layout.final_step; h->full_initial = h->layout.initial_step;
-        h->full_window_lo = h->window_lo; h->full_window_hi = h->window_hi;
-    }
+    remember_full_series(h);
     if (max_length < 1 || max_length > h->full_window_hi - h->full_window_lo)
         return fail(MGX_ERR_INVALID, "Cannot create a trajectory of length %d between initial_step (%d) and final_step (%d)",
                     max_length, h->full_window_lo, h->full_window_hi);
@@ -1112,8 +1159,7 @@ int mgx_reset_windows(mgx_handle *h, const int32_t *start, const int32_t *length
         gather_windows_multi_kernel<<<blocks_for(h->k.N), BLOCK, 0, st>>>(g, h->k.n_load, h->k.n_pv, h->layout.has_grid ? h->k.n_grid : 0);
     else
         gather_windows_kernel<<<blocks_for(h->k.N), BLOCK, 0, st>>>(g);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "gather_windows_kernel launch");
+    if (int rc = launched("gather_windows_kernel launch")) return rc;
     h->rolling = false; h->k.row_mask = -1;
     leave_inplace(h);
     h->k.c.base_load = nullptr;                          // the episode steps over the (materialised) window buffers
@@ -1152,11 +1198,7 @@ int mgx_reset_windows_rolling(mgx_handle *h, const int32_t *start, const int32_t
     if (h->layout.has_grid && !grid_w) return fail(MGX_ERR_INVALID, "mgx_reset_windows_rolling: grid_w is NULL but the layout has a GridModule");
     if (h->k.t_dev) return fail(MGX_ERR_UNSUPPORTED, "mgx_reset_windows_rolling: not offered in device-counter mode");
     if (h->n_shards > 1) return fail(MGX_ERR_UNSUPPORTED, "mgx_reset_windows_rolling: not offered while the handle steps in shards");
-    if (!h->windowed) {
-        h->full_load_ts = h->k.c.load_ts; h->full_pv_ts = h->k.c.pv_ts; h->full_grid_ts = h->k.c.grid_ts;
-        h->full_T = h->k.T; h->full_final = h->layout.final_step; h->full_initial = h->layout.initial_step;
-        h->full_window_lo = h->window_lo; h->full_window_hi = h->window_hi;
-    }
+    remember_full_series(h);
     if (max_length < 1 || max_length > h->full_window_hi - h->full_window_lo)
         return fail(MGX_ERR_INVALID, "Cannot create a trajectory of length %d between initial_step (%d) and final_step (%d)",
                     max_length, h->full_window_lo, h->full_window_hi);
@@ -1172,8 +1214,7 @@ int mgx_reset_windows_rolling(mgx_handle *h, const int32_t *start, const int32_t
     g.start = start; g.length = length; g.mask = nullptr; g.row0 = 0;
     hipStream_t st = (hipStream_t)stream;
     gather_windows_kernel<<<blocks_for(h->k.N), BLOCK, 0, st>>>(g);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "gather_windows_kernel launch");
+    if (int rc = launched("gather_windows_kernel launch")) return rc;
     h->k.c.base_load = nullptr;                          // the episodes step over the (materialised) window rings
     h->k.c.load_ts = load_w; h->k.c.pv_ts = pv_w; if (h->layout.has_grid) h->k.c.grid_ts = grid_w;
     h->k.T = INT32_MAX / 2; h->k.final_step = INT32_MAX / 2; h->k.grid_final = final_abs;
@@ -1205,9 +1246,7 @@ int mgx_reset_episodes(mgx_handle *h, const int32_t *start, const int32_t *lengt
     }
     if (h->prefetch_pending) { if (int rc = mgx_prefetch_wait(h, stream)) return rc; }
     leave_windows(h);                                   // back to the full (factorised) series, whatever mode the handle was in
-    h->full_load_ts = h->k.c.load_ts; h->full_pv_ts = h->k.c.pv_ts; h->full_grid_ts = h->k.c.grid_ts;
-    h->full_T = h->k.T; h->full_final = h->layout.final_step; h->full_initial = h->layout.initial_step;
-    h->full_window_lo = h->window_lo; h->full_window_hi = h->window_hi;
+    remember_full_series(h);
     // Factorised series: profile-major copies of the base tables (1.7 MB for a year of hourly rows) -- in this mode every lane reads
     // its own row.  [T, N] arrays are read where they lie: a lane takes 8 bytes of its own row's line (a gather, 64 lines per wave
     // and component instead of 4; still no window buffers to copy and restart into).
@@ -1228,8 +1267,7 @@ int mgx_reset_episodes(mgx_handle *h, const int32_t *start, const int32_t *lengt
         profile_major_kernel<<<blocks, BLOCK, 0, (hipStream_t)stream>>>(h->full_c.base_load, h->pm_tables, h->full_T, pitch);
         profile_major_kernel<<<blocks, BLOCK, 0, (hipStream_t)stream>>>(h->full_c.base_pv, h->pm_tables + one, h->full_T, pitch);
         if (co2) profile_major_kernel<<<blocks, BLOCK, 0, (hipStream_t)stream>>>(h->full_c.base_co2, h->pm_tables + 2 * one, h->full_T, pitch);
-        e = hipGetLastError();
-        if (e != hipSuccess) return hip_fail(e, "profile_major_kernel launch");
+        if (int rc = launched("profile_major_kernel launch")) return rc;
         h->k.c.base_load = h->pm_tables; h->k.c.base_pv = h->pm_tables + one;
         if (co2) h->k.c.base_co2 = h->pm_tables + 2 * one;
         h->k.pm_pitch = pitch;
@@ -1254,8 +1292,7 @@ int mgx_reset_episodes(mgx_handle *h, const int32_t *start, const int32_t *lengt
             grid_major_kernel<<<tiles, 256, 0, s>>>(h->full_pv_ts, h->gm_tables, N, h->full_T, 1, pitch, ncomp, 1);
             if (h->layout.has_grid)
                 grid_major_kernel<<<dim3(tiles.x, tiles.y, 4), 256, 0, s>>>(h->full_grid_ts, h->gm_tables, N, h->full_T, 4, pitch, ncomp, 2);
-            hipError_t e = hipGetLastError();
-            if (e != hipSuccess) return hip_fail(e, "grid_major_kernel launch");
+            if (int rc = launched("grid_major_kernel launch")) return rc;
             h->k.c.load_ts = h->gm_tables; h->k.c.pv_ts = h->gm_tables + 1;
             if (h->layout.has_grid) h->k.c.grid_ts = h->gm_tables + 2;
             h->k.pm_pitch = pitch;
@@ -1334,8 +1371,7 @@ int mgx_reset_grids_random(mgx_handle *h, const uint8_t *mask, uint64_t seed, in
     g.start = nullptr; g.length = nullptr; g.mask = mask; g.row0 = h->t;
     g.draw = 1; g.fixed_length = fixed_length; g.seed = seed; g.start_io = start_io; g.length_io = length_io; g.t0_io = t0_io;
     gather_windows_kernel<<<blocks_for(h->k.N), BLOCK, 0, (hipStream_t)stream>>>(g);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? MGX_OK : hip_fail(e, "gather_windows_kernel launch");
+    return launched("gather_windows_kernel launch");
 }
 
 int mgx_reset_grids(mgx_handle *h, const uint8_t *mask, const int32_t *start, const int32_t *length, mgx_stream stream)
@@ -1350,8 +1386,7 @@ int mgx_reset_grids(mgx_handle *h, const uint8_t *mask, const int32_t *start, co
     rolling_gather_args(h, &g);
     g.start = start; g.length = length; g.mask = mask; g.row0 = h->t;
     gather_windows_kernel<<<blocks_for(h->k.N), BLOCK, 0, (hipStream_t)stream>>>(g);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? MGX_OK : hip_fail(e, "gather_windows_kernel launch");
+    return launched("gather_windows_kernel launch");
 }
 
 // ---- shards -------------------------------------------------------------------------------------------------
@@ -1435,7 +1470,7 @@ static int episode_step_begin(mgx_handle *h, const uint8_t *done, void *obs, voi
     const bool rows_behind = obs && !obs_inline;
     if (ep->k.final_obs && !obs)
         return fail(MGX_ERR_INVALID, "%s: mgx_set_final_obs is set but the step writes no observation", who);
-    if (ep->k.obs_state_only == 1) ep->k.final_obs = nullptr;    // rings: mgx_patch_windows saves the rows of the restarted grids
+    drop_ring_final_obs(ep->k);
     if (rows_behind && ep->k.final_obs) {
         if (ep->k.ar_mode && !done)
             return fail(MGX_ERR_INVALID, "%s: with a forecast horizon the observation before an automatic restart needs the `done` flags", who);
@@ -1475,8 +1510,7 @@ static int step_once(mgx_handle *h, const void *actions, int normalized, double 
                      hipStream_t st)
 {
     if (h->multi) {
-        // noisy forecasters: the rows come from observe_multi_kernel behind the step (the step kernel carries no noise code)
-        const bool rows_behind = obs && !h->k.obs_state_only && (h->k.c.load_noise_std || h->k.c.pv_noise_std || h->k.c.grid_noise_std);
+        const bool rows_behind = rows_need_noise_pass(h, obs);
         void *obs_rows = obs;
         if (rows_behind) {
             if (h->n_shards > 1) return fail(MGX_ERR_UNSUPPORTED, "mgx_step: noisy observation rows are not written per shard");
@@ -1492,44 +1526,33 @@ static int step_once(mgx_handle *h, const void *actions, int normalized, double 
             }
         });
         if (rows_behind) { if (int rc = launch_observe(h, dev_counter(h) ? 0 : h->t + 1, obs_rows, st)) return rc; }
-        hipError_t em = launch_error();
-        if (em != hipSuccess) return hip_fail(em, "step_multi_kernel launch");
-        advance(h, 1, st);
-        return MGX_OK;
+        return finish_step(h, 1, st, launch_error(), "step_multi_kernel launch");
     }
-    void *obs_inline = (obs && (h->k.H == 0 || h->k.obs_state_only)) ? obs : nullptr;
+    void *obs_inline = rows_inline(h, obs);
     if (h->inplace) {                                     // in-place episodes: the EP form of the kernel (no shards in this mode)
         EpisodeStep ep;
         if (int rc = episode_step_begin(h, done, obs, obs_inline, &ep, "mgx_step")) return rc;
         MGX_DISPATCH_F(h->flags, (step_kernel<F, true><<<blocks_for(ep.k.N), BLOCK, row_tile_lds(ep.k, obs_inline), st>>>(ep.k, actions, h->t, normalized, reward, done,
                                                                                        obs_inline, log)));
         if (int rc = episode_step_end(h, ep, done, obs, obs_inline, st)) return rc;
-        hipError_t ee = hipGetLastError();
-        if (ee != hipSuccess) return hip_fail(ee, "step_kernel launch");
-        advance(h, 1, st);
-        return MGX_OK;
+        return finish_step(h, 1, st, hipGetLastError(), "step_kernel launch");
     }
     for_each_shard_threaded(h, st, [&](const KArgs &k, hipStream_t s) {
         MGX_DISPATCH_F(h->flags, (step_kernel<F><<<blocks_for(k.g1 - k.g0), BLOCK, row_tile_lds(k, obs_inline), s>>>(k, actions, t_arg(h), normalized, reward,
                                                                                        done, obs_inline, log)));
     });
     if (obs && !obs_inline) { if (int rc = launch_observe(h, dev_counter(h) ? 0 : h->t + 1, obs, st)) return rc; }
-    hipError_t e = launch_error();
-    if (e != hipSuccess) return hip_fail(e, "step_kernel launch");
-    advance(h, 1, st);
-    return MGX_OK;
+    return finish_step(h, 1, st, launch_error(), "step_kernel launch");
 }
 
 static int check_step_args(const mgx_handle *h, const void *actions, const double *reward, const void *obs, int32_t K, const char *who)
 {
     if (!h || !reward || (h->action_dim > 0 && !actions)) return fail(MGX_ERR_INVALID, "%s: NULL argument", who);
     if (K <= 0) return fail(MGX_ERR_INVALID, "%s: K must be positive", who);
-    if (!dev_counter(h) && (h->t < 0 || (int64_t)h->t + K > step_limit(h)))
-        return K == 1 ? fail(MGX_ERR_RANGE, "%s: step %d is outside the time series (length %d)", who, h->t, step_limit(h))
-                      : fail(MGX_ERR_RANGE, "%s: steps [%d, %d) leave the time series (length %d)", who, h->t, h->t + K, step_limit(h));
+    if (int rc = check_rows(h, K, who, K != 1)) return rc;
     if (obs) {
         if (int rc = need_obs_bounds(h, who)) return rc;
-        if (h->n_shards > 1 && !h->multi && h->k.H > 0 && !h->k.obs_state_only)
+        if (h->n_shards > 1 && !h->multi && !rows_inline(h, (void *)obs))
             return fail(MGX_ERR_UNSUPPORTED, "%s: observation rows with a forecast horizon are not written per shard; "
                                              "mgx_join, mgx_observe on your stream, mgx_fork", who);
     }
@@ -1548,8 +1571,7 @@ int mgx_check_step(mgx_handle *h, const void *actions, int normalized, uint32_t 
 {
     g_err[0] = 0;
     if (!h || !violations || (h->action_dim > 0 && !actions)) return fail(MGX_ERR_INVALID, "mgx_check_step: NULL argument");
-    if (!dev_counter(h) && (h->t < 0 || h->t >= step_limit(h)))
-        return fail(MGX_ERR_RANGE, "mgx_check_step: step %d is outside the time series (length %d)", h->t, step_limit(h));
+    if (int rc = check_rows(h, 1, "mgx_check_step", false)) return rc;
     for_each_shard(h, (hipStream_t)stream, [&](const KArgs &k, hipStream_t s) {
         if (h->multi) {
             MGX_DISPATCH_F(h->flags, (check_multi_kernel<F><<<multi_blocks(k.g1 - k.g0), BLOCK_MULTI, 0, s>>>(k, actions, t_arg(h), normalized, violations)));
@@ -1557,20 +1579,17 @@ int mgx_check_step(mgx_handle *h, const void *actions, int normalized, uint32_t 
             MGX_DISPATCH_F(h->flags, (check_kernel<F><<<blocks_for(k.g1 - k.g0), BLOCK, 0, s>>>(k, actions, t_arg(h), normalized, violations)));
         }
     });
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? MGX_OK : hip_fail(e, "check_kernel launch");
+    return launched("check_kernel launch");
 }
 
 int mgx_action_bounds(mgx_handle *h, double *lo, double *hi, mgx_stream stream)
 {
     g_err[0] = 0;
     if (!h || !lo || !hi) return fail(MGX_ERR_INVALID, "mgx_action_bounds: NULL argument");
-    if (!dev_counter(h) && (h->t < 0 || h->t >= step_limit(h)))
-        return fail(MGX_ERR_RANGE, "mgx_action_bounds: step %d is outside the time series (length %d)", h->t, step_limit(h));
+    if (int rc = check_rows(h, 1, "mgx_action_bounds", false)) return rc;
     KArgs k = h->k; k.g0 = 0; k.g1 = k.N;
     MGX_DISPATCH_F(h->flags, (action_bounds_kernel<F><<<multi_blocks(k.N), BLOCK_MULTI, 0, (hipStream_t)stream>>>(k, t_arg(h), lo, hi)));
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? MGX_OK : hip_fail(e, "action_bounds_kernel launch");
+    return launched("action_bounds_kernel launch");
 }
 
 int mgx_step_many(mgx_handle *h, const void *actions, int32_t K, int normalized, double *reward, uint8_t *done, void *obs,
@@ -1581,7 +1600,7 @@ int mgx_step_many(mgx_handle *h, const void *actions, int32_t K, int normalized,
     const int64_t N = h->k.N;
     const size_t act_row = (size_t)N * h->action_dim * (h->k.act_f32 ? sizeof(float) : sizeof(double));
     const size_t obs_row = (size_t)N * h->k.obs_dim * (h->k.obs_f32 ? sizeof(float) : sizeof(double));
-    void *obs_inline = (obs && (h->k.H == 0 || h->k.obs_state_only)) ? obs : nullptr;
+    void *obs_inline = rows_inline(h, obs);
     if (h->n_shards > 1 && h->launch_threads && !h->multi && !h->inplace && (!obs || obs_inline)) {
         // every shard's K dependent launches are issued back to back by a thread of their own: no hand-over between the steps
         const int32_t t0 = t_arg(h);
@@ -1593,10 +1612,7 @@ int mgx_step_many(mgx_handle *h, const void *actions, int32_t K, int normalized,
                                               log ? log + (int64_t)k * h->k.log_dim * N : nullptr)));
             }
         }, 1);
-        hipError_t e = launch_error();
-        if (e != hipSuccess) return hip_fail(e, "step_kernel launch");
-        advance(h, K, (hipStream_t)stream);
-        return MGX_OK;
+        return finish_step(h, K, (hipStream_t)stream, launch_error(), "step_kernel launch");
     }
     for (int32_t k = 0; k < K; k++) {
         if (int rc = step_once(h, actions ? (const char *)actions + k * act_row : nullptr, normalized, reward + k * N,
@@ -1614,8 +1630,7 @@ int mgx_step_k(mgx_handle *h, const void *actions, int32_t K, int normalized, do
     if (!h || (h->action_dim > 0 && !actions)) return fail(MGX_ERR_INVALID, "mgx_step_k: NULL argument");
     if (K <= 0) return fail(MGX_ERR_INVALID, "mgx_step_k: K must be positive");
     if (h->rolling) return fail(MGX_ERR_UNSUPPORTED, "mgx_step_k: rolling windows take single steps (grids restart between steps)");
-    if (!dev_counter(h) && (h->t < 0 || (int64_t)h->t + K > step_limit(h)))
-        return fail(MGX_ERR_RANGE, "mgx_step_k: steps [%d, %d) leave the time series (length %d)", h->t, h->t + K, step_limit(h));
+    if (int rc = check_rows(h, K, "mgx_step_k", true)) return rc;
     hipStream_t st = (hipStream_t)stream;
     const FusedOut fo{reward, done, soc_trace, status_trace, ret_acc, log};
     if (h->multi) {                                       // general path: the K-step loop around the general step
@@ -1637,26 +1652,14 @@ int mgx_step_k(mgx_handle *h, const void *actions, int32_t K, int normalized, do
                                               k, actions, nullptr, 0, 0, nullptr, 0, t_arg(h), K, normalized, fo, h->multi_small)));
             }
         });
-        hipError_t em = hipGetLastError();
-        if (em != hipSuccess) return hip_fail(em, "step_k_multi_kernel launch");
-        advance(h, K, st);
-        return MGX_OK;
+        return finish_step(h, K, st, hipGetLastError(), "step_k_multi_kernel launch");
     }
-    const bool fact = factorised(h->k.c);
     for_each_shard(h, st, [&](const KArgs &k, hipStream_t s) {
-        FusedLaunch L;
-        L.flags = h->flags; L.act_f32 = k.act_f32 != 0; L.rich = log != nullptr || status_trace != nullptr; L.fact = fact;
-        L.per_step = false;
-        L.gpb = fused_grids_per_block(h, k.g1 - k.g0);
-        L.blocks = (unsigned)((k.g1 - k.g0 + L.gpb - 1) / L.gpb);
-        L.stream = s; L.k = &k; L.actions = actions; L.tab = nullptr; L.ids = nullptr;
-        L.t = t_arg(h); L.K = K; L.normalized = normalized; L.out = fo;
+        FusedLaunch L = fused_launch_for(h, k, s, fo, K);
+        L.actions = actions; L.act_f32 = k.act_f32 != 0; L.normalized = normalized;
         (void)(launch_step_k_p0(L) || launch_step_k_p1(L) || launch_step_k_p2(L) || launch_step_k_p3(L) || launch_step_k_p4(L));
     });
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "step_k_kernel launch");
-    advance(h, K, st);
-    return MGX_OK;
+    return finish_step(h, K, st, hipGetLastError(), "step_k_kernel launch");
 }
 
 static int encode_table(const mgx_handle *h, const int32_t *table, int32_t n_actions, PLWords *tab, const char *who)
@@ -1689,8 +1692,7 @@ static int launch_expand_lists(mgx_handle *h, const int32_t *action_id, const in
                                                                                                        action_id, t_arg(h), control,
                                                                                                        violations)));
     });
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? MGX_OK : hip_fail(e, "expand_multi_kernel launch");
+    return launched("expand_multi_kernel launch");
 }
 
 int mgx_expand_discrete(mgx_handle *h, const int32_t *action_id, const int32_t *table, int32_t n_actions,
@@ -1698,8 +1700,7 @@ int mgx_expand_discrete(mgx_handle *h, const int32_t *action_id, const int32_t *
 {
     g_err[0] = 0;
     if (!h || !action_id || !table || !control) return fail(MGX_ERR_INVALID, "mgx_expand_discrete: NULL argument");
-    if (!dev_counter(h) && (h->t < 0 || h->t >= step_limit(h)))
-        return fail(MGX_ERR_RANGE, "mgx_expand_discrete: step %d is outside the time series (length %d)", h->t, step_limit(h));
+    if (int rc = check_rows(h, 1, "mgx_expand_discrete", false)) return rc;
     PLWords tab;
     if (int rc = encode_table(h, table, n_actions, &tab, "mgx_expand_discrete")) return rc;
     hipStream_t st = (hipStream_t)stream;
@@ -1727,8 +1728,7 @@ int mgx_expand_discrete(mgx_handle *h, const int32_t *action_id, const int32_t *
     for_each_shard(h, st, [&](const KArgs &k, hipStream_t s) {
         MGX_DISPATCH_F(h->flags, (expand_kernel<F><<<blocks_for(k.g1 - k.g0), BLOCK, 0, s>>>(k, tab, action_id, t_arg(h), control, violations)));
     });
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? MGX_OK : hip_fail(e, "expand_kernel launch");
+    return launched("expand_kernel launch");
 }
 
 int mgx_expand_lists(mgx_handle *h, const int32_t *action_id, const int32_t *lists, int32_t n_lists, int32_t list_len,
@@ -1736,10 +1736,8 @@ int mgx_expand_lists(mgx_handle *h, const int32_t *action_id, const int32_t *lis
 {
     g_err[0] = 0;
     if (!h || !action_id || !lists || !control) return fail(MGX_ERR_INVALID, "mgx_expand_lists: NULL argument");
-    if (n_lists <= 0 || list_len <= 0 || list_len > 3 * MGX_MAX_INSTANCES)
-        return fail(MGX_ERR_INVALID, "mgx_expand_lists: need n_lists > 0 and list_len in [1, %d]", 3 * MGX_MAX_INSTANCES);
-    if (!dev_counter(h) && (h->t < 0 || h->t >= step_limit(h)))
-        return fail(MGX_ERR_RANGE, "mgx_expand_lists: step %d is outside the time series (length %d)", h->t, step_limit(h));
+    if (int rc = check_lists(n_lists, list_len, "mgx_expand_lists")) return rc;
+    if (int rc = check_rows(h, 1, "mgx_expand_lists", false)) return rc;
     return launch_expand_lists(h, action_id, lists, n_lists, list_len, control, violations, (hipStream_t)stream);
 }
 
@@ -1748,11 +1746,10 @@ int mgx_step_lists(mgx_handle *h, const int32_t *action_id, const int32_t *lists
 {
     g_err[0] = 0;
     if (!h || !action_id || !lists) return fail(MGX_ERR_INVALID, "mgx_step_lists: NULL argument");
-    if (n_lists <= 0 || list_len <= 0 || list_len > 3 * MGX_MAX_INSTANCES)
-        return fail(MGX_ERR_INVALID, "mgx_step_lists: need n_lists > 0 and list_len in [1, %d]", 3 * MGX_MAX_INSTANCES);
+    if (int rc = check_lists(n_lists, list_len, "mgx_step_lists")) return rc;
     if (int rc = check_step_args(h, action_id, reward, obs, 1, "mgx_step_lists")) return rc;
     hipStream_t st = (hipStream_t)stream;
-    const bool noisy_rows = obs && !h->k.obs_state_only && (h->k.c.load_noise_std || h->k.c.pv_noise_std || h->k.c.grid_noise_std);
+    const bool noisy_rows = rows_need_noise_pass(h, obs);
     // in-place episodes (mgx_reset_episodes) take the one launch too (the EP form: the grid's own rows, the auto-reset restarts in the
     // kernel); the gathered rolling window buffers (mgx_reset_windows_rolling) are single-instance and never get here
     const bool one_launch = h->multi && h->multi_small && (h->inplace || !h->rolling) && !noisy_rows &&
@@ -1771,10 +1768,7 @@ int mgx_step_lists(mgx_handle *h, const int32_t *action_id, const int32_t *lists
                                           k, action_id, lists, n_lists, list_len, t_arg(h), control, reward, done, obs, log)));
         }
     });
-    hipError_t e = launch_error();
-    if (e != hipSuccess) return hip_fail(e, "step_lists_small_kernel launch");
-    advance(h, 1, st);
-    return MGX_OK;
+    return finish_step(h, 1, st, launch_error(), "step_lists_small_kernel launch");
 }
 
 int mgx_check_discrete(mgx_handle *h, const int32_t *action_id, const int32_t *table, int32_t n_actions, uint32_t *violations,
@@ -1784,15 +1778,13 @@ int mgx_check_discrete(mgx_handle *h, const int32_t *action_id, const int32_t *t
     if (!h || !action_id || !table || !violations) return fail(MGX_ERR_INVALID, "mgx_check_discrete: NULL argument");
     if (h->multi) return fail(MGX_ERR_UNSUPPORTED, "mgx_check_discrete: needs exactly one module of every kind per grid; use "
                                                     "mgx_expand_discrete / mgx_expand_lists with `violations`, then mgx_check_step");
-    if (!dev_counter(h) && (h->t < 0 || h->t >= step_limit(h)))
-        return fail(MGX_ERR_RANGE, "mgx_check_discrete: step %d is outside the time series (length %d)", h->t, step_limit(h));
+    if (int rc = check_rows(h, 1, "mgx_check_discrete", false)) return rc;
     PLWords tab;
     if (int rc = encode_table(h, table, n_actions, &tab, "mgx_check_discrete")) return rc;
     for_each_shard(h, (hipStream_t)stream, [&](const KArgs &k, hipStream_t s) {
         MGX_DISPATCH_F(h->flags, (check_discrete_kernel<F><<<blocks_for(k.g1 - k.g0), BLOCK, 0, s>>>(k, tab, action_id, t_arg(h), violations)));
     });
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? MGX_OK : hip_fail(e, "check_discrete_kernel launch");
+    return launched("check_discrete_kernel launch");
 }
 
 int mgx_step_discrete(mgx_handle *h, const int32_t *action_id, const int32_t *table, int32_t n_actions, double *control,
@@ -1806,27 +1798,21 @@ int mgx_step_discrete(mgx_handle *h, const int32_t *action_id, const int32_t *ta
     PLWords tab;
     if (int rc = encode_table(h, table, n_actions, &tab, "mgx_step_discrete")) return rc;
     hipStream_t st = (hipStream_t)stream;
-    void *obs_inline = (obs && (h->k.H == 0 || h->k.obs_state_only)) ? obs : nullptr;
+    void *obs_inline = rows_inline(h, obs);
     if (h->inplace) {
         EpisodeStep ep;
         if (int rc = episode_step_begin(h, done, obs, obs_inline, &ep, "mgx_step_discrete")) return rc;
         MGX_DISPATCH_F(h->flags, (step_discrete_kernel<F, true><<<blocks_for(ep.k.N), BLOCK, row_tile_lds(ep.k, obs_inline), st>>>(ep.k, tab, action_id, h->t, control, reward,
                                                                                                 done, obs_inline, log)));
         if (int rc = episode_step_end(h, ep, done, obs, obs_inline, st)) return rc;
-        hipError_t ee = hipGetLastError();
-        if (ee != hipSuccess) return hip_fail(ee, "step_discrete_kernel launch");
-        advance(h, 1, st);
-        return MGX_OK;
+        return finish_step(h, 1, st, hipGetLastError(), "step_discrete_kernel launch");
     }
     for_each_shard_threaded(h, st, [&](const KArgs &k, hipStream_t s) {
         MGX_DISPATCH_F(h->flags, (step_discrete_kernel<F><<<blocks_for(k.g1 - k.g0), BLOCK, row_tile_lds(k, obs_inline), s>>>(k, tab, action_id, t_arg(h), control,
                                                                                                 reward, done, obs_inline, log)));
     });
     if (obs && !obs_inline) { if (int rc = launch_observe(h, dev_counter(h) ? 0 : h->t + 1, obs, st)) return rc; }
-    hipError_t e = launch_error();
-    if (e != hipSuccess) return hip_fail(e, "step_discrete_kernel launch");
-    advance(h, 1, st);
-    return MGX_OK;
+    return finish_step(h, 1, st, launch_error(), "step_discrete_kernel launch");
 }
 
 // ---- the Gym step without per-step bookkeeping on the caller's side (mgx_env_*) ---------------------------------
@@ -1903,14 +1889,20 @@ inline EnvTarget env_target(const mgx_handle *h, const mgx_env_slot &sl)
     return EnvTarget{h->env_rings[(h->env_ring_idx + 1) % 3], true};
 }
 // after a successful step: the slot moves on, the env moves to the block it just completed
-inline int env_commit(mgx_handle *h, bool entered, mgx_stream stream)
+inline void env_advance(mgx_handle *h, bool entered)
 {
     h->env_next = h->env_next + 1 < h->env_n_slots ? h->env_next + 1 : 0;
-    if (h->env_ring_K <= 0) return MGX_OK;
-    if (!entered) { h->env_ring_pos += 1; return MGX_OK; }
+    if (h->env_ring_K <= 0) return;
+    if (!entered) { h->env_ring_pos += 1; return; }
     h->env_ring_idx = (h->env_ring_idx + 1) % 3;
     h->env_ring_pos = 0;
-    // the ring behind the one just entered: the windows of counter values t + K .. t + 2K - 1, written beside the next K steps
+}
+// ... and, a ring entered (a fleet step issues this refill itself, with the step: mgx_fleet_env_step), the ring behind it: the
+// windows of counter values t + K .. t + 2K - 1, written beside the next K steps
+inline int env_commit(mgx_handle *h, bool entered, mgx_stream stream)
+{
+    env_advance(h, entered);
+    if (!entered || h->env_ring_K <= 0) return MGX_OK;
     return observe_windows_ahead(h, h->env_ring_K, h->env_ring_K, h->env_rings[(h->env_ring_idx + 1) % 3], (hipStream_t)stream, nullptr, nullptr);
 }
 }  // namespace
@@ -1951,27 +1943,17 @@ int mgx_rollout_discrete(mgx_handle *h, const uint8_t *action_id, int per_step, 
     if (h->rolling) return fail(MGX_ERR_UNSUPPORTED, "mgx_rollout_discrete: rolling windows take single steps");
     if (h->multi) return fail(MGX_ERR_UNSUPPORTED, "mgx_rollout_discrete: needs exactly one module of every kind "
                                                     "per grid; use mgx_expand_discrete / mgx_expand_lists + mgx_step");
-    if (!dev_counter(h) && (h->t < 0 || (int64_t)h->t + K > step_limit(h)))
-        return fail(MGX_ERR_RANGE, "mgx_rollout_discrete: steps [%d, %d) leave the time series (length %d)", h->t, h->t + K, step_limit(h));
+    if (int rc = check_rows(h, K, "mgx_rollout_discrete", true)) return rc;
     PLWords tab;
     if (int rc = encode_table(h, table, n_actions, &tab, "mgx_rollout_discrete")) return rc;
     const FusedOut fo{reward, done, soc_trace, status_trace, ret_acc, log};
     hipStream_t st = (hipStream_t)stream;
-    const bool fact = factorised(h->k.c);
     for_each_shard(h, st, [&](const KArgs &k, hipStream_t s) {
-        FusedLaunch L;
-        L.flags = h->flags; L.act_f32 = false; L.rich = log != nullptr || status_trace != nullptr; L.fact = fact;
-        L.per_step = per_step != 0;
-        L.gpb = fused_grids_per_block(h, k.g1 - k.g0);
-        L.blocks = (unsigned)((k.g1 - k.g0 + L.gpb - 1) / L.gpb);
-        L.stream = s; L.k = &k; L.actions = nullptr; L.tab = &tab; L.ids = action_id;
-        L.t = t_arg(h); L.K = K; L.normalized = 0; L.out = fo;
+        FusedLaunch L = fused_launch_for(h, k, s, fo, K);
+        L.tab = &tab; L.ids = action_id; L.per_step = per_step != 0;
         (void)(launch_rollout_p0(L) || launch_rollout_p1(L) || launch_rollout_p2(L) || launch_rollout_p3(L) || launch_rollout_p4(L));
     });
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "rollout_kernel launch");
-    advance(h, K, st);
-    return MGX_OK;
+    return finish_step(h, K, st, hipGetLastError(), "rollout_kernel launch");
 }
 
 // What the fused launches over in-place episodes refuse, the plain calls and the ones with rows alike (`fn`: the call, for the message)
@@ -2041,10 +2023,7 @@ static int prepare_episode_launch(mgx_handle *h, int32_t K, double *reward, uint
 static int finish_episode_launch(mgx_handle *h, const EpisodeLaunch &L, bool launched, const char *what, const char *fn)
 {
     if (!launched) return fail(MGX_ERR_UNSUPPORTED, "%s: no kernel for layout flags %d", fn, h->flags);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, what);
-    advance(h, L.K, L.stream);
-    return MGX_OK;
+    return finish_step(h, L.K, L.stream, hipGetLastError(), what);
 }
 
 // The roll-out over in-place episodes: one launch of rollout_episodes_kernel (mgx_episodes.hip) or -- rows != NULL -- of
@@ -2127,14 +2106,12 @@ int mgx_rollout_lists(mgx_handle *h, const int32_t *action_id, int per_step, con
     g_err[0] = 0;
     if (!h || !action_id || !lists) return fail(MGX_ERR_INVALID, "mgx_rollout_lists: NULL argument");
     if (K <= 0) return fail(MGX_ERR_INVALID, "mgx_rollout_lists: K must be positive");
-    if (n_lists <= 0 || list_len <= 0 || list_len > 3 * MGX_MAX_INSTANCES)
-        return fail(MGX_ERR_INVALID, "mgx_rollout_lists: need n_lists > 0 and list_len in [1, %d]", 3 * MGX_MAX_INSTANCES);
+    if (int rc = check_lists(n_lists, list_len, "mgx_rollout_lists")) return rc;
     if (h->rolling) return fail(MGX_ERR_UNSUPPORTED, "mgx_rollout_lists: rolling windows take single steps");
     if (factorised(h->k.c)) return fail(MGX_ERR_UNSUPPORTED, "mgx_rollout_lists: the general kernels read materialised series; "
                                                              "use mgx_rollout_discrete on a factorised batch");
     if (h->k.done_bits && done) return fail(MGX_ERR_UNSUPPORTED, "mgx_rollout_lists: the general kernels write `done` as bytes");
-    if (!dev_counter(h) && (h->t < 0 || (int64_t)h->t + K > step_limit(h)))
-        return fail(MGX_ERR_RANGE, "mgx_rollout_lists: steps [%d, %d) leave the time series (length %d)", h->t, h->t + K, step_limit(h));
+    if (int rc = check_rows(h, K, "mgx_rollout_lists", true)) return rc;
     hipStream_t st = (hipStream_t)stream;
     const FusedOut fo{reward, done, soc_trace, status_trace, ret_acc, log};
     const bool static_counts = tune(MGX_TUNE_MULTI_STATIC) != 0 && tune(MGX_TUNE_MULTI_SMALL_OWN) != 0;
@@ -2152,20 +2129,29 @@ int mgx_rollout_lists(mgx_handle *h, const int32_t *action_id, int per_step, con
         MGX_DISPATCH_F(h->flags, (step_k_multi_kernel<F><<<multi_blocks(k.g1 - k.g0), BLOCK_MULTI, h->multi_lds, s>>>(
                                       k, nullptr, lists, n_lists, list_len, action_id, per_step, t_arg(h), K, 0, fo, h->multi_small)));
     });
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "step_k_multi_kernel launch");
-    advance(h, K, st);
-    return MGX_OK;
+    return finish_step(h, K, st, hipGetLastError(), "step_k_multi_kernel launch");
 }
 
 // ---- fleets: several batches (one per layout) stepped by ONE call ---------------------------------------------------
-int mgx_fleet_step(const mgx_fleet_item *items, int32_t n, int normalized, mgx_stream stream)
+// One launch for all batches (continuous and discrete items alike) that can share it; an item that needs kernels of its own
+// (several modules of a kind, rolling windows, a device counter, shards, per-step rows with a horizon) is stepped beside it --
+// the others still share their launch.  Items stepping in-place per-grid episodes (mgx_reset_episodes) with one module of every
+// kind and rows written inline (none, H = 0 rows, or the state columns of a ring block) share a launch of their own: the episode
+// form fleet_step_kernel_v<true> (MGX_TUNE_FLEET_EPISODES = 0: they are stepped beside, one step_kernel<F, true> /
+// step_discrete_kernel<F, true> each).  The phases of mgx_fleet_step stand here in the order they run.
+struct FleetStep {
+    const mgx_fleet_item *items; int32_t n; int normalized; hipStream_t st;    // the call's arguments
+    bool fuse[64], epf[64];       // item j rides in the shared launch / in the episode-form launch
+    int32_t fz[64], nf;           // the items that share the launch, in item order
+    int32_t ez[64], ne;           // the in-place items that share the episode-form launch, in item order
+    bool chunk_done[64];          // window chunks that rode along with the step launch
+};
+
+// all checks first: a fleet step is all or nothing
+static int fleet_check_items(const FleetStep &S)
 {
-    g_err[0] = 0;
-    if (!items || n <= 0) return fail(MGX_ERR_INVALID, "mgx_fleet_step: no items");
-    hipStream_t st = (hipStream_t)stream;
-    for (int32_t j = 0; j < n; j++) {                       // all checks first: a fleet step is all or nothing
-        const mgx_fleet_item &it = items[j];
+    for (int32_t j = 0; j < S.n; j++) {
+        const mgx_fleet_item &it = S.items[j];
         if (it.struct_size != (int32_t)sizeof(mgx_fleet_item))
             return fail(MGX_ERR_INVALID, "mgx_fleet_step: item %d struct_size %d vs %zu", j, it.struct_size, sizeof(mgx_fleet_item));
         if (!it.handle) return fail(MGX_ERR_INVALID, "mgx_fleet_step: item %d has no handle", j);
@@ -2180,199 +2166,223 @@ int mgx_fleet_step(const mgx_fleet_item *items, int32_t n, int normalized, mgx_s
             if (int rc = windows_plan(it.handle, it.refill_ahead, it.refill_K, it.refill_ring, "mgx_fleet_step", &plan, &lds, &ng)) return rc;
         }
     }
-    // One launch for all batches (continuous and discrete items alike) that can share it; an item that needs kernels of its own
-    // (several modules of a kind, rolling windows, a device counter, shards, per-step rows with a horizon) is stepped beside it --
-    // the others still share their launch (round 6: one such bucket used to send EVERY bucket of the fleet to its own launch).
-    // Items stepping in-place per-grid episodes (mgx_reset_episodes) with one module of every kind and rows written inline (none,
-    // H = 0 rows, or the state columns of a ring block) share a launch of their own: the episode form fleet_step_kernel_v<true>
-    // (MGX_TUNE_FLEET_EPISODES = 0: they are stepped beside, one step_kernel<F, true> / step_discrete_kernel<F, true> each).
-    if (n > 64) return fail(MGX_ERR_INVALID, "mgx_fleet_step: at most 64 items per call");
-    bool fuse[64], epf[64];
-    int32_t fz[64], nf = 0;                                 // the items that share the launch, in item order
-    int32_t ez[64], ne = 0;                                 // the in-place items that share the episode-form launch, in item order
+    return MGX_OK;
+}
+
+// which launch steps which item
+static int fleet_classify(FleetStep &S)
+{
+    if (S.n > 64) return fail(MGX_ERR_INVALID, "mgx_fleet_step: at most 64 items per call");
+    S.nf = S.ne = 0;
     const bool ep_launch = tune(MGX_TUNE_FLEET_EPISODES) != 0;
     bool any_chunks = tune(MGX_TUNE_FLEET_BYVALUE) == 0;    // window chunks ride with the POINTER form of the kernel: single-instance layouts only
-    for (int32_t j = 0; j < n; j++) any_chunks = any_chunks || (items[j].refill_ring && items[j].refill_chunks > 0);
-    for (int32_t j = 0; j < n; j++) {
-        const mgx_fleet_item &it = items[j];
+    for (int32_t j = 0; j < S.n; j++) any_chunks = any_chunks || (S.items[j].refill_ring && S.items[j].refill_chunks > 0);
+    for (int32_t j = 0; j < S.n; j++) {
+        const mgx_fleet_item &it = S.items[j];
         const mgx_handle *h = it.handle;
-        // (a bucket with several modules of a kind shares the launch on the register form -- fleet_step_kernel_vm, round 6 -- when it
-        //  holds at most MS of a kind, takes continuous controls, walks the series in lock-step and its rows carry no forecast noise)
+        // (a bucket with several modules of a kind shares the launch on the register form -- fleet_step_kernel_vm -- when it holds at
+        //  most MS of a kind, takes continuous controls, walks the series in lock-step and its rows carry no forecast noise: state-only
+        //  rows of a noisy bucket included, which is why this is not rows_need_noise_pass)
         const bool multi_ok = h->multi && h->multi_small && !any_chunks && !it.action_id && !h->inplace && !h->windowed &&
-                              !(it.obs && (h->k.c.load_noise_std || h->k.c.pv_noise_std || h->k.c.grid_noise_std));
-        fuse[j] = (!h->multi || multi_ok) && !h->rolling && !dev_counter(h) && h->n_shards <= 1 && !(it.obs && h->k.H > 0 && !h->k.obs_state_only);
+                              !(it.obs && noisy(h->k.c));
         // (the rows of an in-place item are written by the step kernel itself exactly when episode_step_begin leaves the restart in it)
-        epf[j] = ep_launch && h->inplace && !h->multi && !dev_counter(h) && h->n_shards <= 1 &&
-                 (!it.obs || h->k.H == 0 || h->k.obs_state_only);
-        if (epf[j] && h->k.final_obs && !it.obs)
+        const bool own_rows = !dev_counter(h) && h->n_shards <= 1 && (!it.obs || rows_inline(h, it.obs));
+        S.fuse[j] = (!h->multi || multi_ok) && !h->rolling && own_rows;
+        S.epf[j] = ep_launch && h->inplace && !h->multi && own_rows;
+        if (S.epf[j] && h->k.final_obs && !it.obs)
             return fail(MGX_ERR_INVALID, "mgx_fleet_step: item %d: mgx_set_final_obs is set but the step writes no observation", j);
         for (int32_t q = 0; q < j; q++)
-            if (items[q].handle == it.handle) return fail(MGX_ERR_INVALID, "mgx_fleet_step: item %d steps the batch of item %d again", j, q);
-        if (fuse[j]) fz[nf++] = j;
-        if (epf[j]) ez[ne++] = j;
+            if (S.items[q].handle == it.handle) return fail(MGX_ERR_INVALID, "mgx_fleet_step: item %d steps the batch of item %d again", j, q);
+        if (S.fuse[j]) S.fz[S.nf++] = j;
+        if (S.epf[j]) S.ez[S.ne++] = j;
+        S.chunk_done[j] = false;
     }
-    bool chunk_done[64];                                    // window chunks that rode along with the step launch
-    for (int32_t j = 0; j < n; j++) chunk_done[j] = false;
-    for (int32_t j = 0; j < n; j++)
-        if (items[j].wait_prefetch) { if (int rc = mgx_prefetch_wait(items[j].handle, stream)) return rc; }
-    if (nf > 0) {
-        for (int32_t z = 0; z < nf; z++) {                // device copies of the batches' KArgs: uploaded when they changed
-            const int32_t j = fz[z];
-            if (int rc = sync_device_kargs(items[j].handle, st, "mgx_fleet_step: uploading the layout table")) return rc;
-            if (!items[j].action_id) continue;            // discrete item: its priority-list table, too
-            mgx_handle *h = items[j].handle;
-            PLWords tab;
-            if (int rc = encode_table(h, items[j].table, items[j].n_actions, &tab, "mgx_fleet_step")) return rc;
-            if (h->table_uploaded_valid && memcmp(&tab, &h->table_uploaded, sizeof(PLWords)) == 0) continue;
-            hipError_t e = hipSuccess;
-            DeviceGuard on_device(h->device);
-            if (!h->d_table) e = hipMalloc((void **)&h->d_table, sizeof(PLWords));
-            if (e == hipSuccess) e = hipMemcpyAsync(h->d_table, &tab, sizeof(PLWords), hipMemcpyHostToDevice, st);
-            if (e != hipSuccess) return hip_fail(e, "mgx_fleet_step: uploading the priority-list table");
-            memcpy(&h->table_uploaded, &tab, sizeof(PLWords));
-            h->table_uploaded_valid = true;
+    return MGX_OK;
+}
+
+// device copy of the priority-list table of a discrete fleet item: encoded, and uploaded on `st` when it changed
+static int upload_table(const mgx_fleet_item &it, hipStream_t st)
+{
+    if (!it.action_id) return MGX_OK;
+    mgx_handle *h = it.handle;
+    PLWords tab;
+    if (int rc = encode_table(h, it.table, it.n_actions, &tab, "mgx_fleet_step")) return rc;
+    if (h->table_uploaded_valid && memcmp(&tab, &h->table_uploaded, sizeof(PLWords)) == 0) return MGX_OK;
+    hipError_t e = hipSuccess;
+    DeviceGuard on_device(h->device);
+    if (!h->d_table) e = hipMalloc((void **)&h->d_table, sizeof(PLWords));
+    if (e == hipSuccess) e = hipMemcpyAsync(h->d_table, &tab, sizeof(PLWords), hipMemcpyHostToDevice, st);
+    if (e != hipSuccess) return hip_fail(e, "mgx_fleet_step: uploading the priority-list table");
+    memcpy(&h->table_uploaded, &tab, sizeof(PLWords));
+    h->table_uploaded_valid = true;
+    return MGX_OK;
+}
+
+// one bucket of a by-value launch; episode_form: the KArgs a single in-place step would get (episode_step_begin)
+static void fill_bucket(FleetBucket &B, const mgx_fleet_item &it, bool episode_form)
+{
+    const mgx_handle *h = it.handle;
+    B.k = h->k;
+    if (episode_form) { B.k.g0 = 0; B.k.g1 = h->k.N; drop_ring_final_obs(B.k); }
+    B.hd.tab = it.action_id ? h->d_table : nullptr; B.hd.n_grids = h->k.N; B.hd.t = h->t; B.hd.flags = h->flags;
+    B.hd.pad0 = h->multi ? 1 : 0; B.hd.pad1 = 0;          // pad0: a bucket of the general path (fleet_step_kernel_vm)
+    B.actions = it.action_id ? (const void *)it.action_id : it.actions;
+    B.reward = it.reward; B.done = it.done; B.obs = it.obs; B.log = it.log;
+}
+
+// The items idx[0 .. nb) in one launch with the buckets' KArgs by value, the bucket = blockIdx.y: fleet_step_kernel_v -- its episode
+// form for in-place items -- or _vm where a bucket is of the general path.  Unused buckets stay unwritten, never read.
+static int fleet_launch_by_value(const FleetStep &S, const int32_t *idx, int32_t nb, bool episode_form)
+{
+    FleetArgsV fv;
+    fv.n = nb; fv.normalized = S.normalized; fv.pad0 = fv.pad1 = 0;
+    int32_t most = 0;
+    bool any_multi = false;                                // (never with chunks: see multi_ok above)
+    for (int32_t q = 0; q < nb; q++) {
+        const mgx_fleet_item &it = S.items[idx[q]];
+        fill_bucket(fv.b[q], it, episode_form);
+        any_multi = any_multi || it.handle->multi;
+        const int32_t wg = (int32_t)blocks_for(it.handle->k.N);
+        if (wg > most) most = wg;
+    }
+    const dim3 grid((unsigned)most, (unsigned)nb);
+    if (any_multi) fleet_step_kernel_vm<<<grid, BLOCK, 0, S.st>>>(fv);            // (in-place items are never of the general path)
+    else if (!episode_form) fleet_step_kernel_v<false><<<grid, BLOCK, 0, S.st>>>(fv);
+    else fleet_step_kernel_v<true><<<grid, BLOCK, 0, S.st>>>(fv);
+    return launched(episode_form ? "fleet_step_kernel_v<true> launch" : "fleet_step_kernel_v launch");
+}
+
+// ... or in the pointer form: the KArgs read from their device copies, window chunks as extra workgroups behind the steps'
+static int fleet_launch_by_pointer(FleetStep &S, const int32_t *idx, int32_t nb)
+{
+    FleetArgs fa;
+    FleetWin fw;
+    memset(&fa, 0, sizeof(fa));
+    memset(&fw, 0, sizeof(fw));
+    fa.n = nb;
+    fa.normalized = S.normalized;
+    int32_t blocks = 0, wblocks = 0;
+    size_t lds_max = 0;
+    for (int32_t q = 0; q < fa.n; q++) {
+        const int32_t j = idx[q];
+        const mgx_fleet_item &it = S.items[j];
+        mgx_handle *h = it.handle;
+        fa.k[q] = h->d_kargs;
+        fa.tab[q] = it.action_id ? h->d_table : nullptr;
+        fa.actions[q] = it.action_id ? (const void *)it.action_id : it.actions; fa.reward[q] = it.reward; fa.done[q] = it.done; fa.obs[q] = it.obs; fa.log[q] = it.log;
+        fa.t[q] = h->t; fa.flags[q] = h->flags; fa.block0[q] = blocks;
+        blocks += (int32_t)((h->k.N + BLOCK_FLEET - 1) / BLOCK_FLEET);
+        if (it.refill_ring && it.refill_chunks > 0) {                        // this step's share of the next ring
+            WindowsKPlan plan; size_t lds; int32_t ng, first, count;
+            (void)windows_plan(h, it.refill_ahead, it.refill_K, it.refill_ring, "mgx_fleet_step", &plan, &lds, &ng);
+            if (lds > 64 * 1024) continue;                                   // launched on its own below
+            chunk_range(ng, it.refill_chunk, it.refill_chunks, &first, &count);
+            S.chunk_done[j] = true;
+            if (count <= 0) continue;
+            const int w = fw.n++;
+            plan.group0 = first;
+            fw.k[w] = h->d_kargs; fw.ring[w] = it.refill_ring; fw.plan[w] = plan;
+            fw.t[w] = h->t + 1 + it.refill_ahead;
+            fw.block0[w] = wblocks;
+            fw.kind[w] = (h->layout.has_grid ? 1 : 0) | (h->k.obs_f32 ? 2 : 0);
+            fw.nstate[w] = 4 * h->layout.has_genset + 2 * h->layout.has_battery;
+            wblocks += count;
+            if (lds > lds_max) lds_max = lds;
         }
-        // MGX_TUNE_FLEET_BYVALUE = 0 keeps the pointer form of the kernel for every launch (A/B)
-        const bool by_value = tune(MGX_TUNE_FLEET_BYVALUE) != 0;
-        for (int32_t z0 = 0; z0 < nf; z0 += MGX_FLEET_MAX) {
-            const int32_t nb = nf - z0 < MGX_FLEET_MAX ? nf - z0 : MGX_FLEET_MAX;
-            bool chunks = !by_value;                       // window chunks riding along with this launch (refill="chunks")?
-            for (int32_t q = 0; q < nb && !chunks; q++) chunks = items[fz[z0 + q]].refill_ring && items[fz[z0 + q]].refill_chunks > 0;
-            bool any_multi = false;                        // (never with chunks: see multi_ok above)
-            for (int32_t q = 0; q < nb; q++) any_multi = any_multi || items[fz[z0 + q]].handle->multi;
-            if (!chunks) {
-                // the buckets' KArgs by value, the bucket = blockIdx.y (fleet_step_kernel_v): unused buckets stay unwritten, never read
-                FleetArgsV fv;
-                fv.n = nb; fv.normalized = normalized; fv.pad0 = fv.pad1 = 0;
-                int32_t most = 0;
-                for (int32_t q = 0; q < nb; q++) {
-                    const mgx_fleet_item &it = items[fz[z0 + q]];
-                    const mgx_handle *h = it.handle;
-                    FleetBucket &B = fv.b[q];
-                    B.k = h->k;
-                    B.hd.tab = it.action_id ? h->d_table : nullptr; B.hd.n_grids = h->k.N; B.hd.t = h->t; B.hd.flags = h->flags;
-                    B.hd.pad0 = h->multi ? 1 : 0; B.hd.pad1 = 0;          // pad0: a bucket of the general path (fleet_step_kernel_vm)
-                    B.actions = it.action_id ? (const void *)it.action_id : it.actions;
-                    B.reward = it.reward; B.done = it.done; B.obs = it.obs; B.log = it.log;
-                    const int32_t wg = (int32_t)blocks_for(h->k.N);
-                    if (wg > most) most = wg;
-                }
-                if (any_multi) fleet_step_kernel_vm<<<dim3((unsigned)most, (unsigned)nb), BLOCK, 0, st>>>(fv);
-                else fleet_step_kernel_v<false><<<dim3((unsigned)most, (unsigned)nb), BLOCK, 0, st>>>(fv);
-                hipError_t ev = hipGetLastError();
-                if (ev != hipSuccess) return hip_fail(ev, "fleet_step_kernel_v launch");
-                continue;
-            }
-            FleetArgs fa;
-            FleetWin fw;
-            memset(&fa, 0, sizeof(fa));
-            memset(&fw, 0, sizeof(fw));
-            fa.n = nb;
-            fa.normalized = normalized;
-            int32_t blocks = 0, wblocks = 0;
-            size_t lds_max = 0;
-            for (int32_t q = 0; q < fa.n; q++) {
-                const int32_t j = fz[z0 + q];
-                const mgx_fleet_item &it = items[j];
-                mgx_handle *h = it.handle;
-                fa.k[q] = h->d_kargs;
-                fa.tab[q] = it.action_id ? h->d_table : nullptr;
-                fa.actions[q] = it.action_id ? (const void *)it.action_id : it.actions; fa.reward[q] = it.reward; fa.done[q] = it.done; fa.obs[q] = it.obs; fa.log[q] = it.log;
-                fa.t[q] = h->t; fa.flags[q] = h->flags; fa.block0[q] = blocks;
-                blocks += (int32_t)((h->k.N + BLOCK_FLEET - 1) / BLOCK_FLEET);
-                if (it.refill_ring && it.refill_chunks > 0) {                        // this step's share of the next ring
-                    WindowsKPlan plan; size_t lds; int32_t ng, first, count;
-                    (void)windows_plan(h, it.refill_ahead, it.refill_K, it.refill_ring, "mgx_fleet_step", &plan, &lds, &ng);
-                    if (lds > 64 * 1024) continue;                                   // launched on its own below
-                    chunk_range(ng, it.refill_chunk, it.refill_chunks, &first, &count);
-                    chunk_done[j] = true;
-                    if (count <= 0) continue;
-                    const int w = fw.n++;
-                    plan.group0 = first;
-                    fw.k[w] = h->d_kargs; fw.ring[w] = it.refill_ring; fw.plan[w] = plan;
-                    fw.t[w] = h->t + 1 + it.refill_ahead;
-                    fw.block0[w] = wblocks;
-                    fw.kind[w] = (h->layout.has_grid ? 1 : 0) | (h->k.obs_f32 ? 2 : 0);
-                    fw.nstate[w] = 4 * h->layout.has_genset + 2 * h->layout.has_battery;
-                    wblocks += count;
-                    if (lds > lds_max) lds_max = lds;
-                }
-            }
-            fw.first_block = blocks;
-            fleet_step_kernel<<<(unsigned)(blocks + wblocks), BLOCK_FLEET, lds_max, st>>>(fa, fw);
-            hipError_t e = hipGetLastError();
-            if (e != hipSuccess) return hip_fail(e, "fleet_step_kernel launch");
-        }
-        for (int32_t z = 0; z < nf; z++) advance(items[fz[z]].handle, 1, st);
     }
-    for (int32_t z0 = 0; z0 < ne; z0 += MGX_FLEET_MAX) {    // in-place episodes: the episode form, KArgs by value as in step_once
-        const int32_t nb = ne - z0 < MGX_FLEET_MAX ? ne - z0 : MGX_FLEET_MAX;
-        FleetArgsV fv;
-        fv.n = nb; fv.normalized = normalized; fv.pad0 = fv.pad1 = 0;
-        int32_t most = 0;
-        for (int32_t q = 0; q < nb; q++) {
-            const mgx_fleet_item &it = items[ez[z0 + q]];
-            mgx_handle *h = it.handle;
-            if (it.action_id) {                            // discrete item: the device copy of its priority-list table
-                PLWords tab;
-                if (int rc = encode_table(h, it.table, it.n_actions, &tab, "mgx_fleet_step")) return rc;
-                if (!(h->table_uploaded_valid && memcmp(&tab, &h->table_uploaded, sizeof(PLWords)) == 0)) {
-                    hipError_t e = hipSuccess;
-                    DeviceGuard on_device(h->device);
-                    if (!h->d_table) e = hipMalloc((void **)&h->d_table, sizeof(PLWords));
-                    if (e == hipSuccess) e = hipMemcpyAsync(h->d_table, &tab, sizeof(PLWords), hipMemcpyHostToDevice, st);
-                    if (e != hipSuccess) return hip_fail(e, "mgx_fleet_step: uploading the priority-list table");
-                    memcpy(&h->table_uploaded, &tab, sizeof(PLWords));
-                    h->table_uploaded_valid = true;
-                }
-            }
-            FleetBucket &B = fv.b[q];
-            B.k = h->k; B.k.g0 = 0; B.k.g1 = h->k.N;
-            if (B.k.obs_state_only == 1) B.k.final_obs = nullptr;  // rings: mgx_patch_windows saves the rows of the restarted grids
-            B.hd.tab = it.action_id ? h->d_table : nullptr; B.hd.n_grids = h->k.N; B.hd.t = h->t; B.hd.flags = h->flags;
-            B.hd.pad0 = 0; B.hd.pad1 = 0;
-            B.actions = it.action_id ? (const void *)it.action_id : it.actions;
-            B.reward = it.reward; B.done = it.done; B.obs = it.obs; B.log = it.log;
-            const int32_t wg = (int32_t)blocks_for(h->k.N);
-            if (wg > most) most = wg;
-        }
-        fleet_step_kernel_v<true><<<dim3((unsigned)most, (unsigned)nb), BLOCK, 0, st>>>(fv);
-        hipError_t ev = hipGetLastError();
-        if (ev != hipSuccess) return hip_fail(ev, "fleet_step_kernel_v<true> launch");
-        for (int32_t q = 0; q < nb; q++) advance(items[ez[z0 + q]].handle, 1, st);
+    fw.first_block = blocks;
+    fleet_step_kernel<<<(unsigned)(blocks + wblocks), BLOCK_FLEET, lds_max, S.st>>>(fa, fw);
+    return launched("fleet_step_kernel launch");
+}
+
+// the prefetched rings some items are about to enter, then the shared launch: MGX_FLEET_MAX items each
+static int fleet_launch_shared(FleetStep &S)
+{
+    for (int32_t j = 0; j < S.n; j++)
+        if (S.items[j].wait_prefetch) { if (int rc = mgx_prefetch_wait(S.items[j].handle, S.st)) return rc; }
+    for (int32_t z = 0; z < S.nf; z++) {                  // device copies of the batches' KArgs and tables: uploaded when they changed
+        const mgx_fleet_item &it = S.items[S.fz[z]];
+        if (int rc = sync_device_kargs(it.handle, S.st, "mgx_fleet_step: uploading the layout table")) return rc;
+        if (int rc = upload_table(it, S.st)) return rc;
     }
-    for (int32_t j = 0; j < n; j++) {                     // the items with kernels of their own
-        if (fuse[j] || epf[j]) continue;
-        const mgx_fleet_item &it = items[j];
-        int rc;
-        if (it.action_id)
-            rc = mgx_step_discrete(it.handle, it.action_id, it.table, it.n_actions, nullptr, it.reward, it.done, it.obs, it.log, stream);
-        else
-            rc = step_once(it.handle, it.actions, normalized, it.reward, it.done, it.obs, it.log, st);
-        if (rc) return rc;
+    for (int32_t z0 = 0; z0 < S.nf; z0 += MGX_FLEET_MAX) {
+        const int32_t *idx = S.fz + z0;
+        const int32_t nb = S.nf - z0 < MGX_FLEET_MAX ? S.nf - z0 : MGX_FLEET_MAX;
+        // window chunks riding along with this launch (refill="chunks")?  MGX_TUNE_FLEET_BYVALUE = 0: the pointer form for every launch (A/B)
+        bool chunks = tune(MGX_TUNE_FLEET_BYVALUE) == 0;
+        for (int32_t q = 0; q < nb && !chunks; q++) chunks = S.items[idx[q]].refill_ring && S.items[idx[q]].refill_chunks > 0;
+        if (int rc = chunks ? fleet_launch_by_pointer(S, idx, nb) : fleet_launch_by_value(S, idx, nb, false)) return rc;
     }
+    for (int32_t z = 0; z < S.nf; z++) advance(S.items[S.fz[z]].handle, 1, S.st);
+    return MGX_OK;
+}
+
+// in-place episodes: the episode form, KArgs by value as in step_once
+static int fleet_launch_episodes(const FleetStep &S)
+{
+    for (int32_t z0 = 0; z0 < S.ne; z0 += MGX_FLEET_MAX) {
+        const int32_t *idx = S.ez + z0;
+        const int32_t nb = S.ne - z0 < MGX_FLEET_MAX ? S.ne - z0 : MGX_FLEET_MAX;
+        for (int32_t q = 0; q < nb; q++)
+            if (int rc = upload_table(S.items[idx[q]], S.st)) return rc;
+        if (int rc = fleet_launch_by_value(S, idx, nb, true)) return rc;
+        for (int32_t q = 0; q < nb; q++) advance(S.items[idx[q]].handle, 1, S.st);
+    }
+    return MGX_OK;
+}
+
+// the items with kernels of their own
+static int fleet_step_beside(const FleetStep &S)
+{
+    for (int32_t j = 0; j < S.n; j++) {
+        const mgx_fleet_item &it = S.items[j];
+        if (S.fuse[j] || S.epf[j]) continue;
+        if (int rc = it.action_id ? mgx_step_discrete(it.handle, it.action_id, it.table, it.n_actions, nullptr, it.reward, it.done, it.obs, it.log, S.st)
+                                  : step_once(it.handle, it.actions, S.normalized, it.reward, it.done, it.obs, it.log, S.st))
+            return rc;
+    }
+    return MGX_OK;
+}
+
+// window prefetch that did not ride along with the step launch
+static int fleet_refills(const FleetStep &S)
+{
     hipEvent_t fleet_gate = nullptr;                        // ONE gate event for every ring refill this fleet step starts
     hipStream_t gated = nullptr;
-    for (int32_t j = 0; j < n; j++) {                       // window prefetch that did not ride along with the step launch
-        const mgx_fleet_item &it = items[j];
-        if (!it.refill_ring || chunk_done[j]) continue;
+    for (int32_t j = 0; j < S.n; j++) {
+        const mgx_fleet_item &it = S.items[j];
+        if (!it.refill_ring || S.chunk_done[j]) continue;
         int rc;
         if (it.refill_chunks > 0)                           // a chunk, on the caller's stream (the counter has advanced: ahead as given)
-            rc = launch_windows(it.handle, it.refill_ahead, it.refill_K, it.refill_ring, st, "mgx_fleet_step", it.refill_chunk, it.refill_chunks);
+            rc = launch_windows(it.handle, it.refill_ahead, it.refill_K, it.refill_ring, S.st, "mgx_fleet_step", it.refill_chunk, it.refill_chunks);
         else if (it.refill_ahead > 0) {
             if (!fleet_gate) {
                 DeviceGuard on_device(it.handle->device);
                 if (int rc0 = ensure_prefetch_stream(it.handle, "mgx_fleet_step: creating the prefetch stream")) return rc0;
-                hipError_t e = hipEventRecord(it.handle->prefetch_gate, st);
+                hipError_t e = hipEventRecord(it.handle->prefetch_gate, S.st);
                 if (e != hipSuccess) return hip_fail(e, "mgx_fleet_step: recording the refill gate");
                 fleet_gate = it.handle->prefetch_gate;
             }
-            rc = observe_windows_ahead(it.handle, it.refill_ahead, it.refill_K, it.refill_ring, st, fleet_gate, &gated);
+            rc = observe_windows_ahead(it.handle, it.refill_ahead, it.refill_K, it.refill_ring, S.st, fleet_gate, &gated);
         } else
-            rc = mgx_observe_windows(it.handle, it.refill_K, it.refill_ring, stream);
+            rc = mgx_observe_windows(it.handle, it.refill_K, it.refill_ring, S.st);
         if (rc) return rc;
     }
     return MGX_OK;
+}
+
+int mgx_fleet_step(const mgx_fleet_item *items, int32_t n, int normalized, mgx_stream stream)
+{
+    g_err[0] = 0;
+    if (!items || n <= 0) return fail(MGX_ERR_INVALID, "mgx_fleet_step: no items");
+    FleetStep S;
+    S.items = items; S.n = n; S.normalized = normalized; S.st = (hipStream_t)stream;
+    if (int rc = fleet_check_items(S)) return rc;
+    if (int rc = fleet_classify(S)) return rc;
+    if (int rc = fleet_launch_shared(S)) return rc;
+    if (int rc = fleet_launch_episodes(S)) return rc;
+    if (int rc = fleet_step_beside(S)) return rc;
+    return fleet_refills(S);
 }
 
 int mgx_fleet_env_step(mgx_handle *const *handles, const void *const *actions, int32_t n, int normalized, mgx_stream stream)
@@ -2404,14 +2414,7 @@ int mgx_fleet_env_step(mgx_handle *const *handles, const void *const *actions, i
         }
     }
     if (int rc = mgx_fleet_step(items, n, normalized, stream)) return rc;
-    for (int32_t j = 0; j < n; j++) {                       // the slots move on, the envs move to the blocks they just completed
-        mgx_handle *h = handles[j];
-        h->env_next = h->env_next + 1 < h->env_n_slots ? h->env_next + 1 : 0;
-        if (h->env_ring_K <= 0) continue;
-        if (!enters[j]) { h->env_ring_pos += 1; continue; }
-        h->env_ring_idx = (h->env_ring_idx + 1) % 3;
-        h->env_ring_pos = 0;
-    }
+    for (int32_t j = 0; j < n; j++) env_advance(handles[j], enters[j]);
     return MGX_OK;
 }
 
@@ -2438,8 +2441,7 @@ int mgx_synthesize_series(const mgx_synth *a, mgx_stream stream)
     if (e != hipSuccess || ndev <= 0)
         return fail(MGX_ERR_DEVICE, "mgx_synthesize_series: no HIP device available -- this engine has no CPU path");
     synthesize_series_kernel<<<blocks_for(a->n_grids), BLOCK, 0, (hipStream_t)stream>>>(*a);
-    e = hipGetLastError();
-    return e == hipSuccess ? MGX_OK : hip_fail(e, "synthesize_series_kernel launch");
+    return launched("synthesize_series_kernel launch");
 }
 
 int mgx_generate_columns(const mgx_gen *a, mgx_stream stream)
@@ -2461,8 +2463,7 @@ int mgx_generate_columns(const mgx_gen *a, mgx_stream stream)
     if (e != hipSuccess || ndev <= 0)
         return fail(MGX_ERR_DEVICE, "mgx_generate_columns: no HIP device available -- this engine has no CPU path");
     generate_columns_kernel<<<blocks_for(a->n_grids), BLOCK, 0, (hipStream_t)stream>>>(*a);
-    e = hipGetLastError();
-    return e == hipSuccess ? MGX_OK : hip_fail(e, "generate_columns_kernel launch");
+    return launched("generate_columns_kernel launch");
 }
 
 int mgx_normalise_series(mgx_handle *h, void *load_n, void *pv_n, void *grid_n, int32_t *clipped, mgx_stream stream)
@@ -2472,7 +2473,7 @@ int mgx_normalise_series(mgx_handle *h, void *load_n, void *pv_n, void *grid_n, 
     if (h->multi) return fail(MGX_ERR_UNSUPPORTED, "mgx_normalise_series: needs exactly one module of every kind per grid");
     if (h->layout.has_grid && !grid_n) return fail(MGX_ERR_INVALID, "mgx_normalise_series: grid_n is NULL but the layout has a GridModule");
     if (h->rolling) return fail(MGX_ERR_UNSUPPORTED, "mgx_normalise_series: not offered for rolling windows (restarts rewrite series rows)");
-    if (h->k.c.load_noise_std || h->k.c.pv_noise_std || h->k.c.grid_noise_std)
+    if (noisy(h->k.c))
         return fail(MGX_ERR_UNSUPPORTED, "mgx_normalise_series: forecast noise depends on (step, horizon index): its windows are not "
                                          "slices of one series");
     if (int rc = need_obs_bounds(h, "mgx_normalise_series")) return rc;
@@ -2494,8 +2495,7 @@ int mgx_normalise_series(mgx_handle *h, void *load_n, void *pv_n, void *grid_n, 
     launch(0, load_n, 1);
     launch(1, pv_n, 1);
     if (h->layout.has_grid) launch(2, grid_n, 4);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? MGX_OK : hip_fail(e, "normalise_series_kernel launch");
+    return launched("normalise_series_kernel launch");
 }
 
 int mgx_metrics(mgx_handle *h, const double *values, int32_t M, double *sums, mgx_stream stream)
@@ -2511,8 +2511,7 @@ int mgx_metrics(mgx_handle *h, const double *values, int32_t M, double *sums, mg
     hipStream_t st = (hipStream_t)stream;
     colsum_stage1<<<dim3(nb, (unsigned)M), BLOCK, 0, st>>>(values, N, (int32_t)per_block, h->scratch);
     colsum_stage2<<<(unsigned)M, BLOCK, 0, st>>>(h->scratch, (int32_t)nb, sums);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? MGX_OK : hip_fail(e, "colsum launch");
+    return launched("colsum launch");
 }
 
 }  // extern "C"
