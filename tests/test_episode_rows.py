@@ -84,7 +84,7 @@ def _actions(g, K, n, names, normalized, device, dtype=torch.float64):
     u = torch.where(edge, torch.tensor(EDGES, dtype=torch.float64, device=device)[which], u)
     if not normalized:
         raw = (u - 0.5) * 300.0
-        goal = torch.tensor(["goal" in nm for nm in names], device=device)
+        goal = torch.tensor(["goal" in nm for nm in names], dtype=torch.bool, device=device)      # (bool also without a control)
         u = torch.where(goal, u, raw)
     return u.to(dtype).contiguous()
 
@@ -118,12 +118,15 @@ def _state_equal(a, b):
             assert torch.equal(a.batch.cols[name], b.batch.cols[name]), name
 
 
-def _twin_steps(twin, controls, hs, want, **step_kw):
+def _twin_steps(twin, controls, hs, want, walked=None, **step_kw):
     """K single steps of the final_observation=True twin: the per-step outputs the fused call offers, the rows, the rows before the
-    restarts (of the grids with done set; NaN elsewhere, as the fused call's pre-filled buffer keeps them) + the host statistics."""
+    restarts (of the grids with done set; NaN elsewhere, as the fused call's pre-filled buffer keeps them) + the host statistics.
+    ``walked``: a list that receives every grid's series row before each step."""
     rows = {k: [] for k in ("reward", "done", "soc_trace", "status_trace", "obs", "final_obs")}
     cols = twin.env.batch.cols
     for k in range(controls.shape[0]):
+        if walked is not None:
+            walked.append(twin.env.current_steps.clone())
         o, r, d, info = twin.step(controls[k], **step_kw)
         rows["reward"].append(r.clone()); rows["done"].append(d.clone())
         rows["obs"].append(o.clone())
@@ -144,11 +147,14 @@ def _same_bits(a, b):
 
 
 def _rows_equal_single_steps(device, discrete, arch, series, length, obs_dtype, shaper=False, per_step=True, normalized=True,
-                             action_dtype=torch.float64):
+                             action_dtype=torch.float64, make_batch=None, trace=None):
     """The fused launch with rows, in launches of uneven size, == a final_observation=True twin stepped K times (same first draw, same
-    seed)."""
+    seed).  ``make_batch(device, arch, series)``: the batch factory (default: ``_batch``, a generated batch of architecture ``arch``);
+    ``trace``: a dict that receives what an independent replay needs -- the controls (and the priority-list table), the series rows
+    the twin walked, the fused rewards and the state after the last launch."""
     from pymgrid_amd import _lib
     from pymgrid_amd.hetero import PerGridWindowEnv
+    make_batch = make_batch or _batch
     old = _lib.get_tunable("grid_major_copy")[0]
     if series == "gather":
         _lib.set_tunable("grid_major_copy", 0)
@@ -157,8 +163,8 @@ def _rows_equal_single_steps(device, discrete, arch, series, length, obs_dtype, 
                   obs_dtype=obs_dtype)
         if not discrete:
             kw["action_dtype"] = action_dtype
-        fused = PerGridWindowEnv(_batch(device, arch, series), **kw)
-        twin = PerGridWindowEnv(_batch(device, arch, series), final_observation=True, **kw)
+        fused = PerGridWindowEnv(make_batch(device, arch, series), **kw)
+        twin = PerGridWindowEnv(make_batch(device, arch, series), final_observation=True, **kw)
         for e in (fused, twin):
             torch.manual_seed(41 + SOAK)                   # the same first draw
             e.obs0 = e.reset()
@@ -175,16 +181,21 @@ def _rows_equal_single_steps(device, discrete, arch, series, length, obs_dtype, 
         for K in LAUNCHES:
             bufs = dict(obs=torch.full((K, N, D), float("nan"), dtype=obs_dtype, device=device),
                         final_obs=torch.full((K, N, D), float("nan"), dtype=obs_dtype, device=device))
+            walked = [] if trace is not None else None
             if discrete:
                 ids = torch.randint(0, n_act, (K, N), device=device, generator=g).to(torch.uint8) if per_step else fixed.expand(K, N)
                 out = fused.rollout(ids if per_step else fixed, K, reward=True, done=True, soc_trace=True, status_trace=True,
                                     observations=True, final_observations=True, out=bufs)
-                ref = _twin_steps(twin, ids.to(torch.int32), hs, out)
+                ref = _twin_steps(twin, ids.to(torch.int32), hs, out, walked)
             else:
                 actions = _actions(g, K, N, names, normalized, device, action_dtype)
                 out = fused.step_k(actions, normalized=normalized, reward=True, done=True, soc_trace=True, status_trace=True,
                                    observations=True, final_observations=True, out=bufs)
-                ref = _twin_steps(twin, actions, hs, out, normalized=normalized)
+                ref = _twin_steps(twin, actions, hs, out, walked, normalized=normalized)
+            if trace is not None:
+                trace["table"] = fused.env._table if discrete else None
+                trace.setdefault("launches", []).append(dict(controls=ids.contiguous() if discrete else actions, rows=torch.stack(walked),
+                                                             reward=out["reward"]))
             assert set(out) == set(ref) and {"obs", "final_obs", "done"} <= set(out), (sorted(out), sorted(ref))
             assert out["obs"] is bufs["obs"] and out["final_obs"] is bufs["final_obs"]
             d = out["done"]
@@ -209,6 +220,8 @@ def _rows_equal_single_steps(device, discrete, arch, series, length, obs_dtype, 
         # the test's own input: it cannot pass vacuously
         assert restarts > N and twice and first and last, (restarts, twice, first, last)
         assert int(fused.episode_stats["episodes"].sum()) == restarts
+        if trace is not None:
+            trace["state"] = {name: fused.env.batch.cols[name].clone() for name in ("charge", "soc", "gen_status") if name in fused.env.batch.cols}
         # the env stands where the twin stands: out["obs"][-1] is what the next step builds on, and the next step agrees
         if discrete:
             a = torch.randint(0, n_act, (N,), device=device, generator=g).to(torch.int32)

@@ -105,25 +105,17 @@ def test_inplace_episodes_equal_rolling_windows_through_restarts(arch, H, discre
     ring.close(); inpl.close()
 
 
-@pytest.mark.parametrize("arch,H,discrete,length,final,prefetch",
-                         [("genset+battery", 0, False, 9, False, 0), ("genset+battery", 0, False, 9, True, 0),
-                          ("genset+battery+grid", 0, True, None, True, 0), ("battery+grid", 4, False, 7, True, 0),
-                          ("genset+battery+grid", 24, False, 11, False, 0), ("genset+battery", 2, True, None, False, 0),
-                          ("genset+battery+grid", 24, False, 11, True, 4), ("battery+grid", 6, True, None, True, 16),
-                          ("genset+battery", 3, False, 5, False, 3)])
-@pytest.mark.parametrize("series", ["factorised", "materialised"])
-def test_native_auto_reset_equals_the_rolling_window_auto_reset(arch, H, discrete, length, final, prefetch, series, device):
-    """PerGridWindowEnv(auto_reset=True) with device draws: native (one launch per step: the step kernel restarts the grids it
-    finishes, mgx_set_auto_reset; the pre-restart rows through mgx_set_final_obs) against the rolling windows (step, restart
-    gather, observation pass): observations, rewards, done flags, final observations, the drawn starts / lengths and the per-grid
-    counters are identical step by step."""
+def _native_equals_rolling(device, arch, H, discrete, length, final, prefetch, series, make_batch=None):
+    """``make_batch(N, T, arch, device, H, series=series)``: the batch factory (default: ``_gen``, a generated batch of architecture
+    ``arch``)."""
     from pymgrid_amd.hetero import PerGridWindowEnv
+    make_batch = make_batch or _gen
     N, T = 1100, 200
     kw = dict(discrete=discrete, auto_reset=True, final_observation=final, seed=123, trajectory_length=length)
     if discrete:
         kw["remove_redundant_gensets"] = False
-    roll = PerGridWindowEnv(_gen(N, T, arch, device, H, series=series), native=False, obs_prefetch=0, **kw)
-    nat = PerGridWindowEnv(_gen(N, T, arch, device, H, series=series), native=True, obs_prefetch=prefetch,   # prefetch > 0: rings + patches
+    roll = PerGridWindowEnv(make_batch(N, T, arch, device, H, series=series), native=False, obs_prefetch=0, **kw)
+    nat = PerGridWindowEnv(make_batch(N, T, arch, device, H, series=series), native=True, obs_prefetch=prefetch,   # prefetch > 0: rings + patches
                            reuse_outputs=(3 if H in (0, 3) else 0), **kw)                         # (rotating reward / done / row buffers)
     assert nat.native and not roll.native
     lengths = None
@@ -150,6 +142,21 @@ def test_native_auto_reset_equals_the_rolling_window_auto_reset(arch, H, discret
         n_done += int(d1.sum())
     assert n_done > N                                       # every grid restarted at least once on average
     roll.close(); nat.close()
+
+
+@pytest.mark.parametrize("arch,H,discrete,length,final,prefetch",
+                         [("genset+battery", 0, False, 9, False, 0), ("genset+battery", 0, False, 9, True, 0),
+                          ("genset+battery+grid", 0, True, None, True, 0), ("battery+grid", 4, False, 7, True, 0),
+                          ("genset+battery+grid", 24, False, 11, False, 0), ("genset+battery", 2, True, None, False, 0),
+                          ("genset+battery+grid", 24, False, 11, True, 4), ("battery+grid", 6, True, None, True, 16),
+                          ("genset+battery", 3, False, 5, False, 3)])
+@pytest.mark.parametrize("series", ["factorised", "materialised"])
+def test_native_auto_reset_equals_the_rolling_window_auto_reset(arch, H, discrete, length, final, prefetch, series, device):
+    """PerGridWindowEnv(auto_reset=True) with device draws: native (one launch per step: the step kernel restarts the grids it
+    finishes, mgx_set_auto_reset; the pre-restart rows through mgx_set_final_obs) against the rolling windows (step, restart
+    gather, observation pass): observations, rewards, done flags, final observations, the drawn starts / lengths and the per-grid
+    counters are identical step by step."""
+    _native_equals_rolling(device, arch, H, discrete, length, final, prefetch, series)
 
 
 @pytest.fixture

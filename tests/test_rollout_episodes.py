@@ -84,11 +84,14 @@ def _state_equal(a, b):
             assert torch.equal(a.batch.cols[name], b.batch.cols[name]), name
 
 
-def _twin_steps(twin, ids, hs, want):
-    """K single steps of the twin: the per-step outputs the roll-out offers + the host statistics."""
+def _twin_steps(twin, ids, hs, want, walked=None):
+    """K single steps of the twin: the per-step outputs the roll-out offers + the host statistics.  ``walked``: a list that receives
+    every grid's series row before each step."""
     rows = {k: [] for k in ("reward", "done", "soc_trace", "status_trace")}
     cols = twin.env.batch.cols
     for k in range(ids.shape[0]):
+        if walked is not None:
+            walked.append(twin.env.current_steps.clone())
         _, r, d, _ = twin.step(ids[k].to(torch.int32))
         rows["reward"].append(r.clone()); rows["done"].append(d.clone())
         if "soc" in cols:
@@ -103,17 +106,18 @@ CASES = list(itertools.product(["genset+battery+grid", "genset+battery", "batter
                                [9, None], [0, 6], [False, True], [False, True]))
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("arch,series,length,H,shaper,per_step", CASES)
-def test_rollout_equals_single_steps(arch, series, length, H, shaper, per_step, device):
-    """rollout(ids) in launches of uneven size == step(ids[k]) K times on a twin env with the same first draw and seed."""
+def _rollout_equals_single_steps(device, arch, series, length, H, shaper, per_step, make_batch=None, trace=None):
+    """``make_batch(device, arch, series, H)``: the batch factory (default: ``_batch``, a generated batch of architecture ``arch``);
+    ``trace``: a dict that receives what an independent replay needs -- the ids, the priority-list table, the series rows the twin
+    walked, the roll-out's rewards and the state after the last launch."""
     from pymgrid_amd import _lib
     from pymgrid_amd.hetero import PerGridWindowEnv
+    make_batch = make_batch or _batch
     old = _lib.get_tunable("grid_major_copy")[0]
     if series == "gather":
         _lib.set_tunable("grid_major_copy", 0)
     try:
-        envs = [PerGridWindowEnv(_batch(device, arch, series, H), trajectory_length=length, discrete=True, auto_reset=True,
+        envs = [PerGridWindowEnv(make_batch(device, arch, series, H), trajectory_length=length, discrete=True, auto_reset=True,
                                  seed=23 + SOAK, reward_shaping_func=_shaper(shaper)) for _ in range(2)]
         roll, twin = envs
         for e in envs:
@@ -130,7 +134,11 @@ def test_rollout_equals_single_steps(arch, series, length, H, shaper, per_step, 
         for K in LAUNCHES:
             ids = torch.randint(0, n_act, (K, N), device=device, generator=g).to(torch.uint8) if per_step else fixed.expand(K, N)
             out = roll.rollout(ids if per_step else fixed, K, reward=True, done=True, soc_trace=True, status_trace=True)
-            ref = _twin_steps(twin, ids, hs, out)
+            walked = [] if trace is not None else None
+            ref = _twin_steps(twin, ids, hs, out, walked)
+            if trace is not None:
+                trace["table"] = roll.env._table
+                trace.setdefault("launches", []).append(dict(controls=ids.contiguous(), rows=torch.stack(walked), reward=out["reward"]))
             assert set(out) == set(ref), (sorted(out), sorted(ref))
             for name in out:
                 assert out[name].shape == (K, N) and torch.equal(out[name], ref[name]), (K, name)
@@ -149,6 +157,8 @@ def test_rollout_equals_single_steps(arch, series, length, H, shaper, per_step, 
         # the test's own input: it cannot pass vacuously
         assert restarts > N and twice and first and last, (restarts, twice, first, last)
         assert int(roll.episode_stats["episodes"].sum()) == restarts
+        if trace is not None:
+            trace["state"] = {name: roll.env.batch.cols[name].clone() for name in ("charge", "soc", "gen_status") if name in roll.env.batch.cols}
         a = torch.randint(0, n_act, (N,), device=device, generator=g).to(torch.int32)
         (o1, r1, d1, _), (o2, r2, d2, _) = roll.step(a), twin.step(a)
         assert torch.equal(o1, o2) and torch.equal(r1, r2) and torch.equal(d1, d2)
@@ -157,6 +167,13 @@ def test_rollout_equals_single_steps(arch, series, length, H, shaper, per_step, 
             e.env.close()
     finally:
         _lib.set_tunable("grid_major_copy", old)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("arch,series,length,H,shaper,per_step", CASES)
+def test_rollout_equals_single_steps(arch, series, length, H, shaper, per_step, device):
+    """rollout(ids) in launches of uneven size == step(ids[k]) K times on a twin env with the same first draw and seed."""
+    _rollout_equals_single_steps(device, arch, series, length, H, shaper, per_step)
 
 
 @pytest.mark.gpu

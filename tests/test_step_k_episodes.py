@@ -75,7 +75,7 @@ def _actions(g, K, n, names, normalized, device, dtype=torch.float64):
     u = torch.where(edge, torch.tensor(EDGES, dtype=torch.float64, device=device)[which], u)
     if not normalized:
         raw = (u - 0.5) * 300.0                           # -225 .. 240 energy units; u == 0.5 -> exactly 0
-        goal = torch.tensor(["goal" in nm for nm in names], device=device)
+        goal = torch.tensor(["goal" in nm for nm in names], dtype=torch.bool, device=device)      # (bool also without a control)
         u = torch.where(goal, u, raw)
     return u.to(dtype).contiguous()
 
@@ -109,11 +109,14 @@ def _state_equal(a, b):
             assert torch.equal(a.batch.cols[name], b.batch.cols[name]), name
 
 
-def _twin_steps(twin, actions, normalized, hs, want):
-    """K single steps of the twin: the per-step outputs the fused call offers + the host statistics."""
+def _twin_steps(twin, actions, normalized, hs, want, walked=None):
+    """K single steps of the twin: the per-step outputs the fused call offers + the host statistics.  ``walked``: a list that receives
+    every grid's series row before each step."""
     rows = {k: [] for k in ("reward", "done", "soc_trace", "status_trace")}
     cols = twin.env.batch.cols
     for k in range(actions.shape[0]):
+        if walked is not None:
+            walked.append(twin.env.current_steps.clone())
         _, r, d, _ = twin.step(actions[k], normalized=normalized)
         rows["reward"].append(r.clone()); rows["done"].append(d.clone())
         if "soc" in cols:
@@ -124,14 +127,18 @@ def _twin_steps(twin, actions, normalized, hs, want):
     return {k: torch.stack(v) for k, v in rows.items() if v and k in want}
 
 
-def _fused_equals_single_steps(device, arch, series, length, H, shaper, normalized, dtype=torch.float64):
+def _fused_equals_single_steps(device, arch, series, length, H, shaper, normalized, dtype=torch.float64, make_batch=None, trace=None):
+    """``make_batch(device, arch, series, H)``: the batch factory (default: ``_batch``, a generated batch of architecture ``arch``);
+    ``trace``: a dict that receives what an independent replay needs -- the controls, the series rows the twin walked, the fused
+    rewards and the state after the last launch."""
     from pymgrid_amd import _lib
+    make_batch = make_batch or _batch
     from pymgrid_amd.hetero import PerGridWindowEnv
     old = _lib.get_tunable("grid_major_copy")[0]
     if series == "gather":
         _lib.set_tunable("grid_major_copy", 0)
     try:
-        envs = [PerGridWindowEnv(_batch(device, arch, series, H), trajectory_length=length, discrete=False, auto_reset=True,
+        envs = [PerGridWindowEnv(make_batch(device, arch, series, H), trajectory_length=length, discrete=False, auto_reset=True,
                                  seed=23 + SOAK, reward_shaping_func=_shaper(shaper), action_dtype=dtype) for _ in range(2)]
         fused, twin = envs
         for e in envs:
@@ -146,7 +153,10 @@ def _fused_equals_single_steps(device, arch, series, length, H, shaper, normaliz
         for K in LAUNCHES:
             actions = _actions(g, K, N, names, normalized, device, dtype)
             out = fused.step_k(actions, normalized=normalized, reward=True, done=True, soc_trace=True, status_trace=True)
-            ref = _twin_steps(twin, actions, normalized, hs, out)
+            walked = [] if trace is not None else None
+            ref = _twin_steps(twin, actions, normalized, hs, out, walked)
+            if trace is not None:
+                trace.setdefault("launches", []).append(dict(controls=actions, rows=torch.stack(walked), reward=out["reward"]))
             assert set(out) == set(ref), (sorted(out), sorted(ref))
             for name in out:
                 assert out[name].shape == (K, N) and torch.equal(out[name], ref[name]), (K, name)
@@ -165,6 +175,8 @@ def _fused_equals_single_steps(device, arch, series, length, H, shaper, normaliz
         # the test's own input: it cannot pass vacuously
         assert restarts > N and twice and first and last, (restarts, twice, first, last)
         assert int(fused.episode_stats["episodes"].sum()) == restarts
+        if trace is not None:
+            trace["state"] = {name: fused.env.batch.cols[name].clone() for name in ("charge", "soc", "gen_status") if name in fused.env.batch.cols}
         a = _actions(g, 1, N, names, normalized, device, dtype)[0]
         (o1, r1, d1, _), (o2, r2, d2, _) = fused.step(a, normalized=normalized), twin.step(a, normalized=normalized)
         assert torch.equal(o1, o2) and torch.equal(r1, r2) and torch.equal(d1, d2)
