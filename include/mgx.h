@@ -593,6 +593,65 @@ int mgx_step_k_episodes_rows(mgx_handle *h, const void *actions, int32_t K, int 
                              double *soc_trace, uint32_t *status_trace, const mgx_episode_stats *stats,
                              const mgx_episode_rows *rows, mgx_stream stream);
 
+/* CLOSED-LOOP fused launches over in-place episodes: the control of every step is chosen inside the launch, by a policy applied to
+ * the observation the grid's last step (or reset) returned -- the loop `a = policy(obs); obs, r, done, _ = env.step(a)` K times in
+ * one launch.
+ *
+ * The policy is a small float64 network of plain IEEE operations (separate multiplies and adds, fixed order), so that a host loop
+ * over the returned observations reproduces every decision bit for bit.  x[0 .. n_in) is the grid's H = 0 observation row AS THE
+ * HANDLE'S OBSERVATION FORMAT HOLDS IT (mgx_set_obs_format float32: the float value widened back to double).
+ *     hidden layer (n_hidden > 0):  hid[u] = b1[u]; for j = 0 .. n_in - 1 in order: hid[u] = hid[u] + w1[u, j] * x[j];
+ *                                   then hid[u] = hid[u] > 0 ? hid[u] : 0.0 (NaN and -0.0 become +0.0)
+ *     output layer:                 y[o] = b2[o]; for j in order: y[o] = y[o] + w2[o, j] * v[j], v = hid (n_hidden > 0) or x
+ *     discrete head (mgx_rollout_policy_episodes):  best = -inf, id = 0; for o = 0 .. n_out - 1: if y[o] > best: best = y[o], id = o
+ *                                   -- ties go to the lowest index, a NaN never wins, all-NaN is id 0
+ *     continuous head (mgx_step_k_policy_episodes): u[o] = !(y[o] > 0) ? 0.0 : (y[o] > 1 ? 1.0 : y[o]) -- normalised controls in
+ *                                   the order of the action columns (mgx_step with normalized = 1)
+ * n_policies >= 1 parameter sets are stacked along a leading axis; policy_index[i] names the set of grid i (NULL: set 0 for every
+ * grid; an index outside [0, n_policies): set 0).  All arrays are float64 device arrays, C order. */
+#define MGX_POLICY_MAX_HIDDEN 64        /* n_hidden of a policy, at most */
+#define MGX_POLICY_LDS_BYTES 32768      /* the staged parameter sets of a launch, at most.  A launch stages
+                                         *     n_policies * 8 * even(m + (n_hidden ? n_hidden * (n_in + 1 + m) : n_in * m)) bytes,
+                                         * m = n_out (the discrete call: n_out rounded up to a multiple of 4), even(v) = v rounded
+                                         * up to an even number */
+typedef struct mgx_policy {
+    int32_t struct_size;         /* = sizeof(mgx_policy) */
+    int32_t n_policies;          /* P >= 1 */
+    int32_t n_in;                /* = mgx_obs_dim of the handle (an H = 0 row: at most 12) */
+    int32_t n_hidden;            /* 0: a linear policy on x; at most MGX_POLICY_MAX_HIDDEN */
+    int32_t n_out;               /* discrete: the table's n_actions (at most 12); continuous: mgx_action_dim (at most 4) */
+    int32_t reserved;
+    const double *w1;            /* [P, n_hidden, n_in]; not read when n_hidden = 0 */
+    const double *b1;            /* [P, n_hidden]; not read when n_hidden = 0 */
+    const double *w2;            /* [P, n_out, n_hidden ? n_hidden : n_in] */
+    const double *b2;            /* [P, n_out] */
+    const int32_t *policy_index; /* [N], or NULL */
+} mgx_policy;
+
+/* K discrete steps in one launch of rollout_policy_episodes_kernel, the priority-list id of step k being the discrete head of
+ * `policy` on the row the grid stands on before the step (after a restart inside the launch: the first row of the new episode).
+ * Everything else is what K calls of mgx_step_discrete with those ids leave: state, counter, the episode arrays, the draws of
+ * mgx_set_auto_reset, the statistics by the rule of mgx_episode_stats, rows->obs / rows->final_obs by the rule of mgx_episode_rows
+ * (rows may be NULL).  action_id_out: uint8 [K, N], the ids taken, or NULL.  `table`, `n_actions` as in mgx_rollout_episodes.
+ * Refused -- nothing is launched -- as mgx_rollout_episodes_rows refuses, with the same codes; a forecast horizon, a state-only
+ * observation mode and a set mgx_set_final_obs whether or not `rows` is given (the policy reads whole H = 0 rows).  On top:
+ * MGX_ERR_INVALID: NULL policy / table, policy->struct_size != sizeof(mgx_policy), n_policies < 1, n_in != mgx_obs_dim,
+ * n_out != n_actions, n_hidden < 0, NULL weights.  MGX_ERR_UNSUPPORTED: n_hidden > MGX_POLICY_MAX_HIDDEN, parameter sets beyond
+ * MGX_POLICY_LDS_BYTES (the message names the size).
+ * An ADDITION to ABI 9 that leaves MGX_ABI_MINOR at 3: consumers find it by name (dlsym). */
+int mgx_rollout_policy_episodes(mgx_handle *h, const mgx_policy *policy, const int32_t *table, int32_t n_actions, int32_t K,
+                                double *reward, uint8_t *done, double *soc_trace, uint32_t *status_trace, uint8_t *action_id_out,
+                                const mgx_episode_stats *stats, const mgx_episode_rows *rows, mgx_stream stream);
+
+/* The continuous twin (step_k_policy_episodes_kernel): the controls of step k are the continuous head of `policy`, stepped as
+ * mgx_step(..., normalized = 1) steps them.  actions_out: double [K, N, A], the controls taken, or NULL.  Refusals as above with
+ * mgx_step_k_episodes_rows in the place of mgx_rollout_episodes_rows and n_out != mgx_action_dim; MGX_ERR_UNSUPPORTED also on a
+ * handle whose action format is float32 (mgx_set_action_format): the controls are formed and written as doubles.
+ * An ADDITION to ABI 9 that leaves MGX_ABI_MINOR at 3: consumers find it by name (dlsym). */
+int mgx_step_k_policy_episodes(mgx_handle *h, const mgx_policy *policy, int32_t K, double *reward, uint8_t *done,
+                               double *soc_trace, uint32_t *status_trace, double *actions_out, const mgx_episode_stats *stats,
+                               const mgx_episode_rows *rows, mgx_stream stream);
+
 /* raise_errors=True (BaseMicrogridModule.__init__, base_module.py:40; as_source / as_sink, :213-224,265-270; _raise_error,
  * :79-93): the reference refuses a request a module cannot meet with a ValueError instead of clipping it.  mgx_step always
  * clips; mgx_check_step is its DRY RUN -- the same arithmetic on a register copy of the state, nothing stored, the counter

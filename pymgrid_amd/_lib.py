@@ -21,10 +21,12 @@ UNITS = (
     ("mgx_episodes.hip", "MGX_EPISODE_PART", 2),                        # MGX_EPISODE_PARTS: the roll-out over in-place episodes,
     ("mgx_step_episodes.hip", "MGX_STEP_EPISODE_PART", 2),              # ... the continuous K-step over them,
     ("mgx_episode_rows.hip", "MGX_EPISODE_ROWS_PART", 2),               # ... the roll-out with observation rows
-    ("mgx_step_episode_rows.hip", "MGX_STEP_EPISODE_ROWS_PART", 2),     # ... and its continuous twin
+    ("mgx_step_episode_rows.hip", "MGX_STEP_EPISODE_ROWS_PART", 2),     # ... and its continuous twin,
+    ("mgx_policy_episodes.hip", "MGX_POLICY_EPISODE_PART", 2),          # ... the closed-loop roll-out (a policy inside the launch)
+    ("mgx_step_policy_episodes.hip", "MGX_STEP_POLICY_EPISODE_PART", 2),    # ... and its continuous twin
 )
 # everything a built library is stamped with (source_hash): a file missing here would leave a stale libmgx.so looking current
-SOURCES = [os.path.join(_PKG, "csrc", f) for f in [u[0] for u in UNITS] + ["mgx_kernels.hpp", "mgx_core.hpp", "mgx_episode_rows.hpp"]] + \
+SOURCES = [os.path.join(_PKG, "csrc", f) for f in [u[0] for u in UNITS] + ["mgx_kernels.hpp", "mgx_core.hpp", "mgx_episode_rows.hpp", "mgx_policy.hpp"]] + \
           [os.path.join(_ROOT, "include", "mgx.h")]
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-fPIC"]
@@ -140,6 +142,17 @@ class EpisodeRows(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32), ("obs", C.c_void_p), ("final_obs", C.c_void_p)]
 
 
+class Policy(C.Structure):
+    """mgx_policy (include/mgx.h): the parameter sets of ``mgx_rollout_policy_episodes`` / ``mgx_step_k_policy_episodes`` (float64
+    device arrays; ``policy_index`` int32 [N] or NULL)."""
+    _fields_ = [(n, C.c_int32) for n in ("struct_size", "n_policies", "n_in", "n_hidden", "n_out", "reserved")] + \
+               [(n, C.c_void_p) for n in ("w1", "b1", "w2", "b2", "policy_index")]
+
+
+POLICY_MAX_HIDDEN = 64     # MGX_POLICY_MAX_HIDDEN
+POLICY_LDS_BYTES = 32768   # MGX_POLICY_LDS_BYTES
+
+
 class EpisodeStats(C.Structure):
     """mgx_episode_stats (include/mgx.h): the per-grid statistics ``mgx_rollout_episodes`` carries (device arrays, each may be NULL)."""
     _fields_ = [("ret_running", C.c_void_p), ("ret_sum", C.c_void_p), ("ret_last", C.c_void_p), ("episodes", C.c_void_p)]
@@ -209,6 +222,11 @@ SYMBOLS = {
                                             C.c_void_p, C.c_void_p, C.POINTER(EpisodeStats), C.POINTER(EpisodeRows), C.c_void_p]),
     "mgx_step_k_episodes_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.POINTER(EpisodeStats), C.POINTER(EpisodeRows), C.c_void_p]),
+    "mgx_rollout_policy_episodes": (C.c_int, [C.c_void_p, C.POINTER(Policy), c_i32_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(EpisodeStats), C.POINTER(EpisodeRows),
+                                              C.c_void_p]),
+    "mgx_step_k_policy_episodes": (C.c_int, [C.c_void_p, C.POINTER(Policy), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.POINTER(EpisodeStats), C.POINTER(EpisodeRows), C.c_void_p]),
     "mgx_metrics": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "mgx_reset_windows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -348,7 +366,8 @@ _REMARK_ECHO = re.compile(r"^\s*(\d+ \||\||In file included from)")     # the so
 
 
 def _parse_resource_usage(stderr_text):
-    """{demangled kernel name: {"vgpr", "sgpr", "scratch", "lds"}} out of hipcc's kernel-resource-usage remarks."""
+    """{demangled kernel name: {"vgpr", "agpr", "sgpr", "occupancy", "scratch", "lds", "sgpr_spill", "vgpr_spill"}} out of hipcc's
+    kernel-resource-usage remarks."""
     out, cur = {}, None
     for ln in stderr_text.splitlines():
         m = re.search(r"remark:\s+Function Name: (\S+)", ln)
@@ -357,7 +376,10 @@ def _parse_resource_usage(stderr_text):
             continue
         if cur is None:
             continue
-        for key, pat in (("sgpr", r"TotalSGPRs: (\d+)"), ("vgpr", r"remark:\s+VGPRs: (\d+)"), ("scratch", r"ScratchSize \[bytes/lane\]: (\d+)"),
+        # (agpr: vector values the compiler moved into accumulation registers when the VGPRs ran out -- no memory traffic and not
+        # counted as "VGPRs Spill", but moves inside the loop, and vgpr + agpr is what sets the occupancy)
+        for key, pat in (("sgpr", r"TotalSGPRs: (\d+)"), ("vgpr", r"remark:\s+VGPRs: (\d+)"), ("agpr", r"remark:\s+AGPRs: (\d+)"),
+                         ("occupancy", r"Occupancy \[waves/SIMD\]: (\d+)"), ("scratch", r"ScratchSize \[bytes/lane\]: (\d+)"),
                          ("lds", r"LDS Size \[bytes/block\]: (\d+)"), ("sgpr_spill", r"SGPRs Spill: (\d+)"), ("vgpr_spill", r"VGPRs Spill: (\d+)")):
             m = re.search(pat, ln)
             if m:

@@ -5,6 +5,7 @@
 //   hipcc --offload-arch=gfx950 -fPIC -shared *.o -o libmgx.so
 #include "mgx_kernels.hpp"
 #include "mgx_episode_rows.hpp"
+#include "mgx_policy.hpp"
 
 #include <cstdarg>
 #include <cstdio>
@@ -2097,6 +2098,84 @@ int mgx_step_k_episodes_rows(mgx_handle *h, const void *actions, int32_t K, int 
     if (!rows || (!rows->obs && !rows->final_obs))
         return mgx_step_k_episodes(h, actions, K, normalized, reward, done, soc_trace, status_trace, stats, stream);
     return step_k_episodes_impl(h, actions, K, normalized, reward, done, soc_trace, status_trace, stats, rows, stream, "mgx_step_k_episodes_rows");
+}
+
+// The closed-loop launches (mgx_policy.hpp).  What they check of the policy before prepare_episode_launch: what needs no handle
+static int policy_struct_refusal(const mgx_policy *policy, const char *fn)
+{
+    if (policy->struct_size != (int32_t)sizeof(mgx_policy))
+        return fail(MGX_ERR_INVALID, "%s: policy->struct_size is %d, sizeof(mgx_policy) is %d", fn, policy->struct_size, (int)sizeof(mgx_policy));
+    if (policy->n_policies < 1 || policy->n_hidden < 0 || policy->n_out < 0)
+        return fail(MGX_ERR_INVALID, "%s: a policy of %d parameter sets, %d hidden units, %d outputs", fn, policy->n_policies,
+                    policy->n_hidden, policy->n_out);
+    if (!policy->w2 || !policy->b2 || (policy->n_hidden > 0 && (!policy->w1 || !policy->b1)))
+        return fail(MGX_ERR_INVALID, "%s: NULL policy weights", fn);
+    return MGX_OK;
+}
+
+// ... and behind it, on a handle the launch accepts (`n_out`: the table's n_actions / the handle's action_dim, `out_name`: which).
+// The rows the policy reads are the rows the launch would write: the same refusals whether or not the caller takes them, so
+// `rows` NULL goes through prepare_episode_launch as a mgx_episode_rows without buffers.  `pad`: the multiple the staged sets round
+// n_out up to.
+static int policy_dims_refusal(mgx_handle *h, const mgx_policy *policy, int32_t n_out, int32_t pad, const char *out_name, const char *fn,
+                               EpisodePolicyLaunch &P)
+{
+    const int32_t D = h->k.obs_dim;
+    const int32_t row = 2 + 4 * ((h->flags & F_GENSET) != 0) + 2 * ((h->flags & F_BATTERY) != 0) + 4 * ((h->flags & F_GRID) != 0);
+    if (D != row) return fail(MGX_ERR_UNSUPPORTED, "%s: the handle's rows hold %d columns, the H = 0 row of its layout %d", fn, D, row);
+    if (policy->n_in != D) return fail(MGX_ERR_INVALID, "%s: policy->n_in is %d, mgx_obs_dim is %d", fn, policy->n_in, D);
+    if (policy->n_out != n_out) return fail(MGX_ERR_INVALID, "%s: policy->n_out is %d, %s is %d", fn, policy->n_out, out_name, n_out);
+    if (policy->n_hidden > MGX_POLICY_MAX_HIDDEN)
+        return fail(MGX_ERR_UNSUPPORTED, "%s: policy->n_hidden is %d, at most MGX_POLICY_MAX_HIDDEN = %d", fn, policy->n_hidden, MGX_POLICY_MAX_HIDDEN);
+    const int32_t n_staged = (n_out + pad - 1) / pad * pad;      // (the discrete kernel takes its outputs in groups: policy_outputs)
+    const int64_t stride = (policy_set_doubles(D, policy->n_hidden, n_staged) + 1) & ~1;
+    const int64_t bytes = (int64_t)policy->n_policies * stride * (int64_t)sizeof(double);
+    if (bytes > MGX_POLICY_LDS_BYTES)
+        return fail(MGX_ERR_UNSUPPORTED, "%s: %d parameter sets of %lld bytes each take %lld bytes of LDS, at most MGX_POLICY_LDS_BYTES = %d",
+                    fn, policy->n_policies, (long long)(stride * (int64_t)sizeof(double)), (long long)bytes, MGX_POLICY_LDS_BYTES);
+    P.pol = PolicyArgs{policy->w1, policy->b1, policy->w2, policy->b2, policy->policy_index, policy->n_policies, policy->n_hidden,
+                       n_staged, n_out, (int32_t)stride};
+    P.lds_bytes = (unsigned)bytes;
+    return MGX_OK;
+}
+
+int mgx_rollout_policy_episodes(mgx_handle *h, const mgx_policy *policy, const int32_t *table, int32_t n_actions, int32_t K,
+                                double *reward, uint8_t *done, double *soc_trace, uint32_t *status_trace, uint8_t *action_id_out,
+                                const mgx_episode_stats *stats, const mgx_episode_rows *rows, mgx_stream stream)
+{
+    g_err[0] = 0;
+    const char *fn = "mgx_rollout_policy_episodes";
+    if (!h || !policy || !table) return fail(MGX_ERR_INVALID, "%s: NULL argument", fn);
+    if (int rc = policy_struct_refusal(policy, fn)) return rc;
+    const mgx_episode_rows none{(int32_t)sizeof(mgx_episode_rows), 0, nullptr, nullptr};
+    PLWords tab;
+    EpisodePolicyLaunch P{};
+    if (int rc = prepare_episode_launch(h, K, reward, done, soc_trace, status_trace, stats, rows ? rows : &none, stream, fn,
+                                        "mgx_rollout_discrete", "mgx_step_lists", table, n_actions, &tab, P.r)) return rc;
+    if (int rc = policy_dims_refusal(h, policy, tab.n_actions, 4, "n_actions", fn, P)) return rc;
+    P.r.e.tab = &tab; P.actions_out = action_id_out;
+    const bool launched = launch_rollout_policy_episodes_p0(P) || launch_rollout_policy_episodes_p1(P);
+    return finish_episode_launch(h, P.r.e, launched, "rollout_policy_episodes_kernel launch", fn);
+}
+
+int mgx_step_k_policy_episodes(mgx_handle *h, const mgx_policy *policy, int32_t K, double *reward, uint8_t *done,
+                               double *soc_trace, uint32_t *status_trace, double *actions_out, const mgx_episode_stats *stats,
+                               const mgx_episode_rows *rows, mgx_stream stream)
+{
+    g_err[0] = 0;
+    const char *fn = "mgx_step_k_policy_episodes";
+    if (!h || !policy) return fail(MGX_ERR_INVALID, "%s: NULL argument", fn);
+    if (int rc = policy_struct_refusal(policy, fn)) return rc;
+    const mgx_episode_rows none{(int32_t)sizeof(mgx_episode_rows), 0, nullptr, nullptr};
+    EpisodePolicyLaunch P{};
+    if (int rc = prepare_episode_launch(h, K, reward, done, soc_trace, status_trace, stats, rows ? rows : &none, stream, fn, "mgx_step_k",
+                                        "mgx_step", nullptr, 0, nullptr, P.r)) return rc;
+    if (h->k.act_f32)
+        return fail(MGX_ERR_UNSUPPORTED, "%s: the handle's action format is float32 (mgx_set_action_format); the policy's controls are doubles", fn);
+    if (int rc = policy_dims_refusal(h, policy, h->action_dim, 1, "mgx_action_dim", fn, P)) return rc;
+    P.actions_out = actions_out;
+    const bool launched = launch_step_k_policy_episodes_p0(P) || launch_step_k_policy_episodes_p1(P);
+    return finish_episode_launch(h, P.r.e, launched, "step_k_policy_episodes_kernel launch", fn);
 }
 
 int mgx_rollout_lists(mgx_handle *h, const int32_t *action_id, int per_step, const int32_t *lists, int32_t n_lists, int32_t list_len,

@@ -1,0 +1,224 @@
+// mgx_policy.hpp -- what the two CLOSED-LOOP fused episode launches share (mgx_rollout_policy_episodes: mgx_policy_episodes.hip,
+// mgx_step_k_policy_episodes: mgx_step_policy_episodes.hip): the policy of include/mgx.h (a small fp64 network of plain IEEE
+// operations) staged in LDS once per workgroup and evaluated per lane between "row of the coming step" and "step", and the
+// lane's row strip -- the H = 0 row is built ONCE per step into the wave's tile, read back as the policy's input and, where
+// the launch returns observations, streamed out of the same tile as the row the step before returned.
+// A header of its own on top of mgx_episode_rows.hpp, which stays as it is: every kernel that exists without this file comes out
+// of the compiler exactly as before.
+#pragma once
+#include "mgx_episode_rows.hpp"
+
+namespace mgx {
+
+// mgx_policy as the kernels see it.  `n_out`: the outputs of a STAGED set -- mgx_policy.n_out (`n_real`), which the discrete call
+// rounds up to a multiple of four (policy_outputs).  `stride`: doubles of one staged set (policy_set_doubles, rounded up to even).
+struct PolicyArgs {
+    const double *w1, *b1, *w2, *b2;
+    const int32_t *index;            // [N] or NULL
+    int32_t n_policies, n_hidden, n_out, n_real, stride;
+};
+
+// One parameter set as it lies in LDS (doubles), for a row of D values:
+//   n_hidden > 0:  b2[0 .. n_out) | per hidden unit u: W1[u, 0 .. D), b1[u], W2[0 .. n_out, u]
+//   n_hidden = 0:  b2[0 .. n_out) | per input j: W2[0 .. n_out, j]
+// -- in the order the evaluation walks it: a unit's pre-activation, then its contribution to every output.  The hidden vector is
+// never stored: unit u is folded into the n_out running sums as soon as it is known, and every sum still receives its addends
+// in the order u = 0, 1, ... the rule of include/mgx.h fixes.
+__host__ __device__ inline int32_t policy_set_doubles(int32_t D, int32_t n_hidden, int32_t n_out)
+{
+    return n_out + (n_hidden > 0 ? n_hidden * (D + 1 + n_out) : D * n_out);
+}
+
+// The P sets out of the caller's arrays into `lds`, by all threads of the workgroup; ends in the workgroup's barrier (call it
+// before any lane leaves).
+__device__ __forceinline__ void stage_policy(const PolicyArgs &pa, int32_t D, double *lds)
+{
+    const int32_t nh = pa.n_hidden, no = pa.n_out, nr = pa.n_real;
+    const int32_t rec = D + 1 + no;
+    const int32_t used = policy_set_doubles(D, nh, no);
+    const int32_t total = pa.n_policies * pa.stride;
+    for (int32_t e = (int32_t)threadIdx.x; e < total; e += BLOCK_K) {
+        const int32_t ps = e / pa.stride, r = e - ps * pa.stride;
+        double v = 0.0;                                          // (a padding output; the padding double of an odd set)
+        if (r < no) {
+            if (r < nr) v = pa.b2[ps * nr + r];
+        } else if (r < used) {
+            const int32_t q = r - no;
+            if (nh > 0) {
+                const int32_t u = q / rec, c = q - u * rec;
+                if (c < D) v = pa.w1[(ps * nh + u) * D + c];
+                else if (c == D) v = pa.b1[ps * nh + u];
+                else if (c - D - 1 < nr) v = pa.w2[(ps * nr + (c - D - 1)) * nh + u];
+            } else {
+                const int32_t j = q / no, o = q - j * no;
+                if (o < nr) v = pa.w2[(ps * nr + o) * D + j];
+            }
+        }
+        lds[e] = v;
+    }
+    __syncthreads();
+}
+
+// where the lane's set starts in the staged image: policy_index[i], 0 where it is absent or outside [0, P)
+__device__ __forceinline__ int32_t policy_lane_offset(const PolicyArgs &pa, int64_t i)
+{
+    int32_t ps = pa.index ? pa.index[i] : 0;
+    if (ps < 0 || ps >= pa.n_policies) ps = 0;
+    return ps * pa.stride;
+}
+
+// y[0 .. no) of the rule of include/mgx.h for the input x[0 .. D): separate multiplies and adds (the build has -ffp-contract=off),
+// every sum in index order.  `w`: the lane's set in LDS -- lanes of one set read the same address (a broadcast).  `no`: the width
+// of the staged set (PolicyArgs.n_out), NO its static bound.  The outputs go in groups of four behind ONE wave-uniform branch
+// each (the discrete call stages a multiple of four, the padding outputs with zero weights and never looked at): a test per
+// output becomes a select under a mask of its own, and twelve masks across the loop over the hidden units spilled scalar registers.
+template <int D, int NO>
+__device__ __forceinline__ void policy_outputs(const double *w, int32_t nh, int32_t no, const double (&x)[D], double (&y)[NO])
+{
+    constexpr int G = NO < 4 ? NO : 4;
+    static_assert(NO % G == 0, "whole groups");
+#pragma unroll
+    for (int o = 0; o < NO; o++) y[o] = 0.0;
+#pragma unroll
+    for (int c = 0; c < NO; c += G)
+        if (c < no) {
+#pragma unroll
+            for (int o = c; o < c + G; o++) y[o] = w[o];
+        }
+    w += no;
+    if (nh > 0) {
+        const int32_t rec = D + 1 + no;
+#pragma nounroll
+        for (int32_t u = 0; u < nh; u++) {
+            double h = w[D];
+#pragma unroll
+            for (int j = 0; j < D; j++) h = h + w[j] * x[j];
+            h = h > 0.0 ? h : 0.0;                                // (NaN and -0.0 become +0.0)
+#pragma unroll
+            for (int c = 0; c < NO; c += G)
+                if (c < no) {
+#pragma unroll
+                    for (int o = c; o < c + G; o++) y[o] = y[o] + w[D + 1 + o] * h;
+                }
+            w += rec;
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < D; j++) {
+#pragma unroll
+            for (int c = 0; c < NO; c += G)
+                if (c < no) {
+#pragma unroll
+                    for (int o = c; o < c + G; o++) y[o] = y[o] + w[o] * x[j];
+                }
+            w += no;
+        }
+    }
+}
+
+// the discrete head: the lowest o whose y[o] is strictly greater than everything before it, from -inf (a NaN never wins)
+template <int NO>
+__device__ __forceinline__ int32_t policy_argmax(const double (&y)[NO], int32_t no)
+{
+    double best = -__builtin_inf();
+    int32_t id = 0;
+#pragma unroll
+    for (int o = 0; o < NO; o++)
+        if (o < no) {
+            const bool m = y[o] > best;
+            best = m ? y[o] : best;
+            id = m ? o : id;
+        }
+    return id;
+}
+
+// the continuous head: a normalised control
+__device__ __forceinline__ double policy_clip(double y) { return !(y > 0.0) ? 0.0 : (y > 1.0 ? 1.0 : y); }
+
+// columns of an H = 0 row of layout F
+template <int F>
+constexpr int policy_row_dim() { return 2 + 4 * ((F & F_GENSET) != 0) + 2 * ((F & F_BATTERY) != 0) + 4 * ((F & F_GRID) != 0); }
+
+// The row the lane's grid stands on -- series row t_row, state `s`, series values out of `in` -- into the lane's strip of the
+// wave's tile, in the handle's observation format (episode_row_h0: observe_row_h0's values bit for bit, the padding rows too),
+// and out of the strip again as the policy's input: float32 rows are widened back, so the policy sees what the caller is given.
+template <int F>
+__device__ __forceinline__ void policy_row(const KArgs *__restrict__ a_dev, int32_t T, uint32_t desc, int64_t i, int32_t t_row,
+                                           const Inputs &in, const RowBounds<F> &b, const Params &p, const State &s, double *tile,
+                                           double (&x)[policy_row_dim<F>()])
+{
+    constexpr int D = policy_row_dim<F>();
+    const int lane = threadIdx.x & 63;
+    if (row_desc_f32(desc)) {
+        float *q = reinterpret_cast<float *>(tile) + lane * D;
+        episode_row_h0<F>(a_dev, T, desc, i, t_row, in, b, p, s, q);
+#pragma unroll
+        for (int j = 0; j < D; j++) x[j] = (double)q[j];
+    } else {
+        double *q = tile + lane * D;
+        episode_row_h0<F>(a_dev, T, desc, i, t_row, in, b, p, s, q);
+#pragma unroll
+        for (int j = 0; j < D; j++) x[j] = q[j];
+    }
+}
+
+// ... and the strips as row `r64` (element offset) of `obs`: a full wave's 64 rows as 16-byte non-temporal stores out of the tile
+// (stream_row_tile), the last wave of a batch that is no multiple of 64 lane by lane -- the bytes store_episode_row writes.
+template <int D>
+__device__ __forceinline__ void emit_policy_row(uint32_t desc, void *__restrict__ obs, int64_t r64, const double *tile)
+{
+    const int lane = threadIdx.x & 63;
+    if (MGX_EPISODE_ROWS_TILE && __builtin_amdgcn_read_exec() == ~0ull) {
+        __builtin_amdgcn_wave_barrier();
+        if (row_desc_f32(desc)) stream_row_tile(reinterpret_cast<const float *>(tile), (float *)obs + (r64 - (int64_t)lane * D), D);
+        else stream_row_tile(tile, (double *)obs + (r64 - (int64_t)lane * D), D);
+        __builtin_amdgcn_wave_barrier();                 // (the next row goes into the same tile)
+    } else if (row_desc_f32(desc)) {
+        const float *q = reinterpret_cast<const float *>(tile) + lane * D;
+#pragma unroll
+        for (int j = 0; j < D; j++) ((float *)obs)[r64 + j] = q[j];
+    } else {
+        const double *q = tile + lane * D;
+#pragma unroll
+        for (int j = 0; j < D; j++) ((double *)obs)[r64 + j] = q[j];
+    }
+}
+
+// The arguments of the two kernels, ONE struct by value each (late_kernargs)
+struct RolloutPolicyArgs {
+    KArgs a;
+    PLWords tab;
+    PolicyArgs pol;
+    int32_t t0, K;
+    FusedOut out;
+    mgx_episode_stats es;
+    int32_t gpb;
+    uint32_t desc;                   // pack_row_desc(a)
+    const KArgs *a_dev;
+    void *obs, *final_obs;
+    uint8_t *ids_out;                // [K, N] or NULL
+};
+struct StepPolicyArgs {
+    KArgs a;
+    PolicyArgs pol;
+    int32_t t0, K;
+    int32_t gpb;
+    uint32_t desc;                   // pack_row_desc(a)
+    FusedOut out;
+    mgx_episode_stats es;
+    const KArgs *a_dev;
+    void *obs, *final_obs;
+    double *actions_out;             // [K, N, A] or NULL
+};
+
+// ---- host side: what mgx_abi.hip hands the slices of the two translation units ----
+struct EpisodePolicyLaunch {
+    EpisodeRowsLaunch r;             // as for the kernels with rows (obs / final_obs may both be NULL here)
+    PolicyArgs pol;
+    unsigned lds_bytes;              // n_policies * stride doubles: the dynamic LDS of the launch
+    void *actions_out;               // the ids (uint8 [K, N]) or controls (double [K, N, A]) the policy chose, or NULL
+};
+bool launch_rollout_policy_episodes_p0(const EpisodePolicyLaunch &L); bool launch_rollout_policy_episodes_p1(const EpisodePolicyLaunch &L);
+bool launch_step_k_policy_episodes_p0(const EpisodePolicyLaunch &L); bool launch_step_k_policy_episodes_p1(const EpisodePolicyLaunch &L);
+
+}  // namespace mgx

@@ -1,0 +1,169 @@
+// mgx_policy_episodes.hip -- the CLOSED-LOOP fused discrete roll-out over per-grid in-place episodes (mgx_rollout_policy_episodes):
+// rollout_episodes_rows_kernel (mgx_episode_rows.hip) with the priority-list id of every step chosen inside the launch, by the
+// policy of include/mgx.h applied to the row the grid stands on.  Translation units of their own (MGX_EPISODE_PARTS slices of the
+// layouts):
+//   hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -c -DMGX_POLICY_EPISODE_PART=p mgx_policy_episodes.hip -o mgx_policy_episodes_p.o
+// so every other kernel comes out of the compiler exactly as it did without this file.
+#include "mgx_policy.hpp"
+
+#ifndef MGX_POLICY_EPISODE_PART
+#error "compile with -DMGX_POLICY_EPISODE_PART=<0..MGX_EPISODE_PARTS-1>"
+#endif
+
+// layouts (template parameter F) of this slice: MGX_EPISODE_FLAGS_<part> (mgx_kernels.hpp)
+#define MGX_PART_FLAGS MGX_CAT(MGX_EPISODE_FLAGS_, MGX_POLICY_EPISODE_PART)
+
+namespace mgx {
+
+// Template parameters, ring, statistics, restart and final_obs as rollout_episodes_rows_kernel; there is no id stream.  Per step k
+// (counter t = t0 + k, row offset `off`):
+//   the row of series row t + off with the state before the step is built from ring slot 0 (which the step is about to consume)
+//   into the lane's strip of the wave's tile (policy_row) -- at k = 0 the row the handle last returned, afterwards the row step
+//   k - 1 returned: it leaves as obs[k - 1] where the launch returns observations, so a row is built once for both uses;
+//   the policy turns the strip into an id, the id into its list word (a 12-entry LDS table) and the step runs as in the open-loop
+//   kernel.  After the last step the row of t0 + K is built for obs[K - 1] alone.
+// The parameter sets wait in dynamic LDS (stage_policy), the lane keeps the offset of its set; inside the loop the policy costs one
+// scalar register (n_hidden and the two n_out in one word) -- its pointers end their lives in the prologue.
+template <int F, int U, int SRC>
+__global__ __launch_bounds__(BLOCK_K) void rollout_policy_episodes_kernel(const RolloutPolicyArgs g)
+{
+    constexpr int D = policy_row_dim<F>();
+    constexpr int NO = 12;                                      // ids of a PLWords table
+    const KArgs &a = g.a;
+    const int32_t t0 = g.t0, K = g.K, gpb = g.gpb;
+    const FusedOut &out = g.out;
+    const mgx_episode_stats &es = g.es;
+    void *__restrict__ obs = g.obs;
+    uint8_t *__restrict__ ids_out = g.ids_out;
+    const bool want_final = g.final_obs != nullptr;
+    uint32_t desc = g.desc;
+    uint32_t dims = (uint32_t)g.pol.n_hidden | (uint32_t)g.pol.n_out << 8 | (uint32_t)g.pol.n_real << 16;
+    const auto *late = late_kernargs<RolloutPolicyArgs>();
+    const int64_t i = (int64_t)blockIdx.x * gpb + threadIdx.x;
+    __shared__ uint32_t word_of_id[NO];
+    // one wave-private tile per wave: the lanes' row strips
+    __shared__ __attribute__((aligned(16))) double row_tiles[(BLOCK_K / 64) * 64 * ROW_TILE_MAX_D];
+    extern __shared__ __attribute__((aligned(16))) double policy_lds[];
+    if (threadIdx.x < NO) word_of_id[threadIdx.x] = pl_select(g.tab, (int32_t)threadIdx.x);
+    stage_policy(g.pol, D, policy_lds);                         // (ends in the only barrier: before any lane leaves)
+    if ((int32_t)threadIdx.x >= gpb || i >= a.N) return;
+    double *tile = row_tiles + (threadIdx.x >> 6) * (64 * ROW_TILE_MAX_D);
+    const double *my_set = policy_lds + policy_lane_offset(g.pol, i);
+    const int64_t N = a.N;
+    Params p; State s; Derived d;
+    load_state<F>(a.c, i, true, s);              // (the SoC too: the first row shows it before any step has formed it)
+    load_params<F>(a.c, i, p);
+    derive<F>(p, d);
+    const bool gen_instant = genset_wave_is_instant<F>(p, s);
+    const bool ar_on = a.ar_mode != 0;
+    int32_t off = a.ep_off[i], fin = a.ep_final[i];
+    GridFactors f;
+    f.lr = 0.0; f.pr = 0.0; f.lp = 0u; f.pp = 0u; f.cp = 0u; f.pat = 0u;
+    if constexpr (SRC == EP_SRC_FACT) load_factors<F>(a.c, i, f);
+    RowBounds<F> rb;
+    load_row_bounds<F>(a.c, N, i, rb);
+    double run = es.ret_running ? es.ret_running[i] : 0.0;
+    double sum = es.ret_sum ? es.ret_sum[i] : 0.0;
+    double last = es.ret_last ? es.ret_last[i] : 0.0;
+    int32_t eps = es.episodes ? es.episodes[i] : 0;
+    {
+        const bool GI = gen_instant;
+        RowSlot ring[U];
+#pragma unroll
+        for (int u = 0; u < U; u++)
+            if (u <= K) fetch_row_slot<F, SRC>(a, f, i, t0 + u, off, ring[u]);
+        int64_t o64 = i;
+        int64_t r64 = i * D - N * D;               // element offset of row (k - 1, i) of obs; + N * D: row (k, i) of final_obs
+#pragma nounroll
+        for (int32_t k = 0; k < K; k++) {
+            const int32_t t = t0 + k;
+            asm volatile("" : "+s"(desc));             // (opaque: the fields are taken out where a row is built, every step)
+            asm volatile("" : "+s"(dims));
+            Inputs in;
+            widen_row_slot<F, SRC>(a, f, ring[0], t, off, in);
+            uint32_t word;
+            {
+                double x[D], y[NO];
+                policy_row<F>(late->a_dev, a.T, desc, i, t + off, in, rb, p, s, tile, x);
+                if (obs && k > 0) emit_policy_row<D>(desc, obs, r64, tile);
+                policy_outputs<D, NO>(my_set, (int32_t)(dims & 0xffu), (int32_t)((dims >> 8) & 0xffu), x, y);
+                const int32_t id = policy_argmax<NO>(y, (int32_t)(dims >> 16));
+                word = word_of_id[id];
+                if (ids_out) ids_out[o64] = (uint8_t)id;
+            }
+#pragma unroll
+            for (int u = 0; u + 1 < U; u++) ring[u] = ring[u + 1];
+            double bat_q;
+            uint32_t xv = 0u;
+            populate_core<F, false>(p, s, word, in, bat_q, 0.0 + -1 * in.load, in.pv, GI, &xv);
+            Outputs o;
+            step_core<F, true>(p, d, s, in, false, true, GI, o, bat_q);
+            const double r = shaped_reward<F>(a.shaper, o);
+            const bool dn = t >= fin - 1;                       // done_at(a, i, t)
+            if (out.reward) out.reward[o64] = r;
+            if (out.done) out.done[o64] = (uint8_t)dn;
+            if constexpr (F & F_BATTERY) { if (out.soc_trace) out.soc_trace[o64] = s.soc; }
+            if constexpr (F & F_GENSET) { if (out.status_trace) out.status_trace[o64] = s.status; }
+            o64 += N;
+            r64 += N * D;
+            run += r;
+            if (t == fin - 1) { last = run; sum += run; eps += 1; run = 0.0; }
+            if (ar_on && dn) {
+                const KArgs *__restrict__ a_dev = late->a_dev;
+                if (want_final) {                               // the row of the episode that ends here: slot 0, still the old rows
+                    Inputs inf;
+                    widen_row_slot<F, SRC>(a, f, ring[0], t + 1, off, inf);
+                    store_final_row<F>(a_dev, a.T, desc, late->final_obs, r64, i, t + 1 + off, inf, rb, p, s);
+                }
+                // (the arguments of the draw out of the handle's device copy of the KArgs, read here, in the branch)
+                off = episode_auto_restart(*a_dev, i, t, off, true);
+                fin = a_dev->ep_final[i];
+                // slot v now stands for step k + 1 + v: all of them again, at the rows of the new episode
+#pragma unroll
+                for (int v = 0; v < U; v++)
+                    if (k + 1 + v <= K) fetch_row_slot<F, SRC>(a, f, i, t + 1 + v, off, ring[v]);
+            } else if (k + U <= K) {
+                fetch_row_slot<F, SRC>(a, f, i, t + U, off, ring[U - 1]);
+            }
+        }
+        if (obs) {                                              // the row the last step returned
+            Inputs inn;
+            double x[D];
+            widen_row_slot<F, SRC>(a, f, ring[0], t0 + K, off, inn);
+            policy_row<F>(late->a_dev, a.T, desc, i, t0 + K + off, inn, rb, p, s, tile, x);
+            emit_policy_row<D>(desc, obs, r64, tile);
+        }
+    }
+    store_state<F>(late->a_dev->c, i, s);     // (the same columns; their addresses need no scalar registers across the loop)
+    // (the statistics' addresses a second time, from the kernarg segment: the first copies ended their lives before the loop)
+    if (double *q = late->es.ret_running) q[i] = run;
+    if (double *q = late->es.ret_sum) q[i] = sum;
+    if (double *q = late->es.ret_last) q[i] = last;
+    if (int32_t *q = late->es.episodes) q[i] = eps;
+}
+
+template <int F>
+static void rollout_policy_episodes_dispatch(const EpisodePolicyLaunch &P)
+{
+    const EpisodeLaunch &L = P.r.e;
+    // ring depth as rollout_episodes_kernel's
+    const RolloutPolicyArgs g{*L.k, *L.tab, P.pol, L.t, L.K, L.out, L.stats, L.gpb, pack_row_desc(*L.k), L.k_dev, P.r.obs, P.r.final_obs,
+                              (uint8_t *)P.actions_out};
+#define MGX_EPISODES(SRC) rollout_policy_episodes_kernel<F, (F & F_GRID) ? 4 : MGX_RING_ROLLOUT, SRC><<<L.blocks, BLOCK_K, P.lds_bytes, L.stream>>>(g)
+    if (L.src == EP_SRC_FACT) MGX_EPISODES(EP_SRC_FACT);
+    else if (L.src == EP_SRC_GRID_MAJOR) MGX_EPISODES(EP_SRC_GRID_MAJOR);
+    else MGX_EPISODES(EP_SRC_GATHER);
+#undef MGX_EPISODES
+}
+
+bool MGX_CAT(launch_rollout_policy_episodes_p, MGX_POLICY_EPISODE_PART)(const EpisodePolicyLaunch &P)
+{
+    switch (P.r.e.flags) {
+#define X(FV) case FV: rollout_policy_episodes_dispatch<FV>(P); return true;
+        MGX_PART_FLAGS(X)
+#undef X
+        default: return false;
+    }
+}
+
+}  // namespace mgx

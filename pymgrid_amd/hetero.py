@@ -724,12 +724,16 @@ class PerGridWindowEnv:
             return "observation_keys: the launch writes whole rows (select the columns from them, or take single steps)"
         return None
 
-    def _check_fused(self, kind, want_rows):
-        """Refuse ``rollout`` / ``step_k`` (``kind``) where this env does not offer it, or not with observation rows."""
+    def _check_fused(self, kind, want_rows, policy=False):
+        """Refuse ``rollout`` / ``step_k`` (``kind``) where this env does not offer it, or not with observation rows.  ``policy``: the
+        call is ``rollout_policy`` / ``step_k_policy``, which reads the rows whether or not it writes them."""
+        name = kind + "_policy" if policy else kind
         why = self._fused_refusal(kind)
         if why is not None:
-            raise ValueError(f"PerGridWindowEnv.{kind} is not offered with {why}")
+            raise ValueError(f"PerGridWindowEnv.{name} is not offered with {why}")
         why = self._rows_refusal() if want_rows else None
+        if why is not None and policy:
+            raise ValueError(f"PerGridWindowEnv.{name} is not offered with {why} -- the policy reads whole rows without a forecast")
         if why is not None:
             raise ValueError(f"PerGridWindowEnv.{kind} writes no observations with {why}")
 
@@ -805,6 +809,52 @@ class PerGridWindowEnv:
         e._check_actions(actions, (int(actions.shape[0]),))
         return self._launch_fused(lambda **kw: e.step_k_episodes(actions, normalized=normalized, **kw), observations, final_observations,
                                   reward=reward, done=done, soc_trace=soc_trace, status_trace=status_trace, out=out)
+
+    def _check_policy(self, kind, policy, head, n_out, what):
+        """What ``rollout_policy`` / ``step_k_policy`` refuse on top of ``rollout`` / ``step_k`` with rows: a policy of the wrong head
+        or the wrong size."""
+        e = self.env.engine
+        if getattr(policy, "head", None) != head:
+            raise ValueError(f"PerGridWindowEnv.{kind}_policy takes an MLPPolicy with head={head!r}")
+        if policy.n_in != e.obs_dim:
+            raise ValueError(f"the policy reads rows of {policy.n_in} columns, the env's observation rows hold {e.obs_dim}")
+        if policy.n_out != n_out:
+            raise ValueError(f"the policy has {policy.n_out} outputs, {what} {n_out}")
+        if policy.policy_index is not None and policy.policy_index.shape[0] != e.N:
+            raise ValueError(f"policy_index names {policy.policy_index.shape[0]} grids, the env {e.N}")
+        if self.starts is None:
+            raise RuntimeError(f"{kind}_policy() before reset()")
+
+    def rollout_policy(self, policy, K, reward=True, done=False, soc_trace=False, status_trace=False, actions=False,
+                       observations=False, final_observations=False, out=None):
+        """``rollout`` with the loop CLOSED inside the launch (``mgx_rollout_policy_episodes``; ``discrete=True``): the id of every step
+        is ``policy`` (``pymgrid_amd.policy.MLPPolicy``, ``head="discrete"``, one output per priority list) applied to the
+        observation the grid's last step -- or reset, or restart inside the launch -- returned, in the env's ``obs_dtype``.  K steps
+        leave exactly what K times ``ids = policy.act(obs); obs, r, done, _ = step(ids)`` leave, bit for bit; ``actions=True`` also
+        returns the ids taken (uint8 ``[K, N]``), which the open-loop ``rollout`` replays.  The other outputs, ``episode_stats``,
+        ``observations`` / ``final_observations`` and ``out=`` as for ``rollout``.  Needs what ``rollout`` with observations needs: no
+        forecast horizon, no ``observation_keys``."""
+        env = self.env
+        self._check_fused("rollout", True, policy=True)
+        self._check_policy("rollout", policy, "discrete", int(np.asarray(env._table).shape[0]), "the env's priority-list table")
+        return self._launch_fused(lambda **kw: env.engine.rollout_policy_episodes(policy, env._table, int(K), **kw), observations,
+                                  final_observations, reward=reward, done=done, soc_trace=soc_trace, status_trace=status_trace,
+                                  actions=actions, out=out)
+
+    def step_k_policy(self, policy, K, reward=True, done=False, soc_trace=False, status_trace=False, actions=False,
+                      observations=False, final_observations=False, out=None):
+        """``step_k`` with the loop CLOSED inside the launch (``mgx_step_k_policy_episodes``; ``discrete=False``, float64 controls):
+        the controls of every step are ``policy`` (``MLPPolicy``, ``head="continuous"``, one output per action column) applied to the
+        observation the grid's last step returned, stepped as ``step(u, normalized=True)``.  K steps leave exactly what K times
+        ``u = policy.act(obs); obs, r, done, _ = step(u)`` leave, bit for bit; ``actions=True`` also returns the controls taken
+        (float64 ``[K, N, A]``), which the open-loop ``step_k`` replays.  Everything else as ``rollout_policy``."""
+        e = self.env.engine
+        self._check_fused("step_k", True, policy=True)
+        self._check_policy("step_k", policy, "continuous", e.action_dim, "the layout's action columns")
+        if e.action_dtype != torch.float64:
+            raise ValueError("PerGridWindowEnv.step_k_policy is not offered with action_dtype=float32: the policy's controls are float64")
+        return self._launch_fused(lambda **kw: e.step_k_policy_episodes(policy, int(K), **kw), observations, final_observations,
+                                  reward=reward, done=done, soc_trace=soc_trace, status_trace=status_trace, actions=actions, out=out)
 
     def _next_final_buf(self):
         """One of FINAL_BUFFERS rotating [N, D] buffers for ``info["final_observation"]`` (valid for FINAL_BUFFERS - 1 further steps)."""

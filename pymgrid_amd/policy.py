@@ -1,0 +1,171 @@
+"""The policy of the closed-loop fused launches (``mgx_rollout_policy_episodes`` / ``mgx_step_k_policy_episodes``,
+``PerGridWindowEnv.rollout_policy`` / ``step_k_policy``): a small float64 network of plain IEEE operations, evaluated inside the
+launch on the observation row every grid stands on.  ``MLPPolicy.act`` states the same rule with torch operations, one multiply
+and one add at a time in the order the kernels take them, so a host loop ``a = policy.act(obs); obs, r, done, _ = env.step(a)``
+reproduces every decision of a fused launch bit for bit (the rule: ``include/mgx.h``, ``mgx_policy``)."""
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import _lib
+
+MAX_IN = 12                 # columns of an H = 0 observation row, at most
+MAX_ACTIONS = 12            # rows of a priority-list table, at most (the discrete head)
+MAX_CONTROLS = 4            # action columns of a layout with one module of every kind, at most (the continuous head)
+
+
+def _f64(name, a, ndim):
+    """``a`` (torch or numpy, float64) with a leading population axis: [P, ...] of ``ndim`` dimensions."""
+    if a is None:
+        return None
+    t = a if torch.is_tensor(a) else torch.as_tensor(np.asarray(a))
+    if t.dtype != torch.float64:
+        raise ValueError(f"{name} must be float64 (the policy is evaluated in float64 on host and device), not {t.dtype}")
+    if t.dim() == ndim - 1:
+        t = t.unsqueeze(0)
+    if t.dim() != ndim:
+        raise ValueError(f"{name} must have {ndim - 1} dimensions, or {ndim} with the population axis first; it has shape {tuple(t.shape)}")
+    return t.contiguous()
+
+
+class MLPPolicy:
+    """``y = W2 . relu(W1 . x + b1) + b2`` (``W1 = b1 = None``: the linear policy ``y = W2 . x + b2``) on the observation row ``x``,
+    every sum taken in index order with a separate multiply and add; ``relu(h) = h if h > 0 else +0.0``.
+
+    ``head="discrete"``: the action is the lowest ``o`` whose ``y[o]`` is strictly greater than everything before it, starting from
+    ``-inf`` -- ties go to the lowest index, a NaN never wins, all-NaN is id 0; ``n_out`` is the number of rows of the env's
+    priority-list table.  ``head="continuous"``: ``u[o] = 0 if not y[o] > 0 else min(y[o], 1)``, normalised controls in the order of
+    ``layout.action_names``.
+
+    Shapes: ``W1 [n_hidden, n_in]``, ``b1 [n_hidden]``, ``W2 [n_out, n_hidden or n_in]``, ``b2 [n_out]`` -- or each with a leading
+    population axis ``P``; ``policy_index`` (int32 ``[N]``) then names the parameter set of every grid (absent: set 0 for all; an
+    index outside ``[0, P)``: set 0).  All parameters are float64."""
+
+    def __init__(self, W1, b1, W2, b2, policy_index=None, head="discrete"):
+        if head not in ("discrete", "continuous"):
+            raise ValueError(f"head must be 'discrete' or 'continuous', not {head!r}")
+        self.head = head
+        if (W1 is None) != (b1 is None):
+            raise ValueError("W1 and b1 come together (both None: a linear policy)")
+        self.W1, self.b1 = _f64("W1", W1, 3), _f64("b1", b1, 2)
+        self.W2, self.b2 = _f64("W2", W2, 3), _f64("b2", b2, 2)
+        if self.W2 is None or self.b2 is None:
+            raise ValueError("W2 and b2 are required")
+        P, n_out, n_mid = self.W2.shape
+        self.n_policies, self.n_out = int(P), int(n_out)
+        if self.W1 is not None:
+            self.n_hidden, self.n_in = int(self.W1.shape[1]), int(self.W1.shape[2])
+            if self.n_hidden < 1:
+                raise ValueError("W1 holds no hidden unit (a linear policy: W1 = b1 = None)")
+            if tuple(self.W1.shape) != (P, n_mid, self.n_in) or tuple(self.b1.shape) != (P, self.n_hidden):
+                raise ValueError(f"W1 {tuple(self.W1.shape)} / b1 {tuple(self.b1.shape)} do not fit W2 {tuple(self.W2.shape)}: "
+                                 f"W1 [P, n_hidden, n_in], b1 [P, n_hidden], W2 [P, n_out, n_hidden]")
+        else:
+            self.n_hidden, self.n_in = 0, int(n_mid)
+        if tuple(self.b2.shape) != (P, n_out):
+            raise ValueError(f"b2 {tuple(self.b2.shape)} does not fit W2 {tuple(self.W2.shape)}: b2 [P, n_out]")
+        if P < 1:
+            raise ValueError("an empty population")
+        if not 1 <= self.n_in <= MAX_IN:
+            raise ValueError(f"n_in = {self.n_in}: an observation row without a forecast holds 1 to {MAX_IN} columns")
+        if self.n_hidden > _lib.POLICY_MAX_HIDDEN:
+            raise ValueError(f"n_hidden = {self.n_hidden}: at most {_lib.POLICY_MAX_HIDDEN} (MGX_POLICY_MAX_HIDDEN)")
+        if head == "discrete" and not 1 <= self.n_out <= MAX_ACTIONS:
+            raise ValueError(f"n_out = {self.n_out}: a priority-list table holds 1 to {MAX_ACTIONS} actions")
+        if head == "continuous" and self.n_out > MAX_CONTROLS:
+            raise ValueError(f"n_out = {self.n_out}: a layout has at most {MAX_CONTROLS} action columns")
+        if self.lds_bytes > _lib.POLICY_LDS_BYTES:
+            raise ValueError(f"{P} parameter sets take {self.lds_bytes} bytes where the kernels keep them, at most "
+                             f"{_lib.POLICY_LDS_BYTES} (MGX_POLICY_LDS_BYTES)")
+        devices = {t.device for t in (self.W1, self.b1, self.W2, self.b2) if t is not None}
+        if len(devices) != 1:
+            raise ValueError(f"the parameters lie on different devices: {sorted(map(str, devices))}")
+        self.policy_index = None
+        if policy_index is not None:
+            idx = policy_index if torch.is_tensor(policy_index) else torch.as_tensor(np.asarray(policy_index))
+            if idx.dtype != torch.int32 or idx.dim() != 1:
+                raise ValueError(f"policy_index must be an int32 vector [N], not {idx.dtype} {tuple(idx.shape)}")
+            self.policy_index = idx.contiguous()
+
+    @property
+    def lds_bytes(self):
+        """Bytes of the parameter sets as the kernels stage them (include/mgx.h, MGX_POLICY_LDS_BYTES)."""
+        m = (self.n_out + 3) // 4 * 4 if self.head == "discrete" else self.n_out
+        per_set = m + (self.n_hidden * (self.n_in + 1 + m) if self.n_hidden else self.n_in * m)
+        return self.n_policies * ((per_set + 1) // 2 * 2) * 8
+
+    def to(self, device):
+        """The policy with its parameters on ``device``: ``self`` where they already lie there, else a COPY made now.  Nothing is
+        cached -- numpy parameters share their memory with the caller's arrays, so a search loop may update them in place between
+        launches and ``act`` and every fused launch see the current values (the launch copies them to the device each time; keep
+        the parameters on the device, as torch tensors, to avoid the copy)."""
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        if self.W2.device == device and (self.policy_index is None or self.policy_index.device == device):
+            return self
+        mv = lambda t: None if t is None else t.to(device)     # noqa: E731
+        return MLPPolicy(mv(self.W1), mv(self.b1), mv(self.W2), mv(self.b2), mv(self.policy_index), head=self.head)
+
+    def _sets(self, n, device):
+        """None (one set for all grids) or the long index [n] of every grid's set, out-of-range indices mapped to 0."""
+        if self.policy_index is None:
+            return None
+        idx = self.policy_index.to(device).long()
+        if idx.shape[0] != n:
+            raise ValueError(f"policy_index names {idx.shape[0]} grids, the observations {n}")
+        return torch.where((idx >= 0) & (idx < self.n_policies), idx, torch.zeros_like(idx))
+
+    @staticmethod
+    def _layer(W, b, idx, v):
+        """[N, O]: b + sum over j in order of W[..., j] * v[:, j], one multiply and one add at a time."""
+        if idx is None:
+            Wn, acc = W[0].unsqueeze(0), b[0].unsqueeze(0).expand(v.shape[0], -1)
+        else:
+            Wn, acc = W[idx], b[idx]
+        for j in range(W.shape[2]):
+            acc = acc + Wn[:, :, j] * v[:, j:j + 1]
+        return acc
+
+    def outputs(self, obs):
+        """``y`` [N, n_out] for observation rows ``obs`` [N, n_in] (float32 rows are widened to float64, not re-rounded)."""
+        if not torch.is_tensor(obs):
+            obs = torch.as_tensor(np.asarray(obs))
+        if obs.dim() != 2 or obs.shape[1] != self.n_in or obs.dtype not in (torch.float32, torch.float64):
+            raise ValueError(f"obs must be float32 or float64 rows [N, {self.n_in}], not {obs.dtype} {tuple(obs.shape)}")
+        me = self.to(obs.device)
+        x = obs.to(torch.float64)
+        idx = me._sets(x.shape[0], x.device)
+        if me.n_hidden:
+            h = self._layer(me.W1, me.b1, idx, x)
+            x = torch.where(h > 0, h, torch.zeros_like(h))
+        return self._layer(me.W2, me.b2, idx, x)
+
+    def act(self, obs):
+        """The actions for observation rows ``obs`` [N, n_in]: priority-list ids (int32 [N]) or normalised controls (float64
+        [N, n_out]) -- what the fused launches take, bit for bit."""
+        y = self.outputs(obs)
+        if self.head == "continuous":
+            return torch.where(~(y > 0), torch.zeros_like(y), torch.where(y > 1, torch.ones_like(y), y))
+        best = torch.full((y.shape[0],), float("-inf"), dtype=torch.float64, device=y.device)
+        ids = torch.zeros(y.shape[0], dtype=torch.int32, device=y.device)
+        for o in range(self.n_out):
+            m = y[:, o] > best
+            best = torch.where(m, y[:, o], best)
+            ids = torch.where(m, torch.full_like(ids, o), ids)
+        return ids
+
+    def c_struct(self, device, n_grids):
+        """``(mgx_policy, keep-alive)`` with the parameters on ``device``."""
+        me = self.to(device)
+        if me.policy_index is not None and me.policy_index.shape[0] != n_grids:
+            raise ValueError(f"policy_index names {me.policy_index.shape[0]} grids, the env {n_grids}")
+        # (no controllable module, n_out = 0: nothing of W2 / b2 is read, but the C call takes no NULL weights)
+        spare = torch.zeros(1, dtype=torch.float64, device=me.W2.device) if me.n_out == 0 else None
+        ptr = lambda t: None if t is None else (t.data_ptr() if t.numel() else spare.data_ptr())
+        st = _lib.Policy()
+        st.struct_size = C.sizeof(_lib.Policy)
+        st.n_policies, st.n_in, st.n_hidden, st.n_out = me.n_policies, me.n_in, me.n_hidden, me.n_out
+        st.w1, st.b1, st.w2, st.b2, st.policy_index = ptr(me.W1), ptr(me.b1), ptr(me.W2), ptr(me.b2), ptr(me.policy_index)
+        return st, (me, spare)
