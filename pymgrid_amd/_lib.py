@@ -19,14 +19,14 @@ UNITS = (
     ("mgx_abi.hip", None, 1),                                           # the host side + the small kernels
     ("mgx_fused.hip", "MGX_FUSED_PART", 6),                             # MGX_FUSED_PARTS: the K-step kernels
     ("mgx_episodes.hip", "MGX_EPISODE_PART", 2),                        # MGX_EPISODE_PARTS: the roll-out over in-place episodes,
-    ("mgx_step_episodes.hip", "MGX_STEP_EPISODE_PART", 2),              # ... the continuous K-step over them,
-    ("mgx_episode_rows.hip", "MGX_EPISODE_ROWS_PART", 2),               # ... the roll-out with observation rows
-    ("mgx_step_episode_rows.hip", "MGX_STEP_EPISODE_ROWS_PART", 2),     # ... and its continuous twin,
-    ("mgx_policy_episodes.hip", "MGX_POLICY_EPISODE_PART", 2),          # ... the closed-loop roll-out (a policy inside the launch)
-    ("mgx_step_policy_episodes.hip", "MGX_STEP_POLICY_EPISODE_PART", 2),    # ... and its continuous twin
+    ("mgx_step_episodes.hip", "MGX_EPISODE_PART", 2),                   # ... the continuous K-step over them,
+    ("mgx_episode_rows.hip", "MGX_EPISODE_PART", 2),                    # ... the roll-out with observation rows
+    ("mgx_step_episode_rows.hip", "MGX_EPISODE_PART", 2),               # ... and its continuous twin,
+    ("mgx_policy_episodes.hip", "MGX_EPISODE_PART", 2),                 # ... the closed-loop roll-out (a policy inside the launch)
+    ("mgx_step_policy_episodes.hip", "MGX_EPISODE_PART", 2),            # ... and its continuous twin
 )
 # everything a built library is stamped with (source_hash): a file missing here would leave a stale libmgx.so looking current
-SOURCES = [os.path.join(_PKG, "csrc", f) for f in [u[0] for u in UNITS] + ["mgx_kernels.hpp", "mgx_core.hpp", "mgx_episode_rows.hpp", "mgx_policy.hpp"]] + \
+SOURCES = [os.path.join(_PKG, "csrc", f) for f in [u[0] for u in UNITS] + ["mgx_kernels.hpp", "mgx_core.hpp", "mgx_episode_loop.hpp", "mgx_episode_rows.hpp", "mgx_policy.hpp"]] + \
           [os.path.join(_ROOT, "include", "mgx.h")]
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-fPIC"]

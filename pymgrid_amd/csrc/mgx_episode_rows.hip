@@ -1,16 +1,8 @@
 // mgx_episode_rows.hip -- the fused discrete roll-out over per-grid in-place episodes WITH observation rows
 // (mgx_rollout_episodes_rows): rollout_episodes_kernel (mgx_episodes.hip) + per step the H = 0 row the step returned and, where a
-// grid restarts, the row before the restart.  Translation units of their own (MGX_EPISODE_PARTS slices of the layouts):
-//   hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -c -DMGX_EPISODE_ROWS_PART=p mgx_episode_rows.hip -o mgx_episode_rows_p.o
-// so every other kernel comes out of the compiler exactly as it did without this file.
+// grid restarts, the row before the restart.  One of the six translation units of mgx_episode_loop.hpp, which states what their
+// loops share and how a unit is compiled; what the rows add is in mgx_episode_rows.hpp.
 #include "mgx_episode_rows.hpp"
-
-#ifndef MGX_EPISODE_ROWS_PART
-#error "compile with -DMGX_EPISODE_ROWS_PART=<0..MGX_EPISODE_PARTS-1>"
-#endif
-
-// layouts (template parameter F) of this slice: MGX_EPISODE_FLAGS_<part> (mgx_kernels.hpp)
-#define MGX_PART_FLAGS MGX_CAT(MGX_EPISODE_FLAGS_, MGX_EPISODE_ROWS_PART)
 
 namespace mgx {
 
@@ -20,9 +12,8 @@ namespace mgx {
 //                        episode_tail writes through mgx_set_final_obs.  After the rotation ring slot 0 holds exactly that series
 //                        row, until the restart branch reads the slots again.
 //   obs[k, i, :]         the row of series row t + 1 + off_new: ring slot 0 again, under the offset the restart left.
-// Hence the ring here reaches ONE row further than the plain kernel's: row t0 + K (the row after the last step, and the first row
-// of an episode that starts at step K - 1) is fetched too -- guards `<= K` where the plain kernel has `< K`.  episode_row clamps
-// every row to the series, so the extra fetch stays inside it.  The id ring keeps its guard: there is no id row K.
+// Hence the ring here reaches ONE row further than the plain kernel's: K + 1 (the ring's reach, mgx_episode_loop.hpp).  The id ring
+// keeps its guard: there is no id row K.
 // SoC is formed every step (the row shows it).
 // Scalar registers: rollout_episodes_kernel leaves five of them free.  So the arguments come as ONE struct and whatever is not
 // needed inside the loop is read late, through late_kernargs: the statistics' addresses for the write-back, the device copy of the
@@ -63,15 +54,18 @@ __global__ __launch_bounds__(BLOCK_K) void rollout_episodes_rows_kernel(const Ro
     const bool ar_on = a.ar_mode != 0;
     int32_t off = a.ep_off[i], fin = a.ep_final[i];
     uint32_t word = PER_STEP ? 0u : pl_select(tab, ids[i]);
+    // THE RING OF THIS KERNEL IS WRITTEN OUT -- the lane's factors, the ring's fill, rotation and advance and the restart are the text
+    // of load_lane_factors / fill_row_ring / rotate_ring / restart_lane + advance_row_ring (mgx_episode_loop.hpp, reach K + 1), not calls:
+    // on the helpers the form <7, 4, *, GRID_MAJOR> took 4.66 us per step of 100 000 grids at K = 64 against 4.33-4.40 (+6.8 %:
+    // profiles/exp_episode_loop_refactor.txt); the compiler's code differs in a few dozen instructions, which of the pieces costs the time is not isolated.
+    // A change to one of those helpers is made here too.
     GridFactors f;
     f.lr = 0.0; f.pr = 0.0; f.lp = 0u; f.pp = 0u; f.cp = 0u; f.pat = 0u;
     if constexpr (SRC == EP_SRC_FACT) load_factors<F>(a.c, i, f);
     RowBounds<F> rb;
     load_row_bounds<F>(a.c, N, i, rb);
-    double run = es.ret_running ? es.ret_running[i] : 0.0;
-    double sum = es.ret_sum ? es.ret_sum[i] : 0.0;
-    double last = es.ret_last ? es.ret_last[i] : 0.0;
-    int32_t eps = es.episodes ? es.episodes[i] : 0;
+    LaneStats st;
+    st.load(es, i);
     {
         const bool GI = gen_instant;
         RowSlot ring[U];
@@ -108,13 +102,9 @@ __global__ __launch_bounds__(BLOCK_K) void rollout_episodes_rows_kernel(const Ro
             step_core<F, true>(p, d, s, in, false, true, GI, o, bat_q);
             const double r = shaped_reward<F>(a.shaper, o);
             const bool dn = t >= fin - 1;                       // done_at(a, i, t)
-            if (out.reward) out.reward[o64] = r;
-            if (out.done) out.done[o64] = (uint8_t)dn;
-            if constexpr (F & F_BATTERY) { if (out.soc_trace) out.soc_trace[o64] = s.soc; }
-            if constexpr (F & F_GENSET) { if (out.status_trace) out.status_trace[o64] = s.status; }
+            store_step_outputs<F>(out, o64, r, dn, s);
             o64 += N;
-            run += r;
-            if (t == fin - 1) { last = run; sum += run; eps += 1; run = 0.0; }
+            st.update(r, t, fin);
             if (ar_on && dn) {
                 const KArgs *__restrict__ a_dev = late->a_dev;
                 if (want_final) {                               // the row of the episode that ends here: slot 0, still the old rows
@@ -122,10 +112,8 @@ __global__ __launch_bounds__(BLOCK_K) void rollout_episodes_rows_kernel(const Ro
                     widen_row_slot<F, SRC>(a, f, ring[0], t + 1, off, inf);
                     store_final_row<F>(a_dev, a.T, desc, late->final_obs, r64, i, t + 1 + off, inf, rb, p, s);
                 }
-                // (the arguments of the draw out of the handle's device copy of the KArgs, read here, in the branch)
                 off = episode_auto_restart(*a_dev, i, t, off, true);
                 fin = a_dev->ep_final[i];
-                // slot v now stands for step k + 1 + v: all of them again, at the rows of the new episode
 #pragma unroll
                 for (int v = 0; v < U; v++)
                     if (k + 1 + v <= K) fetch_row_slot<F, SRC>(a, f, i, t + 1 + v, off, ring[v]);
@@ -142,39 +130,21 @@ __global__ __launch_bounds__(BLOCK_K) void rollout_episodes_rows_kernel(const Ro
     }
     store_state<F>(late->a_dev->c, i, s);     // (the same columns; their addresses need no scalar registers across the loop)
     // (the statistics' addresses a second time, from the kernarg segment: the first copies ended their lives before the loop)
-    if (double *q = late->es.ret_running) q[i] = run;
-    if (double *q = late->es.ret_sum) q[i] = sum;
-    if (double *q = late->es.ret_last) q[i] = last;
-    if (int32_t *q = late->es.episodes) q[i] = eps;
+    st.store(late->es.ret_running, late->es.ret_sum, late->es.ret_last, late->es.episodes, i);
 }
 
 template <int F>
 static void rollout_episodes_rows_dispatch(const EpisodeRowsLaunch &R)
 {
     const EpisodeLaunch &L = R.e;
-    // ring depth as rollout_episodes_kernel's
     const RolloutRowsArgs g{*L.k, *L.tab, L.ids, L.t, L.K, L.out, L.stats, L.gpb, pack_row_desc(*L.k), L.k_dev, R.obs, R.final_obs};
-#define MGX_EPISODES(PS, SRC) rollout_episodes_rows_kernel<F, (F & F_GRID) ? 4 : MGX_RING_ROLLOUT, PS, SRC><<<L.blocks, BLOCK_K, 0, L.stream>>>(g)
-    if (L.per_step) {
-        if (L.src == EP_SRC_FACT) MGX_EPISODES(true, EP_SRC_FACT);
-        else if (L.src == EP_SRC_GRID_MAJOR) MGX_EPISODES(true, EP_SRC_GRID_MAJOR);
-        else MGX_EPISODES(true, EP_SRC_GATHER);
-    } else {
-        if (L.src == EP_SRC_FACT) MGX_EPISODES(false, EP_SRC_FACT);
-        else if (L.src == EP_SRC_GRID_MAJOR) MGX_EPISODES(false, EP_SRC_GRID_MAJOR);
-        else MGX_EPISODES(false, EP_SRC_GATHER);
-    }
-#undef MGX_EPISODES
+    with_episode_src(L.src, [&](auto src) {
+        constexpr int SRC = decltype(src)::value;
+        if (L.per_step) rollout_episodes_rows_kernel<F, ROW_RING<F>, true, SRC><<<L.blocks, BLOCK_K, 0, L.stream>>>(g);
+        else rollout_episodes_rows_kernel<F, ROW_RING<F>, false, SRC><<<L.blocks, BLOCK_K, 0, L.stream>>>(g);
+    });
 }
 
-bool MGX_CAT(launch_rollout_episodes_rows_p, MGX_EPISODE_ROWS_PART)(const EpisodeRowsLaunch &R)
-{
-    switch (R.e.flags) {
-#define X(FV) case FV: rollout_episodes_rows_dispatch<FV>(R); return true;
-        MGX_PART_FLAGS(X)
-#undef X
-        default: return false;
-    }
-}
+MGX_EPISODE_LAUNCH_FN(rollout_episodes_rows, EpisodeRowsLaunch, L.e.flags)
 
 }  // namespace mgx

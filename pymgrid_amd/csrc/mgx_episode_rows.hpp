@@ -1,76 +1,11 @@
-// mgx_episode_rows.hpp -- what the two fused episode launches WITH observation rows share (mgx_rollout_episodes_rows:
-// mgx_episode_rows.hip, mgx_step_k_episodes_rows: mgx_step_episode_rows.hip): the slot of the series-row ring, its fetch and its
-// widening as free functions, the H = 0 row built from series values that are already in registers, and the wave's row tile.
-// A header of its own: mgx_kernels.hpp, mgx_episodes.hip and mgx_step_episodes.hip stay as they are, so every kernel that exists
-// without this file comes out of the compiler exactly as before.
+// mgx_episode_rows.hpp -- what the fused episode launches that build observation rows add to mgx_episode_loop.hpp
+// (mgx_rollout_episodes_rows: mgx_episode_rows.hip, mgx_step_k_episodes_rows: mgx_step_episode_rows.hip, and the two closed-loop
+// launches of mgx_policy.hpp): the H = 0 row built from series values that are already in registers, the wave's row tile, the
+// kernel arguments read late and the one-struct arguments of the two kernels.
 #pragma once
-#include "mgx_kernels.hpp"
+#include "mgx_episode_loop.hpp"
 
 namespace mgx {
-
-// What a slot of the row ring holds until its step consumes it: the raw values of one series row of the lane's grid.
-// SRC = EP_SRC_FACT: the base-table values + the 64-row outage word of the row (ratios, tariff and status bit are applied when the
-// slot is widened).  Materialised series: the row itself.
-struct RowSlot {
-    double load, pv, g_pimp, g_pexp, g_co2, g_stat;
-    uint64_t outage;
-};
-
-// the raw row of counter value t under the lane's offset `off` (the rows of EP_SRC_*: rollout_episodes_kernel)
-template <int F, int SRC>
-__device__ __forceinline__ void fetch_row_slot(const KArgs &a, const GridFactors &f, int64_t i, int32_t t, int32_t off, RowSlot &r)
-{
-    const int64_t N = a.N;
-    const int32_t pm = a.pm_pitch;
-    const int64_t row = episode_row(a, t, off);
-    if constexpr (SRC == EP_SRC_FACT) {
-        r.load = a.c.base_load[(int64_t)f.lp * pm + row];
-        r.pv = a.c.base_pv[(int64_t)f.pp * pm + row];
-        if constexpr (F & F_GRID) {
-            r.g_co2 = a.c.base_co2[(int64_t)f.cp * pm + row];
-            r.outage = 0;
-            if (a.c.outage_bits) r.outage = a.c.outage_bits[(row >> 6) * N + i];
-        }
-    } else if constexpr (SRC == EP_SRC_GRID_MAJOR) {
-        // rows of 16 / 48 bytes in a 16-byte aligned copy: whole 16-byte loads
-        constexpr int C = (F & F_GRID) ? 6 : 2;
-        const double2 *q = reinterpret_cast<const double2 *>(a.c.load_ts + (i * pm + row) * C);
-        const double2 v0 = q[0];
-        r.load = v0.x; r.pv = v0.y;
-        if constexpr (F & F_GRID) {
-            const double2 v1 = q[1], v2 = q[2];
-            r.g_pimp = v1.x; r.g_pexp = v1.y; r.g_co2 = v2.x; r.g_stat = v2.y;
-        }
-    } else {
-        r.load = a.c.load_ts[row * N + i];
-        r.pv = a.c.pv_ts[row * N + i];
-        if constexpr (F & F_GRID) {
-            const double *g = a.c.grid_ts + (row * 4) * N + i;
-            r.g_pimp = g[0]; r.g_pexp = g[N]; r.g_co2 = g[2 * N]; r.g_stat = g[3 * N];
-        }
-    }
-}
-
-// ... and the series values out of it: what fact_series / load_series_row give a single step and what series_component gives
-// observe_row_h0 (the same operations on the same operands)
-template <int F, int SRC>
-__device__ __forceinline__ void widen_row_slot(const KArgs &a, const GridFactors &f, const RowSlot &r, int32_t t, int32_t off, Inputs &in)
-{
-    in.g_stat = 1.0;
-    if constexpr (SRC == EP_SRC_FACT) {
-        in.load = fact_load(r.load, f.lr);
-        in.pv = fact_pv(r.pv, f.pr);
-        if constexpr (F & F_GRID) {
-            const int64_t row = episode_row(a, t, off);
-            in.g_pimp = tariff_price((int32_t)f.pat, (int32_t)row); in.g_pexp = 0.0;
-            in.g_co2 = r.g_co2;
-            in.g_stat = ((r.outage >> (row & 63)) & 1ull) ? 0.0 : 1.0;
-        }
-    } else {
-        in.load = r.load; in.pv = r.pv;
-        if constexpr (F & F_GRID) { in.g_pimp = r.g_pimp; in.g_pexp = r.g_pexp; in.g_co2 = r.g_co2; in.g_stat = r.g_stat; }
-    }
-}
 
 // Lower bound and spread of the series columns of an H = 0 row (load, pv, the four grid components): loop-invariant, so the fused
 // kernels hold them in registers -- 4 or 12 doubles -- instead of 4 or 12 loads per step.

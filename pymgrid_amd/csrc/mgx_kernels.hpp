@@ -650,8 +650,8 @@ bool launch_step_k_p3(const FusedLaunch &L); bool launch_step_k_p4(const FusedLa
 bool launch_rollout_p0(const FusedLaunch &L); bool launch_rollout_p1(const FusedLaunch &L); bool launch_rollout_p2(const FusedLaunch &L);
 bool launch_rollout_p3(const FusedLaunch &L); bool launch_rollout_p4(const FusedLaunch &L);
 // The fused launches over in-place episodes: mgx_rollout_episodes (rollout_episodes_kernel, mgx_episodes.hip) and its continuous twin
-// mgx_step_k_episodes (step_k_episodes_kernel, mgx_step_episodes.hip) -- translation units of their own, so that the lock-step kernels
-// above are compiled exactly as before.  One descriptor serves both: a call fills the fields of its kind and leaves the others unset.
+// mgx_step_k_episodes (step_k_episodes_kernel, mgx_step_episodes.hip) -- translation units of their own (what their loops share:
+// mgx_episode_loop.hpp).  One descriptor serves both: a call fills the fields of its kind and leaves the others unset.
 enum : int { EP_SRC_FACT = 0, EP_SRC_GRID_MAJOR = 1, EP_SRC_GATHER = 2 };    // where a lane finds the rows of its series
 struct EpisodeLaunch {
     int flags;                       // layout (template parameter F)
@@ -671,8 +671,8 @@ struct EpisodeLaunch {
     FusedOut out;                    // (ret_acc and log stay NULL)
     mgx_episode_stats stats;
 };
-// Each of the four translation units (those two and their forms with rows, mgx_episode_rows.hpp) is compiled in MGX_EPISODE_PARTS
-// slices of the layouts (template parameter F); together: 0..7, 14, 15 (MGX_DISPATCH_F in mgx_abi.hip)
+// Those two units, their forms with rows (mgx_episode_rows.hpp) and with a policy (mgx_policy.hpp) are compiled in MGX_EPISODE_PARTS
+// slices of the layouts (template parameter F, -DMGX_EPISODE_PART=p); together: 0..7, 14, 15 (MGX_DISPATCH_F in mgx_abi.hip)
 constexpr int MGX_EPISODE_PARTS = 2;
 #define MGX_EPISODE_FLAGS_0(X) X(0) X(1) X(2) X(3) X(4) X(5)
 #define MGX_EPISODE_FLAGS_1(X) X(6) X(7) X(14) X(15)

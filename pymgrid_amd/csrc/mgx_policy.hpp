@@ -3,8 +3,7 @@
 // operations) staged in LDS once per workgroup and evaluated per lane between "row of the coming step" and "step", and the
 // lane's row strip -- the H = 0 row is built ONCE per step into the wave's tile, read back as the policy's input and, where
 // the launch returns observations, streamed out of the same tile as the row the step before returned.
-// A header of its own on top of mgx_episode_rows.hpp, which stays as it is: every kernel that exists without this file comes out
-// of the compiler exactly as before.
+// On top of mgx_episode_rows.hpp (the rows) and, through it, mgx_episode_loop.hpp (what all six episode loops share).
 #pragma once
 #include "mgx_episode_rows.hpp"
 

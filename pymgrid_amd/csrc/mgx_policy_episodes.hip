@@ -1,17 +1,8 @@
 // mgx_policy_episodes.hip -- the CLOSED-LOOP fused discrete roll-out over per-grid in-place episodes (mgx_rollout_policy_episodes):
 // rollout_episodes_rows_kernel (mgx_episode_rows.hip) with the priority-list id of every step chosen inside the launch, by the
-// policy of include/mgx.h applied to the row the grid stands on.  Translation units of their own (MGX_EPISODE_PARTS slices of the
-// layouts):
-//   hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -c -DMGX_POLICY_EPISODE_PART=p mgx_policy_episodes.hip -o mgx_policy_episodes_p.o
-// so every other kernel comes out of the compiler exactly as it did without this file.
+// policy of include/mgx.h applied to the row the grid stands on.  One of the six translation units of mgx_episode_loop.hpp, which
+// states what their loops share and how a unit is compiled; what the rows add is in mgx_episode_rows.hpp, the policy in mgx_policy.hpp.
 #include "mgx_policy.hpp"
-
-#ifndef MGX_POLICY_EPISODE_PART
-#error "compile with -DMGX_POLICY_EPISODE_PART=<0..MGX_EPISODE_PARTS-1>"
-#endif
-
-// layouts (template parameter F) of this slice: MGX_EPISODE_FLAGS_<part> (mgx_kernels.hpp)
-#define MGX_PART_FLAGS MGX_CAT(MGX_EPISODE_FLAGS_, MGX_POLICY_EPISODE_PART)
 
 namespace mgx {
 
@@ -57,15 +48,19 @@ __global__ __launch_bounds__(BLOCK_K) void rollout_policy_episodes_kernel(const 
     const bool gen_instant = genset_wave_is_instant<F>(p, s);
     const bool ar_on = a.ar_mode != 0;
     int32_t off = a.ep_off[i], fin = a.ep_final[i];
+    // THE RING OF THIS KERNEL IS WRITTEN OUT -- the lane's factors, the ring's fill, rotation and advance and the restart are the text
+    // of load_lane_factors / fill_row_ring / rotate_ring / restart_lane + advance_row_ring (mgx_episode_loop.hpp, reach K + 1), not calls:
+    // under restart_lane or advance_row_ring this kernel takes more accumulation registers (forms <7 | 15, 4, GRID_MAJOR | GATHER>: 47 -> 48
+    // AGPRs, <4, 4, ...>: 2 -> 4, <3, 8, FACT>: 5 -> 6; by value and split in two likewise), and on the other helpers <7, 4, *> with 16 hidden units
+    // took 23.45 us per step of 100 000 grids against 23.15-23.25 (+1.1 %: profiles/exp_episode_loop_refactor.txt).
+    // A change to one of those helpers is made here too.
     GridFactors f;
     f.lr = 0.0; f.pr = 0.0; f.lp = 0u; f.pp = 0u; f.cp = 0u; f.pat = 0u;
     if constexpr (SRC == EP_SRC_FACT) load_factors<F>(a.c, i, f);
     RowBounds<F> rb;
     load_row_bounds<F>(a.c, N, i, rb);
-    double run = es.ret_running ? es.ret_running[i] : 0.0;
-    double sum = es.ret_sum ? es.ret_sum[i] : 0.0;
-    double last = es.ret_last ? es.ret_last[i] : 0.0;
-    int32_t eps = es.episodes ? es.episodes[i] : 0;
+    LaneStats st;
+    st.load(es, i);
     {
         const bool GI = gen_instant;
         RowSlot ring[U];
@@ -100,14 +95,10 @@ __global__ __launch_bounds__(BLOCK_K) void rollout_policy_episodes_kernel(const 
             step_core<F, true>(p, d, s, in, false, true, GI, o, bat_q);
             const double r = shaped_reward<F>(a.shaper, o);
             const bool dn = t >= fin - 1;                       // done_at(a, i, t)
-            if (out.reward) out.reward[o64] = r;
-            if (out.done) out.done[o64] = (uint8_t)dn;
-            if constexpr (F & F_BATTERY) { if (out.soc_trace) out.soc_trace[o64] = s.soc; }
-            if constexpr (F & F_GENSET) { if (out.status_trace) out.status_trace[o64] = s.status; }
+            store_step_outputs<F>(out, o64, r, dn, s);
             o64 += N;
             r64 += N * D;
-            run += r;
-            if (t == fin - 1) { last = run; sum += run; eps += 1; run = 0.0; }
+            st.update(r, t, fin);
             if (ar_on && dn) {
                 const KArgs *__restrict__ a_dev = late->a_dev;
                 if (want_final) {                               // the row of the episode that ends here: slot 0, still the old rows
@@ -115,10 +106,8 @@ __global__ __launch_bounds__(BLOCK_K) void rollout_policy_episodes_kernel(const 
                     widen_row_slot<F, SRC>(a, f, ring[0], t + 1, off, inf);
                     store_final_row<F>(a_dev, a.T, desc, late->final_obs, r64, i, t + 1 + off, inf, rb, p, s);
                 }
-                // (the arguments of the draw out of the handle's device copy of the KArgs, read here, in the branch)
                 off = episode_auto_restart(*a_dev, i, t, off, true);
                 fin = a_dev->ep_final[i];
-                // slot v now stands for step k + 1 + v: all of them again, at the rows of the new episode
 #pragma unroll
                 for (int v = 0; v < U; v++)
                     if (k + 1 + v <= K) fetch_row_slot<F, SRC>(a, f, i, t + 1 + v, off, ring[v]);
@@ -136,34 +125,20 @@ __global__ __launch_bounds__(BLOCK_K) void rollout_policy_episodes_kernel(const 
     }
     store_state<F>(late->a_dev->c, i, s);     // (the same columns; their addresses need no scalar registers across the loop)
     // (the statistics' addresses a second time, from the kernarg segment: the first copies ended their lives before the loop)
-    if (double *q = late->es.ret_running) q[i] = run;
-    if (double *q = late->es.ret_sum) q[i] = sum;
-    if (double *q = late->es.ret_last) q[i] = last;
-    if (int32_t *q = late->es.episodes) q[i] = eps;
+    st.store(late->es.ret_running, late->es.ret_sum, late->es.ret_last, late->es.episodes, i);
 }
 
 template <int F>
 static void rollout_policy_episodes_dispatch(const EpisodePolicyLaunch &P)
 {
     const EpisodeLaunch &L = P.r.e;
-    // ring depth as rollout_episodes_kernel's
     const RolloutPolicyArgs g{*L.k, *L.tab, P.pol, L.t, L.K, L.out, L.stats, L.gpb, pack_row_desc(*L.k), L.k_dev, P.r.obs, P.r.final_obs,
                               (uint8_t *)P.actions_out};
-#define MGX_EPISODES(SRC) rollout_policy_episodes_kernel<F, (F & F_GRID) ? 4 : MGX_RING_ROLLOUT, SRC><<<L.blocks, BLOCK_K, P.lds_bytes, L.stream>>>(g)
-    if (L.src == EP_SRC_FACT) MGX_EPISODES(EP_SRC_FACT);
-    else if (L.src == EP_SRC_GRID_MAJOR) MGX_EPISODES(EP_SRC_GRID_MAJOR);
-    else MGX_EPISODES(EP_SRC_GATHER);
-#undef MGX_EPISODES
+    with_episode_src(L.src, [&](auto src) {
+        rollout_policy_episodes_kernel<F, ROW_RING<F>, decltype(src)::value><<<L.blocks, BLOCK_K, P.lds_bytes, L.stream>>>(g);
+    });
 }
 
-bool MGX_CAT(launch_rollout_policy_episodes_p, MGX_POLICY_EPISODE_PART)(const EpisodePolicyLaunch &P)
-{
-    switch (P.r.e.flags) {
-#define X(FV) case FV: rollout_policy_episodes_dispatch<FV>(P); return true;
-        MGX_PART_FLAGS(X)
-#undef X
-        default: return false;
-    }
-}
+MGX_EPISODE_LAUNCH_FN(rollout_policy_episodes, EpisodePolicyLaunch, L.r.e.flags)
 
 }  // namespace mgx

@@ -1,17 +1,9 @@
 // mgx_step_policy_episodes.hip -- the CLOSED-LOOP fused continuous K-step over per-grid in-place episodes
 // (mgx_step_k_policy_episodes): step_k_episodes_rows_kernel (mgx_step_episode_rows.hip) with the normalised controls of every step
 // chosen inside the launch, by the policy of include/mgx.h applied to the row the grid stands on.  The continuous twin of
-// rollout_policy_episodes_kernel (mgx_policy_episodes.hip).  Translation units of their own (MGX_EPISODE_PARTS slices of the layouts):
-//   hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -c -DMGX_STEP_POLICY_EPISODE_PART=p mgx_step_policy_episodes.hip -o mgx_step_policy_episodes_p.o
-// so every other kernel comes out of the compiler exactly as it did without this file.
+// rollout_policy_episodes_kernel (mgx_policy_episodes.hip).  One of the six translation units of mgx_episode_loop.hpp, which states
+// what their loops share and how a unit is compiled; what the rows add is in mgx_episode_rows.hpp, the policy in mgx_policy.hpp.
 #include "mgx_policy.hpp"
-
-#ifndef MGX_STEP_POLICY_EPISODE_PART
-#error "compile with -DMGX_STEP_POLICY_EPISODE_PART=<0..MGX_EPISODE_PARTS-1>"
-#endif
-
-// layouts (template parameter F) of this slice: MGX_EPISODE_FLAGS_<part> (mgx_kernels.hpp)
-#define MGX_PART_FLAGS MGX_CAT(MGX_EPISODE_FLAGS_, MGX_STEP_POLICY_EPISODE_PART)
 
 namespace mgx {
 
@@ -50,15 +42,18 @@ __global__ __launch_bounds__(BLOCK_K) void step_k_policy_episodes_kernel(const S
     const bool gen_instant = genset_wave_is_instant<F>(p, s);
     const bool ar_on = a.ar_mode != 0;
     int32_t off = a.ep_off[i], fin = a.ep_final[i];
+    // THE RING OF THIS KERNEL IS WRITTEN OUT -- the lane's factors, the ring's fill, rotation and advance and the restart are the text
+    // of load_lane_factors / fill_row_ring / rotate_ring / restart_lane + advance_row_ring (mgx_episode_loop.hpp, reach K + 1), not calls:
+    // on the helpers the form <7, 4, GRID_MAJOR> took 2.98 us per step of 100 000 grids at K = 64 against 2.77 (+7.6 %, linear policy;
+    // +4.0 % with 16 hidden units: profiles/exp_episode_loop_refactor.txt) while <7, 4, FACT> gained 2.7 %; which of the pieces moves it is not isolated.
+    // A change to one of those helpers is made here too.
     GridFactors f;
     f.lr = 0.0; f.pr = 0.0; f.lp = 0u; f.pp = 0u; f.cp = 0u; f.pat = 0u;
     if constexpr (SRC == EP_SRC_FACT) load_factors<F>(a.c, i, f);
     RowBounds<F> rb;
     load_row_bounds<F>(a.c, N, i, rb);
-    double run = es.ret_running ? es.ret_running[i] : 0.0;
-    double sum = es.ret_sum ? es.ret_sum[i] : 0.0;
-    double last = es.ret_last ? es.ret_last[i] : 0.0;
-    int32_t eps = es.episodes ? es.episodes[i] : 0;
+    LaneStats st;
+    st.load(es, i);
     {
         const bool GI = gen_instant;
         RowSlot ring[U];
@@ -99,14 +94,10 @@ __global__ __launch_bounds__(BLOCK_K) void step_k_policy_episodes_kernel(const S
             step_core<F>(p, d, s, in, true, true, GI, o);
             const double r = shaped_reward<F>(a.shaper, o);
             const bool dn = t >= fin - 1;                       // done_at(a, i, t)
-            if (out.reward) out.reward[o64] = r;
-            if (out.done) out.done[o64] = (uint8_t)dn;
-            if constexpr (F & F_BATTERY) { if (out.soc_trace) out.soc_trace[o64] = s.soc; }
-            if constexpr (F & F_GENSET) { if (out.status_trace) out.status_trace[o64] = s.status; }
+            store_step_outputs<F>(out, o64, r, dn, s);
             o64 += N;
             r64 += N * D;
-            run += r;
-            if (t == fin - 1) { last = run; sum += run; eps += 1; run = 0.0; }
+            st.update(r, t, fin);
             if (ar_on && dn) {
                 const KArgs *__restrict__ a_dev = late->a_dev;
                 if (want_final) {                               // the row of the episode that ends here: slot 0, still the old rows
@@ -114,10 +105,8 @@ __global__ __launch_bounds__(BLOCK_K) void step_k_policy_episodes_kernel(const S
                     widen_row_slot<F, SRC>(a, f, ring[0], t + 1, off, inf);
                     store_final_row<F>(a_dev, a.T, desc, late->final_obs, r64, i, t + 1 + off, inf, rb, p, s);
                 }
-                // (the arguments of the draw out of the handle's device copy of the KArgs, read here, in the branch)
                 off = episode_auto_restart(*a_dev, i, t, off, true);
                 fin = a_dev->ep_final[i];
-                // row slot v now stands for step k + 1 + v: all of them again, at the rows of the new episode
 #pragma unroll
                 for (int v = 0; v < U; v++)
                     if (k + 1 + v <= K) fetch_row_slot<F, SRC>(a, f, i, t + 1 + v, off, ring[v]);
@@ -135,34 +124,20 @@ __global__ __launch_bounds__(BLOCK_K) void step_k_policy_episodes_kernel(const S
     }
     store_state<F>(late->a_dev->c, i, s);     // (the same columns; their addresses need no scalar registers across the loop)
     // (the statistics' addresses a second time, from the kernarg segment: the first copies ended their lives before the loop)
-    if (double *q = late->es.ret_running) q[i] = run;
-    if (double *q = late->es.ret_sum) q[i] = sum;
-    if (double *q = late->es.ret_last) q[i] = last;
-    if (int32_t *q = late->es.episodes) q[i] = eps;
+    st.store(late->es.ret_running, late->es.ret_sum, late->es.ret_last, late->es.episodes, i);
 }
 
 template <int F>
 static void step_k_policy_episodes_dispatch(const EpisodePolicyLaunch &P)
 {
     const EpisodeLaunch &L = P.r.e;
-    // row ring as rollout_episodes_kernel's: a slot of a layout with a GridModule holds up to six values (depth 4), else two (depth 8)
     const StepPolicyArgs g{*L.k, P.pol, L.t, L.K, L.gpb, pack_row_desc(*L.k), L.out, L.stats, L.k_dev, P.r.obs, P.r.final_obs,
                            (double *)P.actions_out};
-#define MGX_STEP_EPISODES(SRC) step_k_policy_episodes_kernel<F, (F & F_GRID) ? 4 : MGX_RING_ROLLOUT, SRC><<<L.blocks, BLOCK_K, P.lds_bytes, L.stream>>>(g)
-    if (L.src == EP_SRC_FACT) MGX_STEP_EPISODES(EP_SRC_FACT);
-    else if (L.src == EP_SRC_GRID_MAJOR) MGX_STEP_EPISODES(EP_SRC_GRID_MAJOR);
-    else MGX_STEP_EPISODES(EP_SRC_GATHER);
-#undef MGX_STEP_EPISODES
+    with_episode_src(L.src, [&](auto src) {
+        step_k_policy_episodes_kernel<F, ROW_RING<F>, decltype(src)::value><<<L.blocks, BLOCK_K, P.lds_bytes, L.stream>>>(g);
+    });
 }
 
-bool MGX_CAT(launch_step_k_policy_episodes_p, MGX_STEP_POLICY_EPISODE_PART)(const EpisodePolicyLaunch &P)
-{
-    switch (P.r.e.flags) {
-#define X(FV) case FV: step_k_policy_episodes_dispatch<FV>(P); return true;
-        MGX_PART_FLAGS(X)
-#undef X
-        default: return false;
-    }
-}
+MGX_EPISODE_LAUNCH_FN(step_k_policy_episodes, EpisodePolicyLaunch, L.r.e.flags)
 
 }  // namespace mgx

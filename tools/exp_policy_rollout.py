@@ -14,6 +14,7 @@ Every leg: warm-up calls, then `--repeats` timed blocks (torch.cuda.synchronize(
 (min .. max) are reported.  (a)/(c) and (c)/(b) from the medians, + the resource figures of the two kernels of this configuration.
 
     python tools/exp_policy_rollout.py [--out profiles/exp_policy_rollout.txt] [--grids 100000] [--K 64] [--repeats 5]
+                                       [--series materialised] [--root DIR]      (--root: the tree whose pymgrid_amd is imported)
 """
 import argparse
 import json
@@ -33,6 +34,7 @@ def main():
     ap.add_argument("--launches", type=int, default=8, help="fused launches per timed block")
     ap.add_argument("--stepped", type=int, default=128, help="single steps per timed block of leg (a)")
     ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--series", choices=["factorised", "materialised"], default="factorised")
     ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     a = ap.parse_args()
     sys.path.insert(0, os.path.abspath(a.root))
@@ -44,7 +46,7 @@ def main():
     _lib.build()
     dev = torch.device("cuda:0")
     N, K = a.grids, a.K
-    lines = [f"# tools/exp_policy_rollout.py: {N} genset+battery+grid grids, T = {a.T}, {a.length}-step episodes, factorised, H = 0, "
+    lines = [f"# tools/exp_policy_rollout.py: {N} genset+battery+grid grids, T = {a.T}, {a.length}-step episodes, {a.series}, H = 0, "
              f"K = {K}; kernels {_lib.source_hash()}; {torch.cuda.get_device_name(0)}",
              f"# us per env-step: median of {a.repeats} blocks (min .. max); a block = {a.launches} launches of {K} steps, leg (a): "
              f"{a.stepped} single steps"]
@@ -69,7 +71,7 @@ def main():
     for discrete in (True, False):
         for n_hidden in (0, 16):
             head = "discrete" if discrete else "continuous"
-            mk = lambda: PerGridWindowEnv(generate(N, n_steps=a.T, seed=42, arch="genset+battery+grid", device=dev, series="factorised"),  # noqa: E731
+            mk = lambda: PerGridWindowEnv(generate(N, n_steps=a.T, seed=42, arch="genset+battery+grid", device=dev, series=a.series),  # noqa: E731
                                           trajectory_length=a.length, discrete=discrete, auto_reset=True, seed=7)
             pe = mk()
             obs0 = pe.reset()
