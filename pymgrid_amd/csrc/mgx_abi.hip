@@ -1650,7 +1650,7 @@ int mgx_step_k(mgx_handle *h, const void *actions, int32_t K, int normalized, do
                                               k, actions, t_arg(h), K, normalized, fo)));
             } else {
                 MGX_DISPATCH_F(h->flags, (step_k_multi_kernel<F><<<multi_blocks(k.g1 - k.g0), BLOCK_MULTI, h->multi_lds, s>>>(
-                                              k, actions, nullptr, 0, 0, nullptr, 0, t_arg(h), K, normalized, fo, h->multi_small)));
+                                              k, actions, nullptr, 0, 0, nullptr, 0, t_arg(h), K, normalized, fo)));
             }
         });
         return finish_step(h, K, st, hipGetLastError(), "step_k_multi_kernel launch");
@@ -2206,7 +2206,7 @@ int mgx_rollout_lists(mgx_handle *h, const int32_t *action_id, int per_step, con
             return;
         }
         MGX_DISPATCH_F(h->flags, (step_k_multi_kernel<F><<<multi_blocks(k.g1 - k.g0), BLOCK_MULTI, h->multi_lds, s>>>(
-                                      k, nullptr, lists, n_lists, list_len, action_id, per_step, t_arg(h), K, 0, fo, h->multi_small)));
+                                      k, nullptr, lists, n_lists, list_len, action_id, per_step, t_arg(h), K, 0, fo)));
     });
     return finish_step(h, K, st, hipGetLastError(), "step_k_multi_kernel launch");
 }

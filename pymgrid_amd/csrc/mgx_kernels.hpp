@@ -971,6 +971,124 @@ __device__ __forceinline__ bool store_colmajor_packs(const IT *image, int32_t BP
     return true;
 }
 
+// Phase 2 of every ring refill (windows_body, obs_windows_k_multi_kernel): the image of a group of plan.group grids in LDS -> the K
+// blocks of the ring, on the first OBS_K_THREADS threads of the workgroup (the caller's barrier after phase 1 is behind them, none
+// follows).  map[c]: offset of column c's k = 0 entry in a grid's block of the image (pitch plan.bp); offsets from S0 on are state
+// columns.  with_state: the launch writes the state columns (block 0 holds the current state); without it (a refill AHEAD of the
+// counter) they are one strip of zeros.  pairs_ok: the caller's word that 2-element stores into ROW-major blocks are safe -- the
+// ring 16-byte aligned (8 for floats) and D even, so that a pair never straddles two rows.  g0: first grid of the group.
+template <typename OT, typename IT>
+__device__ __forceinline__ void store_window_blocks(const KArgs &a, const WindowsKPlan &plan, const IT *image, const uint32_t *map,
+                                                    int32_t S0, bool with_state, bool pairs_ok, int64_t g0, OT *__restrict__ ring)
+{
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (tid >= OBS_K_THREADS) return;
+    const int32_t G = plan.group, K = plan.K, BP = plan.bp, D = a.obs_dim;
+    const int32_t g = tid & (G - 1), q = tid / G, Q2 = OBS_K_THREADS / G;     // thread (g, q) of Q2 per grid
+    const int64_t N = a.N;
+    const int32_t n_valid = (N - g0 < G) ? (int32_t)(N - g0) : G;
+    const int32_t total = n_valid * D;
+    typedef OT vec2 __attribute__((ext_vector_type(2)));
+    constexpr int KW = OBS_K_THREADS / 64;
+    if (a.obs_colpitch) {
+        // COLUMN-major blocks: value (block k, column c, grid g0 + g) at (k * D + c) * P + g0 + g.  Thread (g, cq) writes column
+        // c = cq, cq + Q2, ... of its grid for every block: the G grids of a (k, c) pair -- 16 doubles, or 32 floats out of the
+        // float image -- are whole 128-byte lines (P and g0 are multiples of G), written whole by G adjacent lanes.  Nothing else
+        // ever writes into such a line's bytes except the step's state columns -- which are whole coalesced lines of their own here
+        // (a wave's 64 grids x 8 B per column).
+        const int64_t P = a.obs_colpitch, kstride = (int64_t)D * P;
+        if (plan.pairs && store_colmajor_packs<OT, IT>(image, BP, map, D, with_state ? 0x7fffffff : S0, K, G, g0, N, P, ring, tid)) return;
+        const bool in_batch = g0 + g < N;
+        OT *outc = ring + g0 + g;
+        for (int32_t c = q; c < D; c += Q2) {
+            const uint32_t m = map[c];
+            // a ring written ahead of the counter leaves the state columns to the steps: here they are lines of their own, so
+            // not writing them costs nothing (in row-major blocks the same holes make partial lines: MGX_WIN_SKIP_STATE)
+            if (!with_state && m >= (uint32_t)S0) continue;
+            const IT *src = image + g * BP + m;
+            OT *o = outc + (int64_t)c * P;
+            int32_t k = 0;
+            if constexpr (WIN_U > 1) {                   // WIN_U image words in flight before the first store of the batch
+                for (; k + WIN_U <= K; k += WIN_U) {
+                    IT v[WIN_U];
+#pragma unroll
+                    for (int u = 0; u < WIN_U; u++) v[u] = src[k + u];
+#pragma unroll
+                    for (int u = 0; u < WIN_U; u++)
+                        if (in_batch) MGX_WIN_STORE((OT)v[u], o + (int64_t)(k + u) * kstride);
+                }
+            }
+            for (; k < K; k++)
+                if (in_batch) MGX_WIN_STORE((OT)src[k], o + (int64_t)k * kstride);
+        }
+        return;
+    }
+    // ROW-major blocks.  A lane's element schedule (which (grid, column) its j-th store carries) is the same for every block: the
+    // column map is looked up once per element and reused for the wave's blocks k = wave, wave + 4, ... (image[... + k]:
+    // consecutive words)
+    const int64_t block_stride = (int64_t)plan.pitch * D;
+    OT *out0 = ring + ((int64_t)wave * plan.pitch + g0) * D;
+    // MGX_WIN_SKIP_STATE=1 (experiment, OFF): a ring written ahead of the counter would leave the state columns alone -- the
+    // step that reaches a block writes them, so the zeros here are bytes written twice, 3 % of a config-5 fleet step.  Measured
+    // 10-25 % SLOWER (profiles/r04/exp_fleet_state_holes_ab.txt: 31 -> 34 us per fleet step at K = 16, 29 -> 36 us at K = 32):
+    // a 48-byte hole per row turns 1.25 of its 9.75 lines into partial-line writes, and those cost far more than the bytes
+    // they save.  (The state blocks start on even columns in both flat orders: a 16-byte pair is all state or all window.)
+#ifndef MGX_WIN_SKIP_STATE
+#define MGX_WIN_SKIP_STATE 0
+#endif
+    const bool skip_state = !with_state && MGX_WIN_SKIP_STATE;
+    if (pairs_ok) {                                      // element pair f, f + 1 = 2 lane + 128 j -> (row, column)
+        int32_t r = 2 * lane / D, c = 2 * lane - r * D;
+        for (int32_t f = 2 * lane; f < total; f += 128) {
+            const uint32_t m0 = map[c], m1 = map[c + 1];               // D even, c even: the pair never straddles two rows
+            if (!(skip_state && m0 >= (uint32_t)S0)) {
+                const IT *s0 = image + r * BP + m0 + wave;
+                const IT *s1 = image + r * BP + m1 + wave;
+                OT *out = out0 + f;
+                const int64_t kw_stride = KW * block_stride;
+                int32_t k = wave;
+                if constexpr (WIN_U > 1) {               // WIN_U pairs of image words in flight before the first store of the batch
+                    for (; k + (WIN_U - 1) * KW < K; k += WIN_U * KW) {
+                        IT a0[WIN_U], a1[WIN_U];
+#pragma unroll
+                        for (int u = 0; u < WIN_U; u++) { a0[u] = s0[u * KW]; a1[u] = s1[u * KW]; }
+#pragma unroll
+                        for (int u = 0; u < WIN_U; u++) {
+                            vec2 v2;
+                            v2.x = (OT)a0[u]; v2.y = (OT)a1[u];
+                            MGX_WIN_STORE(v2, reinterpret_cast<vec2 *>(out + u * kw_stride));
+                        }
+                        s0 += WIN_U * KW; s1 += WIN_U * KW; out += WIN_U * kw_stride;
+                    }
+                }
+                for (; k < K; k += KW) {
+                    vec2 v2;
+                    v2.x = (OT)*s0; v2.y = (OT)*s1;
+                    MGX_WIN_STORE(v2, reinterpret_cast<vec2 *>(out));
+                    s0 += KW; s1 += KW; out += kw_stride;
+                }
+            }
+            c += 128;
+            while (c >= D) { c -= D; r++; }
+        }
+    } else {                                             // element by element: a ring off the pair's alignment, or an odd D
+        int32_t r = lane / D, c = lane - r * D;
+        for (int32_t f = lane; f < total; f += 64) {
+            const uint32_t m0 = map[c];
+            if (!(skip_state && m0 >= (uint32_t)S0)) {
+                const IT *s0 = image + r * BP + m0 + wave;
+                OT *out = out0 + f;
+                for (int32_t k = wave; k < K; k += KW) {
+                    MGX_WIN_STORE((OT)*s0, out);
+                    s0 += KW; out += KW * block_stride;
+                }
+            }
+            c += 64;
+            while (c >= D) { c -= D; r++; }
+        }
+    }
+}
+
 // Body shared by obs_windows_k_kernel and the window part of fleet_step_kernel: workgroup `group` (16 grids) of the batch.
 // GRID: the layout has a GridModule (6 instead of 2 series components).  `now` (meaningful in the q == 0 lanes, with have_now):
 // the state columns of the current state for block 0; without it (a prefetch ahead of the counter) every state column is zero.
@@ -981,7 +1099,7 @@ __device__ __forceinline__ void windows_body(const KArgs &a, const WindowsKPlan 
     typedef typename std::conditional<sizeof(OT) == 4, float, double>::type IT;       // float rows: a float image (windows_k_module)
     IT *image = reinterpret_cast<IT *>(image_raw);
     constexpr int NCOMP = 2 + (GRID ? 4 : 0);
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     // Two phases with their own thread counts.  Phase 1 (series rows -> normalised image in LDS) is a chain of dependent loads,
     // divisions and LDS stores per value: with one wave per SIMD nothing hides its latencies -- it took 84-99 of the 200-290 us of
     // a refill (profiles/r05/exp_refill_variants.txt: the "nostore" build) -- so ALL blockDim.x threads of the launch share it
@@ -1046,109 +1164,10 @@ __device__ __forceinline__ void windows_body(const KArgs &a, const WindowsKPlan 
         map[col] = comp == 0xffffu ? S0 + (have_now ? h * K : 0) : (h == 0 ? NU0 + comp * K : comp * RP + h);
     }
     __syncthreads();
-    if (tid >= OBS_K_THREADS) return;                    // phase 2: the first OBS_K_THREADS threads (no barrier follows)
-    const int32_t Q2 = OBS_K_THREADS / G;                // ... thread (g, q) of Q2 per grid (q = tid / G < Q2 here)
-    const int32_t n_valid = (N - g0 < G) ? (int32_t)(N - g0) : G;
-    const int32_t total = n_valid * D;                   // D is even (one load, one renewable module)
+    // phase 2.  D is even here (one load, one renewable module): pairs wherever the ring is aligned for them
     typedef OT vec2 __attribute__((ext_vector_type(2)));
     const bool wide = (reinterpret_cast<uintptr_t>(ring) & (sizeof(vec2) - 1)) == 0;
-    constexpr int KW = OBS_K_THREADS / 64;
-    if (a.obs_colpitch) {
-        // COLUMN-major blocks: value (block k, column c, grid g0 + g) at (k * D + c) * P + g0 + g.  Thread (g, cq) writes column
-        // c = cq, cq + Q, ... of its grid for the wave's blocks k = wave', ...: the G grids of a (k, c) pair -- 16 doubles, or 32
-        // floats out of the float image -- are ONE 128-byte line (P and g0 are multiples of G), written whole by G adjacent lanes.  Nothing else ever writes into such a line's bytes
-        // except the step's state columns -- which are whole coalesced lines of their own here (a wave's 64 grids x 8 B per column).
-        const int64_t P = a.obs_colpitch;
-        if (plan.pairs && store_colmajor_packs<OT, IT>(image, BP, map, D, have_now ? 0x7fffffff : S0, K, G, g0, N, P, ring, tid)) return;
-        const bool in_batch = i < N;
-        OT *outc = ring + g0 + g;
-        for (int32_t c = q; c < D; c += Q2) {
-            const uint32_t m = map[c];
-            // a ring written ahead of the counter leaves the state columns to the steps: here they are lines of their own, so
-            // not writing them costs nothing (in row-major blocks the same holes make partial lines: MGX_WIN_SKIP_STATE)
-            if (!have_now && m >= (uint32_t)S0) continue;
-            const IT *src = image + g * BP + m;
-            OT *o = outc + (int64_t)c * P;
-            const int64_t kstride = (int64_t)D * P;
-            int32_t k = 0;
-            if constexpr (WIN_U > 1) {                   // WIN_U image words in flight before the first store of the batch
-                for (; k + WIN_U <= K; k += WIN_U) {
-                    IT v[WIN_U];
-#pragma unroll
-                    for (int u = 0; u < WIN_U; u++) v[u] = src[k + u];
-#pragma unroll
-                    for (int u = 0; u < WIN_U; u++)
-                        if (in_batch) MGX_WIN_STORE((OT)v[u], o + (int64_t)(k + u) * kstride);
-                }
-            }
-            for (; k < K; k++)
-                if (in_batch) MGX_WIN_STORE((OT)src[k], o + (int64_t)k * kstride);
-        }
-        return;
-    }
-    // A lane's element schedule (which (grid, column) its j-th store carries) is the same for every block: the column map is
-    // looked up once per element and reused for the wave's blocks k = wave, wave + 4, ... (image[... + k]: consecutive words)
-    const int64_t block_stride = (int64_t)plan.pitch * D;
-    OT *out0 = ring + ((int64_t)wave * plan.pitch + g0) * D;
-    // MGX_WIN_SKIP_STATE=1 (experiment, OFF): a ring written ahead of the counter would leave the state columns alone -- the
-    // step that reaches a block writes them, so the zeros here are bytes written twice, 3 % of a config-5 fleet step.  Measured
-    // 10-25 % SLOWER (profiles/r04/exp_fleet_state_holes_ab.txt: 31 -> 34 us per fleet step at K = 16, 29 -> 36 us at K = 32):
-    // a 48-byte hole per row turns 1.25 of its 9.75 lines into partial-line writes, and those cost far more than the bytes
-    // they save.  (The state blocks start on even columns in both flat orders: a 16-byte pair is all state or all window.)
-#ifndef MGX_WIN_SKIP_STATE
-#define MGX_WIN_SKIP_STATE 0
-#endif
-    const bool skip_state = !have_now && MGX_WIN_SKIP_STATE;
-    if (wide) {                                          // element pair f, f + 1 = 2 lane + 128 j -> (row, column)
-        int32_t r = 2 * lane / D, c = 2 * lane - r * D;
-        for (int32_t f = 2 * lane; f < total; f += 128) {
-            const uint32_t m0 = map[c], m1 = map[c + 1];               // D even, c even: the pair never straddles two rows
-            if (!(skip_state && m0 >= (uint32_t)S0)) {
-                const IT *s0 = image + r * BP + m0 + wave;
-                const IT *s1 = image + r * BP + m1 + wave;
-                OT *out = out0 + f;
-                const int64_t kw_stride = KW * block_stride;
-                int32_t k = wave;
-                if constexpr (WIN_U > 1) {               // WIN_U pairs of image words in flight before the first store of the batch
-                    for (; k + (WIN_U - 1) * KW < K; k += WIN_U * KW) {
-                        IT a0[WIN_U], a1[WIN_U];
-#pragma unroll
-                        for (int u = 0; u < WIN_U; u++) { a0[u] = s0[u * KW]; a1[u] = s1[u * KW]; }
-#pragma unroll
-                        for (int u = 0; u < WIN_U; u++) {
-                            vec2 v2;
-                            v2.x = (OT)a0[u]; v2.y = (OT)a1[u];
-                            MGX_WIN_STORE(v2, reinterpret_cast<vec2 *>(out + u * kw_stride));
-                        }
-                        s0 += WIN_U * KW; s1 += WIN_U * KW; out += WIN_U * kw_stride;
-                    }
-                }
-                for (; k < K; k += KW) {
-                    vec2 v2;
-                    v2.x = (OT)*s0; v2.y = (OT)*s1;
-                    MGX_WIN_STORE(v2, reinterpret_cast<vec2 *>(out));
-                    s0 += KW; s1 += KW; out += kw_stride;
-                }
-            }
-            c += 128;
-            while (c >= D) { c -= D; r++; }
-        }
-    } else {
-        int32_t r = lane / D, c = lane - r * D;
-        for (int32_t f = lane; f < total; f += 64) {
-            const uint32_t m0 = map[c];
-            if (!(skip_state && m0 >= (uint32_t)S0)) {
-                const IT *s0 = image + r * BP + m0 + wave;
-                OT *out = out0 + f;
-                for (int32_t k = wave; k < K; k += KW) {
-                    MGX_WIN_STORE((OT)*s0, out);
-                    s0 += KW; out += KW * block_stride;
-                }
-            }
-            c += 64;
-            while (c >= D) { c -= D; r++; }
-        }
-    }
+    store_window_blocks<OT, IT>(a, plan, image, map, S0, have_now, wide, g0, ring);
 }
 
 template <int F, typename OT>
@@ -1861,30 +1880,51 @@ __device__ inline void observe_row_multi(const KArgs &a, int64_t i, int32_t t, O
     }
 }
 
-// One general-path step of grid i on the register form (at most MS modules of a kind), lock-step: what a bucket with several
-// modules of a kind runs inside the fleet's launch (fleet_step_kernel_vm, round 6) -- the `small` arm of step_multi_kernel
-// without per-grid episodes.
+// Where a general step's or mgx_observe's observation goes: into a COLUMN-major ring block whose window columns are written already
+// (obs_is_ring_block) -- then only the state columns of grid i, coalesced runs (observe_ring_state_multi) -- or a whole row [D] at
+// obs + i D, as float or double (observe_row_multi).  The three step kernels spell the choice
+//     if (obs_is_ring_block(a)) observe_ring_state_multi<F>(a, i, obs);  else if (a.obs_f32) <float row>;  else <double row>;
+// themselves: as ONE piece (`observe_step_multi`, forced inline or not) it cost step_lists_small_kernel<15, true> 26 -> 36 spilled
+// SGPRs and step_multi_kernel<6, true> 0 -> 1 (profiles/exp_general_path_refactor.txt); a ring-state piece that returned whether it
+// had written took 2 VGPRs of every form of observe_multi_kernel and a wave per SIMD of <1> (96 -> 98 VGPRs, 5 -> 4).
+__device__ __forceinline__ bool obs_is_ring_block(const KArgs &a) { return a.obs_state_only == 1 && a.obs_colpitch; }
+template <int F>
+__device__ __forceinline__ void observe_ring_state_multi(const KArgs &a, int64_t i, void *obs)
+{
+    const int64_t P = a.obs_colpitch, k0 = (int64_t)(a.n_load + a.n_pv) * (1 + a.H);
+    if (a.obs_f32) observe_state_multi<F>(a, i, (float *)obs + k0 * P + i, P);
+    else observe_state_multi<F>(a, i, (double *)obs + k0 * P + i, P);
+}
+
+// One general-path step of grid i on the register form (at most MS modules of a kind) at series row tr: everything requested up
+// front, the sweep on registers, the state back into the columns.
+template <int F>
+__device__ __forceinline__ void step_multi_small_at(const KArgs &a, const void *actions, int64_t i, int32_t tr, bool normalized, double *log,
+                                                    Outputs &o)
+{
+    const int A = 2 * a.n_genset + a.n_battery + a.n_grid;
+    MultiRegs R; MultiStepIn sin;
+    load_multi_regs<F>(a, i, R);
+    if (a.act_f32) load_multi_step_in<F>(a, (const float *)actions + i * A, i, tr, sin);
+    else load_multi_step_in<F>(a, (const double *)actions + i * A, i, tr, sin);
+    step_multi_small<F>(a, R, sin, i, normalized, log ? log + i : nullptr, o);
+    store_multi_state<F>(a, i, R);
+}
+
+// ... lock-step, with its outputs: what a bucket with several modules of a kind runs inside the fleet's launch
+// (fleet_step_kernel_vm, round 6).
 template <int F>
 __device__ __forceinline__ void step_multi_small_body(const KArgs &a, const void *__restrict__ actions, int32_t t, int normalized,
                                                       double *__restrict__ reward, uint8_t *__restrict__ done, void *__restrict__ obs,
                                                       double *__restrict__ log, int64_t i)
 {
-    const int A = 2 * a.n_genset + a.n_battery + a.n_grid;
     Outputs o;
-    MultiRegs R; MultiStepIn sin;
-    load_multi_regs<F>(a, i, R);
-    if (a.act_f32) load_multi_step_in<F>(a, (const float *)actions + i * A, i, t, sin);
-    else load_multi_step_in<F>(a, (const double *)actions + i * A, i, t, sin);
-    step_multi_small<F>(a, R, sin, i, normalized != 0, log ? log + i : nullptr, o);
-    store_multi_state<F>(a, i, R);
+    step_multi_small_at<F>(a, actions, i, t, normalized != 0, log, o);
     reward[i] = shaped_reward<F>(a.shaper, o);
     if (done) done[i] = done_at(a, i, t);
     if (obs) {
-        if (a.obs_state_only == 1 && a.obs_colpitch) {            // the state columns of a COLUMN-major ring block: coalesced runs
-            const int64_t P = a.obs_colpitch, k0 = (int64_t)(a.n_load + a.n_pv) * (1 + a.H);
-            if (a.obs_f32) observe_state_multi<F>(a, i, (float *)obs + k0 * P + i, P);
-            else observe_state_multi<F>(a, i, (double *)obs + k0 * P + i, P);
-        } else if (a.obs_f32) observe_row_multi<F>(a, i, t + 1, (float *)obs + i * a.obs_dim);
+        if (obs_is_ring_block(a)) observe_ring_state_multi<F>(a, i, obs);
+        else if (a.obs_f32) observe_row_multi<F>(a, i, t + 1, (float *)obs + i * a.obs_dim);
         else observe_row_multi<F>(a, i, t + 1, (double *)obs + i * a.obs_dim);
     }
 }
@@ -1926,25 +1966,16 @@ __global__ __launch_bounds__(BLOCK_MULTI) void step_multi_kernel(const KArgs a, 
         // own [T, n, N] series (a per-lane gather); `tr` is the counter itself otherwise
         int32_t off = 0, tr = t;
         if constexpr (EP) { off = a.ep_off[i]; tr = (int32_t)episode_row(a, t, off); }
-        if (small) {                                     // at most MS modules of a kind: everything requested up front, the sweep on registers
-            MultiRegs R; MultiStepIn sin;
-            load_multi_regs<F>(a, i, R);
-            if (a.act_f32) load_multi_step_in<F>(a, (const float *)actions + i * A, i, tr, sin);
-            else load_multi_step_in<F>(a, (const double *)actions + i * A, i, tr, sin);
-            step_multi_small<F>(a, R, sin, i, normalized != 0, log ? log + i : nullptr, o);
-            store_multi_state<F>(a, i, R);
-        } else if (a.act_f32) step_multi_core<F>(a, (const float *)actions + i * A, i, tr, normalized != 0, L, log ? log + i : nullptr, o);
+        if (small) step_multi_small_at<F>(a, actions, i, tr, normalized != 0, log, o);      // at most MS modules of a kind
+        else if (a.act_f32) step_multi_core<F>(a, (const float *)actions + i * A, i, tr, normalized != 0, L, log ? log + i : nullptr, o);
         else step_multi_core<F>(a, (const double *)actions + i * A, i, tr, normalized != 0, L, log ? log + i : nullptr, o);
         reward[i] = shaped_reward<F>(a.shaper, o);
         const uint8_t dn = done_at(a, i, t);
         if (done) done[i] = dn;
         if constexpr (EP) { off = episode_auto_restart(a, i, t, off, dn != 0); t += off; }  // (the observation: row counter + 1 + offset)
         if (obs) {
-            if (a.obs_state_only == 1 && a.obs_colpitch) {            // the state columns of a COLUMN-major ring block: coalesced runs
-                const int64_t P = a.obs_colpitch, k0 = (int64_t)(a.n_load + a.n_pv) * (1 + a.H);
-                if (a.obs_f32) observe_state_multi<F>(a, i, (float *)obs + k0 * P + i, P);
-                else observe_state_multi<F>(a, i, (double *)obs + k0 * P + i, P);
-            } else if (a.obs_f32) observe_row_multi<F>(a, i, t + 1, (float *)obs + i * a.obs_dim);
+            if (obs_is_ring_block(a)) observe_ring_state_multi<F>(a, i, obs);
+            else if (a.obs_f32) observe_row_multi<F>(a, i, t + 1, (float *)obs + i * a.obs_dim);
             else observe_row_multi<F>(a, i, t + 1, (double *)obs + i * a.obs_dim);
         }
     }
@@ -1958,12 +1989,7 @@ __global__ __launch_bounds__(BLOCK_MULTI) void observe_multi_kernel(const KArgs 
     const int64_t i = (int64_t)a.g0 + (int64_t)blockIdx.x * BLOCK_MULTI + threadIdx.x;
     if (i >= a.g1) return;
     if (a.ep_off) t += a.ep_off[i];                                   // in-place episodes: the grid's own row
-    if (a.obs_state_only == 1 && a.obs_colpitch) {                    // state columns of a column-major ring block (step_multi_kernel)
-        const int64_t P = a.obs_colpitch, k0 = (int64_t)(a.n_load + a.n_pv) * (1 + a.H);
-        if (a.obs_f32) observe_state_multi<F>(a, i, (float *)obs + k0 * P + i, P);
-        else observe_state_multi<F>(a, i, (double *)obs + k0 * P + i, P);
-        return;
-    }
+    if (obs_is_ring_block(a)) { observe_ring_state_multi<F>(a, i, obs); return; }
     const bool noisy = a.c.load_noise_std || a.c.pv_noise_std || a.c.grid_noise_std;
     if (noisy) {
         if (a.obs_f32) observe_row_multi<F, float, true>(a, i, t, (float *)obs + i * a.obs_dim);
@@ -1986,8 +2012,8 @@ __global__ __launch_bounds__(OBS_P1_THREADS) void obs_windows_k_multi_kernel(con
     extern __shared__ double image_raw[];
     typedef typename std::conditional<sizeof(OT) == 4, float, double>::type IT;       // float rows: a float image (windows_body)
     IT *image = reinterpret_cast<IT *>(image_raw);
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int32_t NT = (int32_t)blockDim.x;              // phase 1 on every thread of the launch, phase 2 on the first OBS_K_THREADS (windows_body)
+    const int tid = threadIdx.x;
+    const int32_t NT = (int32_t)blockDim.x;              // phase 1 on every thread of the launch (the two phases: windows_body)
     const int32_t G = plan.group, Q = NT / G, K = plan.K, RP = plan.rp, BP = plan.bp;
     const int32_t g = tid & (G - 1), q = tid / G;
     const int64_t group = (int64_t)plan.group0 + blockIdx.x, g0 = group * G, N = a.N;
@@ -2041,87 +2067,10 @@ __global__ __launch_bounds__(OBS_P1_THREADS) void obs_windows_k_multi_kernel(con
         map[col] = m;
     }
     __syncthreads();
-    if (tid >= OBS_K_THREADS) return;                    // phase 2: the first OBS_K_THREADS threads (no barrier follows)
-    const int32_t n_valid = (N - g0 < G) ? (int32_t)(N - g0) : G;
-    const int32_t total = n_valid * D;
+    // phase 2.  The general D may be odd: pairs only where they never straddle two rows and the ring is aligned for them
     typedef OT vec2 __attribute__((ext_vector_type(2)));
-    constexpr int KW = OBS_K_THREADS / 64;
-    if (a.obs_colpitch) {
-        // COLUMN-major blocks (windows_body): value (block k, column c, grid g0 + g) at (k * D + c) * P + g0 + g -- the G grids
-        // of a (k, c) pair are whole 128-byte lines (32 doubles: two, 32 floats: one).  A ring written ahead of the counter leaves the state columns to the
-        // steps: here they are lines of their own, so not writing them costs nothing (7 % of a 162-column row).
-        const int64_t P = a.obs_colpitch, kstride = (int64_t)D * P;
-        if (plan.pairs && store_colmajor_packs<OT, IT>(image, BP, map, D, plan.with_state ? 0x7fffffff : S0, K, G, g0, N, P, ring, tid)) return;
-        const int32_t Q2 = OBS_K_THREADS / G;
-        const bool in_batch = i < N;
-        OT *outc = ring + g0 + g;
-        for (int32_t c = q; c < D; c += Q2) {
-            const uint32_t m = map[c];
-            if (!plan.with_state && m >= (uint32_t)S0) continue;
-            const IT *src = image + g * BP + m;
-            OT *o = outc + (int64_t)c * P;
-            int32_t k = 0;
-            if constexpr (WIN_U > 1) {
-                for (; k + WIN_U <= K; k += WIN_U) {
-                    IT v[WIN_U];
-#pragma unroll
-                    for (int u = 0; u < WIN_U; u++) v[u] = src[k + u];
-#pragma unroll
-                    for (int u = 0; u < WIN_U; u++)
-                        if (in_batch) MGX_WIN_STORE((OT)v[u], o + (int64_t)(k + u) * kstride);
-                }
-            }
-            for (; k < K; k++)
-                if (in_batch) MGX_WIN_STORE((OT)src[k], o + (int64_t)k * kstride);
-        }
-        return;
-    }
-    const int64_t block_stride = (int64_t)plan.pitch * D;
-    OT *out0 = ring + ((int64_t)wave * plan.pitch + g0) * D;
-    // pairs of elements where they never straddle two rows (D even) and the ring is 16-byte aligned; else element by element
-    if (!(D & 1) && (reinterpret_cast<uintptr_t>(ring) & (sizeof(vec2) - 1)) == 0) {
-        int32_t r = 2 * lane / D, c = 2 * lane - r * D;
-        for (int32_t f = 2 * lane; f < total; f += 128) {
-            const IT *s0 = image + r * BP + map[c] + wave, *s1 = image + r * BP + map[c + 1] + wave;
-            OT *out = out0 + f;
-            const int64_t kw_stride = KW * block_stride;
-            int32_t k = wave;
-            if constexpr (WIN_U > 1) {                   // WIN_U pairs of image words in flight before the first store of the batch
-                for (; k + (WIN_U - 1) * KW < K; k += WIN_U * KW) {
-                    IT a0[WIN_U], a1[WIN_U];
-#pragma unroll
-                    for (int u = 0; u < WIN_U; u++) { a0[u] = s0[u * KW]; a1[u] = s1[u * KW]; }
-#pragma unroll
-                    for (int u = 0; u < WIN_U; u++) {
-                        vec2 v2;
-                        v2.x = (OT)a0[u]; v2.y = (OT)a1[u];
-                        MGX_WIN_STORE(v2, reinterpret_cast<vec2 *>(out + u * kw_stride));
-                    }
-                    s0 += WIN_U * KW; s1 += WIN_U * KW; out += WIN_U * kw_stride;
-                }
-            }
-            for (; k < K; k += KW) {
-                vec2 v2;
-                v2.x = (OT)*s0; v2.y = (OT)*s1;
-                MGX_WIN_STORE(v2, reinterpret_cast<vec2 *>(out));
-                s0 += KW; s1 += KW; out += kw_stride;
-            }
-            c += 128;
-            while (c >= D) { c -= D; r++; }
-        }
-    } else {
-        int32_t r = lane / D, c = lane - r * D;
-        for (int32_t f = lane; f < total; f += 64) {
-            const IT *s0 = image + r * BP + map[c] + wave;
-            OT *out = out0 + f;
-            for (int32_t k = wave; k < K; k += KW) {
-                MGX_WIN_STORE((OT)*s0, out);
-                s0 += KW; out += KW * block_stride;
-            }
-            c += 64;
-            while (c >= D) { c -= D; r++; }
-        }
-    }
+    const bool pairs_ok = !(D & 1) && (reinterpret_cast<uintptr_t>(ring) & (sizeof(vec2) - 1)) == 0;
+    store_window_blocks<OT, IT>(a, plan, image, map, S0, plan.with_state != 0, pairs_ok, g0, ring);
 }
 
 // dry run (mgx_check_step) on the general path: the violations of the controllable instances depend on their own
@@ -2215,11 +2164,72 @@ __global__ __launch_bounds__(BLOCK_MULTI) void action_bounds_kernel(const KArgs 
 // soc_trace / status_trace report battery 0 / genset 0.
 constexpr int MGX_MAX_ACTIONS_MULTI = 4 * MGX_MAX_INSTANCES;
 
+// What the K-step launches of the general path have in common (step_k_multi_kernel: the memory form; step_k_multi_small_kernel and
+// rollout_multi_small_kernel: the register form), stated once: multi_k_done, store_multi_step_out, multi_step_pipeline,
+// finish_multi_small.  Each kernel keeps its prologue, its fetch and its step.
+// WRITTEN OUT in step_k_multi_small_kernel: the per-step stores and the two-step loop (the figures at the place,
+// profiles/exp_general_path_refactor.txt) -- a change to store_multi_step_out or multi_step_pipeline is made there too.
+// The first step of the launch (counted from t0) at which the lane's grid reports done.
+__device__ __forceinline__ int32_t multi_k_done(const KArgs &a, int64_t i, int32_t t0)
+{
+    return (a.grid_final ? a.grid_final[i] : a.final_step) - 1 - t0;
+}
+
+// What a step of the launch writes for its lane, off = k N + i: reward, done, the traces of battery 0 / genset 0 (soc, status: used
+// only where the layout has the module and the trace is asked for) and the running return.  NT: the write-once [K, N] streams go out
+// as non-temporal stores, as in the single-instance fused kernels.
+template <int F, bool NT>
+__device__ __forceinline__ void store_multi_step_out(const FusedOut &out, int64_t off, double r, bool dn, double soc, uint32_t status,
+                                                     double &ret)
+{
+    if constexpr (NT) {
+        if (out.reward) __builtin_nontemporal_store(r, out.reward + off);
+        if (out.done) out.done[off] = (uint8_t)dn;
+        if constexpr (F & F_BATTERY) { if (out.soc_trace) __builtin_nontemporal_store(soc, out.soc_trace + off); }
+        if constexpr (F & F_GENSET) { if (out.status_trace) __builtin_nontemporal_store(status, out.status_trace + off); }
+    } else {
+        if (out.reward) out.reward[off] = r;
+        if (out.done) out.done[off] = (uint8_t)dn;
+        if constexpr (F & F_BATTERY) { if (out.soc_trace) out.soc_trace[off] = soc; }
+        if constexpr (F & F_GENSET) { if (out.status_trace) out.status_trace[off] = status; }
+    }
+    ret += r;
+}
+
+// The K steps of the register form, two per trip: the inputs of step k + 1 are requested into `nxt` before step k runs on `cur`, those
+// of step k + 2 into `cur` before step k + 1 runs on `nxt` -- no copy of 26 doubles per step between the two buffers.
+// fetch(k, dst): request the inputs of step k (past the end the last step's are read again: unconditional loads); step(k, in): run it.
+template <class IN, class FETCH, class STEP>
+__device__ __forceinline__ void multi_step_pipeline(int32_t K, IN &cur, IN &nxt, FETCH &&fetch, STEP &&step)
+{
+    if (K > 0) fetch(0, cur);
+    int32_t k = 0;
+    for (; k + 1 < K; k += 2) {
+        fetch(k + 1, nxt);
+        step(k, cur);
+        fetch(k + 2 < K ? k + 2 : K - 1, cur);
+        step(k + 1, nxt);
+    }
+    if (k < K) step(k, cur);
+}
+
+// ... and what follows them: the state back into the columns, the return into its accumulator.
+// (the state columns' addresses are formed again here from an index the compiler cannot see through: held across the loop since the
+//  prologue's loads they were the registers the three-of-a-kind form spilled)
+template <int F, class CNT, int M>
+__device__ __forceinline__ void finish_multi_small(const KArgs &a, int64_t i, const MultiRegsT<M> &R, const FusedOut &out, double ret)
+{
+    int64_t i_out = i;
+    asm volatile("" : "+v"(i_out));
+    store_multi_state<F, CNT, M>(a, i_out, R);
+    if (out.ret_acc) out.ret_acc[i] += ret;
+}
+
 template <int F>
 __global__ __launch_bounds__(BLOCK_MULTI) void step_k_multi_kernel(const KArgs a, const void *__restrict__ actions,
                                                                    const int32_t *__restrict__ lists, int32_t n_lists, int32_t list_len,
                                                                    const int32_t *__restrict__ ids, int per_step, int32_t t0, int32_t K,
-                                                                   int normalized, const FusedOut out, int small)
+                                                                   int normalized, const FusedOut out)
 {
     extern __shared__ double multi_lds[];
     const int32_t K_launch = K;
@@ -2230,37 +2240,8 @@ __global__ __launch_bounds__(BLOCK_MULTI) void step_k_multi_kernel(const KArgs a
         const int64_t N = a.N;
         const int A = 2 * a.n_genset + a.n_battery + a.n_grid;
         StepLists L = multi_lists(a, multi_lds);
-        const int32_t k_done = (a.grid_final ? a.grid_final[i] : a.final_step) - 1 - t0;
+        const int32_t k_done = multi_k_done(a, i, t0);
         double ret = 0.0;
-        if (small && !lists) {
-            // At most MS modules of a kind, continuous controls: parameters and state stay in REGISTERS for the K steps (loaded
-            // once, the state written back once); per step only the controls and the series rows are read -- the NEXT step's are
-            // requested before this step's sweep starts -- and the requested outputs written.
-            MultiRegs R; MultiStepIn cur, nxt;
-            load_multi_regs<F>(a, i, R);
-            if (K > 0) {
-                if (a.act_f32) load_multi_step_in<F>(a, (const float *)actions + (int64_t)i * A, i, t0, cur);
-                else load_multi_step_in<F>(a, (const double *)actions + (int64_t)i * A, i, t0, cur);
-            }
-            for (int32_t k = 0; k < K; k++) {
-                const int64_t off = (int64_t)k * N + i;
-                const int32_t kn = k + 1 < K ? k + 1 : k;                // (the last step re-reads its own inputs: unconditional loads)
-                const int64_t offn = (int64_t)kn * N + i;
-                if (a.act_f32) load_multi_step_in<F>(a, (const float *)actions + offn * A, i, t0 + kn, nxt);
-                else load_multi_step_in<F>(a, (const double *)actions + offn * A, i, t0 + kn, nxt);
-                Outputs o;
-                double *log = out.log ? out.log + (int64_t)k * a.log_dim * N + i : nullptr;
-                step_multi_small<F>(a, R, cur, i, normalized != 0, log, o);
-                const double r = shaped_reward<F>(a.shaper, o);
-                if (out.reward) out.reward[off] = r;
-                if (out.done) out.done[off] = (uint8_t)(k >= k_done);
-                if constexpr (F & F_BATTERY) { if (out.soc_trace) out.soc_trace[off] = R.b_soc[0]; }
-                if constexpr (F & F_GENSET) { if (out.status_trace) out.status_trace[off] = R.g_status[0]; }
-                ret += r;
-                cur = nxt;
-            }
-            store_multi_state<F>(a, i, R);
-        } else
         for (int32_t k = 0; k < K; k++) {
             const int64_t off = (int64_t)k * N + i;
             Outputs o;
@@ -2276,21 +2257,22 @@ __global__ __launch_bounds__(BLOCK_MULTI) void step_k_multi_kernel(const KArgs a
             } else {
                 step_multi_core<F>(a, (const double *)actions + off * A, i, t0 + k, normalized != 0, L, log, o);
             }
-            const double r = shaped_reward<F>(a.shaper, o);
-            if (out.reward) out.reward[off] = r;
-            if (out.done) out.done[off] = (uint8_t)(k >= k_done);
-            if constexpr (F & F_BATTERY) { if (out.soc_trace) out.soc_trace[off] = a.c.soc[i]; }
-            if constexpr (F & F_GENSET) { if (out.status_trace) out.status_trace[off] = a.c.gen_status[i]; }
-            ret += r;
+            double soc = 0.0;                            // (the columns are read only where a trace is asked for)
+            uint32_t status = 0u;
+            if constexpr (F & F_BATTERY) { if (out.soc_trace) soc = a.c.soc[i]; }
+            if constexpr (F & F_GENSET) { if (out.status_trace) status = a.c.gen_status[i]; }
+            store_multi_step_out<F, false>(out, off, shaped_reward<F>(a.shaper, o), k >= k_done, soc, status, ret);
         }
         if (out.ret_acc) out.ret_acc[i] += ret;
     }
     advance_counter_in_kernel(a, K_launch);
 }
 
-// The register form of the K-step launch alone (layouts of at most MS modules of a kind, continuous controls): the same loop as the
-// `small` arm of step_k_multi_kernel in a kernel of its own -- without the run-time-count arm and the priority-list arm beside it the
-// loop keeps its pointers in SGPRs (the shared kernel reloaded ~100 spilled SGPRs per step through v_readlane).
+// The register form of the K-step launch (layouts of at most MS modules of a kind, continuous controls): parameters and state stay in
+// REGISTERS for the K steps (loaded once, the state written back once); per step only the controls and the series rows are read -- the
+// NEXT step's are requested before this step's sweep starts (multi_step_pipeline) -- and the requested outputs written.  A kernel of
+// its own: beside the run-time-count loop and the priority-list arm of step_k_multi_kernel the loop lost its pointers to spilled SGPRs
+// (~100 reloaded per step through v_readlane).
 // CNT: the instance counts, run-time (CountsRT: any small layout) or compile-time (CountsCT: the layouts of mgx_fused.hip part 5).
 #ifndef MGX_M3_WAVES
 #define MGX_M3_WAVES 2
@@ -2314,7 +2296,7 @@ __global__ __launch_bounds__(BLOCK_MULTI, (M >= 3 ? MGX_M3_WAVES : 1)) void step
     if (i < a.g1) {
         const int64_t N = a.N;
         const int A = 2 * CNT::ng(a) + CNT::nb(a) + CNT::nr(a);
-        const int32_t k_done = (a.grid_final ? a.grid_final[i] : a.final_step) - 1 - t0;
+        const int32_t k_done = multi_k_done(a, i, t0);
         double ret = 0.0;
         MultiRegsT<M> R; MultiStepInT<M> cur, nxt;
         load_multi_regs<F, CNT, M>(a, i, R);
@@ -2323,8 +2305,6 @@ __global__ __launch_bounds__(BLOCK_MULTI, (M >= 3 ? MGX_M3_WAVES : 1)) void step
             if (a.act_f32) load_multi_step_in<F, float, CNT, M>(a, (const float *)actions + (int64_t)i * A, i, t0, cur);
             else load_multi_step_in<F, double, CNT, M>(a, (const double *)actions + (int64_t)i * A, i, t0, cur);
         }
-        // two steps per trip: the inputs of step k + 1 are requested into `nxt` before step k runs on `cur`, those of step k + 2 into
-        // `cur` before step k + 1 runs on `nxt` -- no copy of 26 doubles per step between the two buffers
         auto fetch = [&](int32_t kk, MultiStepInT<M> &dst) __attribute__((always_inline)) {
             const int32_t kc = kk < K ? kk : K - 1;                  // (past the end: re-read the last step's inputs, unconditional loads)
             const int64_t offc = (int64_t)kc * N + i;
@@ -2337,13 +2317,17 @@ __global__ __launch_bounds__(BLOCK_MULTI, (M >= 3 ? MGX_M3_WAVES : 1)) void step
             double *log = out.log ? out.log + (int64_t)k * a.log_dim * N + i : nullptr;
             step_multi_small<F, CNT, M, PARK>(a, R, in, i, normalized != 0, log, o, pk);
             const double r = shaped_reward<F>(a.shaper, o);
-            // (write-once [K, N] streams: non-temporal stores, as in the single-instance fused kernels)
+            // store_multi_step_out<F, true>, WRITTEN OUT: through the piece 16 of the 27 forms of this kernel spilled more SGPRs (<1, CountsRT, 2>
+            // 30 -> 32, <15, CountsRT, 2> 89 -> 90) and <3, CountsCT<3, 3, 0, 1, 1>, 3> took 206 -> 212 VGPRs
             if (out.reward) __builtin_nontemporal_store(r, out.reward + off);
             if (out.done) out.done[off] = (uint8_t)(k >= k_done);
             if constexpr (F & F_BATTERY) { if (out.soc_trace) __builtin_nontemporal_store(R.b_soc[0], out.soc_trace + off); }
             if constexpr (F & F_GENSET) { if (out.status_trace) __builtin_nontemporal_store(R.g_status[0], out.status_trace + off); }
             ret += r;
         };
+        // multi_step_pipeline, WRITTEN OUT (with the first fetch above and the clamp in `fetch`): through the piece <3, CountsRT, 2> spilled
+        // 31 -> 50 SGPRs and <3, CountsCT<3, 3, 0, 1, 1>, 3> 8 -> 12; with both pieces every form took 4-10 more VGPRs, which cost three
+        // forms a wave per SIMD (<2, CountsRT, 2> 4 -> 3, <3, CountsCT<1, 2, 0, 1, 1>, 2> 3 -> 2, <7, CountsRT, 2> 2 -> 1)
         int32_t k = 0;
         for (; k + 1 < K; k += 2) {
             fetch(k + 1, nxt);
@@ -2352,12 +2336,7 @@ __global__ __launch_bounds__(BLOCK_MULTI, (M >= 3 ? MGX_M3_WAVES : 1)) void step
             one_step(k + 1, nxt);
         }
         if (k < K) one_step(k, cur);
-        // (the state columns' addresses are formed again here from an index the compiler cannot see through: held across the loop since the
-        //  prologue's loads they were the registers the three-of-a-kind form spilled)
-        int64_t i_out = i;
-        asm volatile("" : "+v"(i_out));
-        store_multi_state<F, CNT, M>(a, i_out, R);
-        if (out.ret_acc) out.ret_acc[i] += ret;
+        finish_multi_small<F, CNT, M>(a, i, R, out, ret);
     }
     advance_counter_in_kernel(a, K_launch);
 }
@@ -2404,11 +2383,8 @@ __global__ __launch_bounds__(BLOCK_MULTI) void step_lists_small_kernel(const KAr
         if (done) done[i] = dn;
         if constexpr (EP) { off = episode_auto_restart(a, i, t, off, dn != 0); t += off; }  // (the observation: row counter + 1 + offset)
         if (obs) {
-            if (a.obs_state_only == 1 && a.obs_colpitch) {
-                const int64_t P = a.obs_colpitch, k0 = (int64_t)(a.n_load + a.n_pv) * (1 + a.H);
-                if (a.obs_f32) observe_state_multi<F>(a, i, (float *)obs + k0 * P + i, P);
-                else observe_state_multi<F>(a, i, (double *)obs + k0 * P + i, P);
-            } else if (a.obs_f32) observe_row_multi<F>(a, i, t + 1, (float *)obs + i * a.obs_dim);
+            if (obs_is_ring_block(a)) observe_ring_state_multi<F>(a, i, obs);
+            else if (a.obs_f32) observe_row_multi<F>(a, i, t + 1, (float *)obs + i * a.obs_dim);
             else observe_row_multi<F>(a, i, t + 1, (double *)obs + i * a.obs_dim);
         }
     }
@@ -2417,7 +2393,7 @@ __global__ __launch_bounds__(BLOCK_MULTI) void step_lists_small_kernel(const KAr
 
 // mgx_rollout_lists on the register form (round 6): K fused steps whose controls come from a priority list over module instances --
 // RuleBasedControl on a layout with several modules of a kind (rbc.py:64-93; ids [N]: one fixed list per grid) or a discrete roll-out
-// (ids [K, N]).  The loop of step_k_multi_small_kernel with populate_multi_small in place of the action stream: per step only the
+// (ids [K, N]).  The pieces of step_k_multi_small_kernel with populate_multi_small in place of the action stream: per step only the
 // series rows are read.  The list is packed into one 64-bit word (pack_priority_list): once per launch for fixed lists.
 template <int F, class CNT, int M>
 __global__ __launch_bounds__(BLOCK_MULTI, (M >= 3 ? MGX_M3_WAVES : 1)) void rollout_multi_small_kernel(
@@ -2434,7 +2410,7 @@ __global__ __launch_bounds__(BLOCK_MULTI, (M >= 3 ? MGX_M3_WAVES : 1)) void roll
     lds_double *pk = (lds_double *)park + threadIdx.x;
     if (i < a.g1) {
         const int64_t N = a.N;
-        const int32_t k_done = (a.grid_final ? a.grid_final[i] : a.final_step) - 1 - t0;
+        const int32_t k_done = multi_k_done(a, i, t0);
         double ret = 0.0;
         MultiRegsT<M> R; MultiStepInT<M> cur, nxt;
         load_multi_regs<F, CNT, M>(a, i, R);
@@ -2444,11 +2420,7 @@ __global__ __launch_bounds__(BLOCK_MULTI, (M >= 3 ? MGX_M3_WAVES : 1)) void roll
             return pack_priority_list(lists + (int64_t)id * list_len * 3, list_len, CNT::ng(a), CNT::nb(a), CNT::nr(a));
         };
         uint64_t plw = per_step ? 0ull : list_word(ids[i]);
-        if (K > 0) load_multi_series<F, CNT, M>(a, i, t0, cur);
-        auto fetch = [&](int32_t kk, MultiStepInT<M> &dst) __attribute__((always_inline)) {
-            const int32_t kc = kk < K ? kk : K - 1;                  // (past the end: re-read the last step's rows, unconditional loads)
-            load_multi_series<F, CNT, M>(a, i, t0 + kc, dst);
-        };
+        auto fetch = [&](int32_t k, MultiStepInT<M> &dst) __attribute__((always_inline)) { load_multi_series<F, CNT, M>(a, i, t0 + k, dst); };
         auto one_step = [&](int32_t k, MultiStepInT<M> &in) __attribute__((always_inline)) {
             const int64_t off = (int64_t)k * N + i;
             if (per_step) plw = list_word(ids[off]);
@@ -2456,25 +2428,10 @@ __global__ __launch_bounds__(BLOCK_MULTI, (M >= 3 ? MGX_M3_WAVES : 1)) void roll
             Outputs o;
             double *log = out.log ? out.log + (int64_t)k * a.log_dim * N + i : nullptr;
             step_multi_small<F, CNT, M, PARK>(a, R, in, i, false, log, o, pk, xv);
-            const double r = shaped_reward<F>(a.shaper, o);
-            if (out.reward) __builtin_nontemporal_store(r, out.reward + off);
-            if (out.done) out.done[off] = (uint8_t)(k >= k_done);
-            if constexpr (F & F_BATTERY) { if (out.soc_trace) __builtin_nontemporal_store(R.b_soc[0], out.soc_trace + off); }
-            if constexpr (F & F_GENSET) { if (out.status_trace) __builtin_nontemporal_store(R.g_status[0], out.status_trace + off); }
-            ret += r;
+            store_multi_step_out<F, true>(out, off, shaped_reward<F>(a.shaper, o), k >= k_done, (F & F_BATTERY) ? R.b_soc[0] : 0.0, (F & F_GENSET) ? R.g_status[0] : 0u, ret);
         };
-        int32_t k = 0;
-        for (; k + 1 < K; k += 2) {
-            fetch(k + 1, nxt);
-            one_step(k, cur);
-            fetch(k + 2, cur);
-            one_step(k + 1, nxt);
-        }
-        if (k < K) one_step(k, cur);
-        int64_t i_out = i;
-        asm volatile("" : "+v"(i_out));
-        store_multi_state<F, CNT, M>(a, i_out, R);
-        if (out.ret_acc) out.ret_acc[i] += ret;
+        multi_step_pipeline(K, cur, nxt, fetch, one_step);
+        finish_multi_small<F, CNT, M>(a, i, R, out, ret);
     }
     advance_counter_in_kernel(a, K_launch);
 }

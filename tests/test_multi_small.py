@@ -125,6 +125,42 @@ def test_compile_time_counts_equal_run_time_counts(device):
         assert float(o1["reward"].std()) > 0
 
 
+def test_step_k_through_the_shared_kernel_equals_the_register_kernel(device):
+    """mgx_step_k on a small general layout with the tunable multi_small_own = 0 (step_k_multi_kernel: the run-time-count loop around
+    step_multi_core, the state re-read from the columns every step) against multi_small_own = 1 (step_k_multi_small_kernel, run-time
+    counts: multi_static = 0): reward, done, both traces, every log column, the return accumulator and the final state `==`."""
+    import torch
+    from pymgrid_amd import StepEngine, _lib
+    from pymgrid_amd.generator import generate, widen
+    N, K = 200, 5
+    g = torch.Generator(device=device); g.manual_seed(29)
+    acts, res = None, []
+    for own in (1, 0):
+        _lib.set_tunable("multi_static", 0)
+        _lib.set_tunable("multi_small_own", own)
+        try:
+            assert _lib.get_tunable("multi_small_own") == (own, 1)
+            e = StepEngine(widen(generate(N, n_steps=40, seed=7, arch="genset+battery+grid", device=device), n_genset=2, n_battery=2))
+            if acts is None:
+                acts = torch.rand(K, N, e.layout.action_dim, dtype=torch.float64, device=device, generator=g)
+            acc = torch.full((N,), 0.25, dtype=torch.float64, device=device)
+            out = e.step_k(acts, normalized=True, reward=True, done=True, soc_trace=True, status_trace=True, log=True, ret_acc=acc)
+            torch.cuda.synchronize()
+            out = {k: v.clone() for k, v in out.items()}           # (the accumulator among them)
+            for name in ("charge", "soc", "gen_status"):
+                out["state_" + name] = e.batch.cols[name].clone()
+            res.append(out)
+            e.close()
+        finally:
+            _lib.set_tunable("multi_static", 1)
+            _lib.set_tunable("multi_small_own", 1)
+    own, shared = res
+    assert set(own) == set(shared) and {"reward", "done", "soc_trace", "status_trace", "log", "ret_acc"} <= set(own)
+    for k in own:
+        assert own[k].shape == shared[k].shape and bool((own[k] == shared[k]).all()), k
+    assert float(own["reward"].std()) > 0 and not torch.equal(own["ret_acc"], torch.full_like(own["ret_acc"], 0.25))
+
+
 @pytest.mark.gpu
 def test_list_rollouts_on_the_register_form_equal_the_run_time_form(device):
     """mgx_rollout_lists on the compile-time-count specialisations (rollout_multi_small_kernel: the priority-list walk out of registers,

@@ -157,3 +157,53 @@ def test_discrete_steps_of_multi_instance_grids_in_per_grid_windows(device, wind
     for name in ("charge", "soc", "gen_status"):
         assert torch.equal(a.batch.cols[name], b.batch.cols[name])
     a.close(); b.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("columns", [False, True])
+@pytest.mark.parametrize("dt", ["float64", "float32"])
+def test_refill_into_a_ring_off_the_store_alignment(device, dt, columns):
+    """The store phase of a refill (store_window_blocks, shared by obs_windows_k_kernel and obs_windows_k_multi_kernel) on its fallback
+    arms: a ring whose first element lies ONE element into a larger buffer (8 bytes off for doubles, 4 for floats) is not aligned for
+    the 2-element stores -- the row-major blocks go out element by element, the column-major ones a grid per lane -- and must receive
+    exactly what the aligned ring of the same build receives (itself pinned to the per-step rows by the tests above and by
+    test_ring_layout.py), every byte of both buffers compared: the sentinel around the rings, the rows between the batch and the
+    pitch, and the state columns a refill AHEAD of the counter leaves alone.  N = 69: a ragged last group and a last pair with one grid
+    inside the batch; K = 18: a full batch of four blocks and a remainder in wave 0."""
+    from pymgrid_amd import StepEngine
+    from pymgrid_amd.generator import generate, widen
+    dt = getattr(torch, dt)
+    N, K = 69, 18
+
+    def batch():
+        return generate(N, n_steps=40, seed=11, arch="genset+battery+grid", horizon=4, device=device)
+    for multi in (False, True):
+        e = StepEngine(widen(batch(), n_genset=2, n_battery=2, n_grid=1) if multi else batch(), obs_dtype=dt)
+        assert bool(e.layout.multi) == multi
+        pitch = N
+        if columns:
+            pitch = 96
+            e.set_ring_pitch(pitch); e.set_ring_layout(True)
+        e.reset(0, want_obs=False)
+        D, n = e.obs_dim, K * pitch * e.obs_dim
+
+        def ring_at(buf, first):
+            flat = buf[first:first + n]
+            return flat.view(K, D, pitch)[:, :, :N].transpose(1, 2) if columns else flat.view(K, pitch, D)[:, :N]
+        for ahead in (False, True):
+            bufs = [torch.full((n + 8,), -7.5, dtype=dt, device=device) for _ in range(2)]
+            rings = [ring_at(bufs[0], 0), ring_at(bufs[1], 1)]
+            esz = bufs[0].element_size()
+            assert rings[0].data_ptr() % 16 == 0 and rings[1].data_ptr() % (2 * esz) == esz
+            for ring in rings:
+                e._check_ring(ring)                                # the view off the alignment is a ring like any other
+                if ahead:
+                    e.observe_windows_ahead(K, ring); e.prefetch_wait()
+                else:
+                    e.observe_windows(K, ring)
+            torch.cuda.synchronize()
+            assert torch.equal(bufs[0][:n], bufs[1][1:1 + n]), (multi, ahead)
+            assert bool((bufs[0][n:] == -7.5).all()) and bool((bufs[1][:1] == -7.5).all()) and bool((bufs[1][1 + n:] == -7.5).all())
+            written = bufs[0][:n] != -7.5
+            assert bool(written.any()) and (ahead or columns or bool(written.all()))      # (dense row-major rings at the counter: every element)
+        e.close()
