@@ -515,19 +515,43 @@ class StepEngine:
         self._call(self._lib.mgx_action_bounds, lo.data_ptr(), hi.data_ptr())
         return lo, hi
 
+    def _step_outputs(self, out, want_done, want_obs, want_log, want_control=False, lead=()):
+        """The outputs of a single-step call (``lead = (K,)``: of the K steps of ``step_many``): (reward, done, obs, log, control) --
+        each tensor taken from ``out``, allocated, or None where it is not asked for.  Written flat: every unbound env step and every
+        per-grid-episode fleet step passes here."""
+        reward = done = obs = log = control = None
+        if out:
+            reward, done, obs, log, control = out.get("reward"), out.get("done"), out.get("obs"), out.get("log"), out.get("control")
+        if reward is None:
+            reward = self._empty(*lead, self.N)
+        if not want_done:
+            done = None
+        elif done is None:
+            done = self._empty(*lead, self.N, dtype=torch.uint8)
+        if not want_obs:
+            obs = None
+        elif not lead:
+            obs = self._obs_buf(obs)
+        elif obs is None:
+            obs = self._empty(*lead, self.N, self.obs_dim, dtype=self.obs_dtype)
+        if not want_log:
+            log = None
+        elif log is None:
+            log = self._empty(*lead, self.log_dim, self.N)
+        if not want_control:
+            control = None
+        elif control is None:
+            control = self._empty(self.N, self.action_dim)
+        return reward, done, obs, log, control
+
     def step_many(self, actions, normalized=True, want_obs=False, want_log=False, done=True, out=None):
         """K single-step launches issued by one call (``mgx_step_many``): actions [K, N, A] -> reward [K, N], done [K, N],
         optionally obs [K, N, D] and log [K, L, N]."""
         K = int(actions.shape[0])
         actions = self._check_actions(actions, (K,))
-        out = out or {}
-        reward = out.get("reward") if out.get("reward") is not None else self._empty(K, self.N)
-        d = (out.get("done") if out.get("done") is not None else self._empty(K, self.N, dtype=torch.uint8)) if done else None
         if want_obs and getattr(self, "_obs_compact", False):
             raise ValueError("step_many writes whole rows per step: not offered with compact state rows")
-        obs = (out.get("obs") if out.get("obs") is not None
-               else torch.empty((K, self.N, self.obs_dim), dtype=self.obs_dtype, device=self.device)) if want_obs else None
-        log = (out.get("log") if out.get("log") is not None else self._empty(K, self.log_dim, self.N)) if want_log else None
+        reward, d, obs, log, _ = self._step_outputs(out, done, want_obs, want_log, lead=(K,))
         self._call(self._lib.mgx_step_many, _ptr(actions), K, 1 if normalized else 0, reward.data_ptr(), _ptr(d), _ptr(obs),
                    _ptr(log))
         if self._t is not None:
@@ -544,20 +568,7 @@ class StepEngine:
         preallocated ``obs`` / ``reward`` / ``done`` / ``log`` tensors.  ``want_done=False``: no per-grid done bytes are
         written (in lock-step `done` is the same for every grid: ``done_steps``)."""
         actions = self._check_actions(actions, ())
-        reward = done = obs = log = None
-        if out:
-            reward, done, obs, log = out.get("reward"), out.get("done"), out.get("obs"), out.get("log")
-        if reward is None:
-            reward = self._empty(self.N)
-        if not want_done:
-            done = None
-        elif done is None:
-            done = self._empty(self.N, dtype=torch.uint8)
-        obs = self._obs_buf(obs) if want_obs else None
-        if not want_log:
-            log = None
-        elif log is None:
-            log = self._empty(self.log_dim, self.N)
+        reward, done, obs, log, _ = self._step_outputs(out, want_done, want_obs, want_log)
         self._call(self._lib.mgx_step, _ptr(actions), 1 if normalized else 0, reward.data_ptr(), _ptr(done),
                    _ptr(obs), _ptr(log))
         if self._t is not None:
@@ -625,13 +636,7 @@ class StepEngine:
         if action_id.dtype != torch.int32 or tuple(action_id.shape) != (self.N,) or action_id.device != self.device:
             raise ValueError(f"action_id must be an int32 tensor of shape ({self.N},) on {self.device}")
         tptr, n_lists = self._table_ptr(table)
-        out = out or {}
-        reward = out.get("reward") if out.get("reward") is not None else self._empty(self.N)
-        done = (out.get("done") if out.get("done") is not None else self._empty(self.N, dtype=torch.uint8)) if want_done else None
-        obs = self._obs_buf(out.get("obs")) if want_obs else None
-        log = (out.get("log") if out.get("log") is not None else self._empty(self.log_dim, self.N)) if want_log else None
-        control = (out.get("control") if out.get("control") is not None
-                   else self._empty(self.N, self.action_dim)) if want_control else None
+        reward, done, obs, log, control = self._step_outputs(out, want_done, want_obs, want_log, want_control)
         self._call(self._lib.mgx_step_discrete, _ptr(action_id), tptr, n_lists,
                    _ptr(control), reward.data_ptr(), _ptr(done), _ptr(obs), _ptr(log))
         if self._t is not None:
@@ -647,10 +652,7 @@ class StepEngine:
         if lists.dtype != torch.int32 or lists.dim() != 3 or lists.shape[2] != 3 or lists.device != self.device or not lists.is_contiguous():
             raise ValueError(f"lists must be a contiguous int32 tensor [n_lists, list_len, 3] on {self.device}")
         out = out or {}
-        reward = out.get("reward") if out.get("reward") is not None else self._empty(self.N)
-        done = (out.get("done") if out.get("done") is not None else self._empty(self.N, dtype=torch.uint8)) if want_done else None
-        obs = self._obs_buf(out.get("obs")) if want_obs else None
-        log = (out.get("log") if out.get("log") is not None else self._empty(self.log_dim, self.N)) if want_log else None
+        reward, done, obs, log, _ = self._step_outputs(out, want_done, want_obs, want_log)
         L = self.layout
         one_launch = L.multi and max(L.n_genset, L.n_battery, L.n_grid, L.n_load, L.n_pv) <= 2 and min(L.n_load, L.n_pv) >= 1
         control = None

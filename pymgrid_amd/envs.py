@@ -18,6 +18,8 @@ Differences that are deliberate:
   * the flat observation order is fixed: load, pv, genset, battery, grid (the reference leaves it to gym's
     ``Dict`` ordering); ``info`` holds batched log columns instead of per-module dict lists.
 """
+import ctypes as C
+
 import numpy as np
 import torch
 
@@ -34,6 +36,18 @@ class MicrogridAssertion(AssertionError, ValueError):
     [0, 1], genset_module.py:146-147; a sink with a negative limit asked to absorb, base_module.py:272; the asserts of
     ``_populate_action``, priority_list.py:73-154).  Also a ValueError: the dry run of ``raise_errors=True`` reports every
     refusal through one exception family."""
+
+
+def _as_ids(action_id, device, N=None, dtype=torch.int32):
+    """Priority-list ids as the engine takes them: a contiguous ``dtype`` (int32) tensor on ``device``, out of whatever holds them (a
+    list, a numpy array, a tensor of another dtype, device or stride); with ``N``, a shape other than ``[N]`` is refused.  The lean
+    per-step paths test inline whether the ids are right already and come here only when they are not."""
+    if not torch.is_tensor(action_id):
+        action_id = torch.as_tensor(np.asarray(action_id), device=device)
+    action_id = action_id.to(device=device, dtype=dtype).contiguous()
+    if N is not None and action_id.shape != (N,):
+        raise ValueError(f"action_id must be an int32 tensor of shape ({N},) on {device}")
+    return action_id
 
 
 class ObsViews:
@@ -275,6 +289,22 @@ class BatchedMicrogridEnv:
                     and not (isinstance(self, DiscreteBatchedMicrogridEnv) and self.layout.multi)
                     and not (self._ring is not None and (self._ring_phase or e._window_start is not None)))
 
+    def _env_plan(self, slots):
+        """The ``mgx_env_plan`` over ``slots`` (whose reward / done / obs pointers are the caller's decision: this env's own rotating
+        buffers, or a fleet's): struct size, the three ring pointers where the handle walks rings and a discrete env's priority-list
+        table.  Returns (plan, K) -- K the ring depth the handle walks, 0 without rings."""
+        plan = _lib.EnvPlan()
+        plan.struct_size = C.sizeof(_lib.EnvPlan)
+        K = self.obs_prefetch if self._ring is not None else 0
+        plan.n_slots, plan.slots, plan.ring_K = len(slots), slots, K
+        if K:
+            for r in range(3):
+                plan.rings[r] = self._rings[r].data_ptr()
+        table = getattr(self, "_table", None)
+        if table is not None:
+            plan.table, plan.n_actions = self.engine._table_ptr(table)
+        return plan, K
+
     def _unbind_fast(self):
         """Back to per-call bookkeeping: the Python-side positions take over from where the handle stands."""
         if self._fleet_ref is not None:            # (a fleet's bound step may hold this env's handle: the fleet hands everything back)
@@ -293,7 +323,6 @@ class BatchedMicrogridEnv:
     def _rebind_fast(self):
         """(Re)bind the env's rotating buffers to the handle at the env's CURRENT position; called at the end of everything that
         changes them (construction, resets, set_obs_prefetch).  Leaves ``_fp`` None where a step needs host work."""
-        import ctypes as C
         self._unbind_fast()
         if not self._fast_eligible():
             return
@@ -308,18 +337,7 @@ class BatchedMicrogridEnv:
             slots[k].reward = self._rew_bufs[k].data_ptr()
             slots[k].done = self._done_bufs[k].data_ptr() if pergrid else None
             slots[k].obs = self._obs_bufs[k].data_ptr() if (self._obs_bufs is not None and self._ring is None and self._observations) else None
-        plan = _lib.EnvPlan()
-        plan.struct_size = C.sizeof(_lib.EnvPlan)
-        plan.n_slots, plan.slots = R, slots
-        K = self.obs_prefetch if self._ring is not None else 0
-        plan.ring_K = K
-        if K:
-            for r in range(3):
-                plan.rings[r] = self._rings[r].data_ptr()
-        table = getattr(self, "_table", None)
-        if table is not None:
-            tptr, n_lists = e._table_ptr(table)
-            plan.table, plan.n_actions = tptr, n_lists
+        plan, K = self._env_plan(slots)
         if e._lib.mgx_env_bind(e._h, C.byref(plan)):
             return                                 # (a mode the handle walks no rings in: per-call bookkeeping stays)
         if e._lib.mgx_env_seek(e._h, self._out_pos, self._ring_idx if K else 0, self._ring_pos if K else 0):
@@ -346,7 +364,6 @@ class BatchedMicrogridEnv:
 
     def _resync_fast(self, fp):
         """The Python mirror of the bound step's position, re-read from the handle (mgx_env_position, mgx_current_step)."""
-        import ctypes as C
         e = self.engine
         s_, r_, p_ = C.c_int32(0), C.c_int32(0), C.c_int32(0)
         if e._lib.mgx_env_position(e._h, C.byref(s_), C.byref(r_), C.byref(p_)):
@@ -775,6 +792,24 @@ class BatchedMicrogridEnv:
             return obs
         return obs.index_select(1, self._obs_index)
 
+    def _step_targets(self):
+        """In front of the launch of an unbound step: (want_obs, out, dconst) -- where the step writes (``_obs_target``) and its
+        lock-step `done` (``_lockstep_done``; None: the kernel writes the flags)."""
+        want_obs, out = self._obs_target()
+        return want_obs, out, self._lockstep_done()
+
+    def _step_end(self, obs, reward, done, log, dconst):
+        """Behind the launch of an unbound step: the ring / state-buffer walk, the log rows kept, the observation columns selected and
+        `done` -- in lock-step the constant tensor, else the kernel's 0/1 bytes reinterpreted (no conversion kernel).  Returns what
+        ``step`` returns."""
+        obs = self._obs_after(obs)
+        info = {}
+        if log is not None:
+            self._log_rows.append(log)
+            self._shaped_rows.append(reward.clone())
+            info["log"] = log
+        return self._select_obs(obs), reward, (dconst if dconst is not None else done.view(torch.bool)), info
+
     def step(self, action, normalized=True):
         """action: tensor [N, A] of the env's ``action_dtype`` (float64 by default; columns ``layout.action_names``) or
         a control dict as taken by ``Microgrid.run``.  Returns (obs [N, D], reward [N], done [N] bool, info)."""
@@ -791,18 +826,9 @@ class BatchedMicrogridEnv:
                 return self._step_fast(fp, fp.fn, (fp.h, action.data_ptr(), 1 if normalized else 0))
         if self.raise_errors:             # dry run first (mgx_check_step): a refused request raises BEFORE anything is applied
             self._raise_on_violations(self.engine.check_step(action, normalized=normalized))
-        want_obs, out = self._obs_target()
-        dconst = self._lockstep_done()
-        obs, reward, done, log = self.engine.step(action, normalized=normalized, want_obs=want_obs,
-                                                  want_log=self._keep_log, out=out, want_done=dconst is None)
-        obs = self._obs_after(obs)
-        info = {}
-        if log is not None:
-            self._log_rows.append(log)
-            self._shaped_rows.append(reward.clone())
-            info["log"] = log
-        # lock-step: a constant tensor; else 0/1 bytes reinterpreted, no conversion kernel
-        return self._select_obs(obs), reward, (dconst if dconst is not None else done.view(torch.bool)), info
+        want_obs, out, dconst = self._step_targets()
+        return self._step_end(*self.engine.step(action, normalized=normalized, want_obs=want_obs, want_log=self._keep_log, out=out,
+                                                want_done=dconst is None), dconst)
 
     _VIOLATIONS = ((1, "Genset", "supply requested value as a source (outside [min_production, max_production])"),
                    (2, "BatteryModule", "supply / absorb requested value (above max_production / max_consumption)"),
@@ -1019,9 +1045,7 @@ class DiscreteBatchedMicrogridEnv(BatchedMicrogridEnv):
     def get_action(self, action_id, violations=None):
         """DiscreteMicrogridEnv._get_action: ids [N] -> unnormalised control [N, A].  ``violations``: optional int32 [N] tensor
         for the states in which the reference's ``_populate_action`` asserts (``engine.expand_discrete``)."""
-        if not torch.is_tensor(action_id):
-            action_id = torch.as_tensor(np.asarray(action_id), device=self.batch.device)
-        action_id = action_id.to(device=self.batch.device, dtype=torch.int32).contiguous()
+        action_id = _as_ids(action_id, self.batch.device, self.n_grids)
         if self._instances:
             return self.engine.expand_lists(action_id, self._lists, violations=violations)
         return self.engine.expand_discrete(action_id, self._table, violations=violations)
@@ -1039,28 +1063,13 @@ class DiscreteBatchedMicrogridEnv(BatchedMicrogridEnv):
             if not self._instances or self.raise_errors or self._views or self._fleet_owned or self._fp is not None:
                 return super().step(self.get_action(action_id), normalized=False)
             # priority lists over module instances: expansion and step in one call (mgx_step_lists: one launch for two of a kind)
-            if not (torch.is_tensor(action_id) and action_id.dtype == torch.int32 and action_id.is_contiguous()
-                    and action_id.device == self.batch.device):
-                action_id = torch.as_tensor(np.asarray(action_id.cpu() if torch.is_tensor(action_id) else action_id),
-                                            device=self.batch.device).to(torch.int32).contiguous()
-            if action_id.shape != (self.n_grids,):
-                raise ValueError(f"action_id must be an int32 tensor of shape ({self.n_grids},) on {self.batch.device}")
-            want_obs, out = self._obs_target()
-            dconst = self._lockstep_done()
-            obs, reward, done, log = self.engine.step_lists(action_id, self._lists, want_obs=want_obs, want_log=self._keep_log, out=out,
-                                                            want_done=dconst is None)
-            obs = self._obs_after(obs)
-            info = {}
-            if log is not None:
-                self._log_rows.append(log)
-                self._shaped_rows.append(reward.clone())
-                info["log"] = log
-            return self._select_obs(obs), reward, (dconst if dconst is not None else done.view(torch.bool)), info
+            action_id = _as_ids(action_id, self.batch.device, self.n_grids)
+            want_obs, out, dconst = self._step_targets()
+            return self._step_end(*self.engine.step_lists(action_id, self._lists, want_obs=want_obs, want_log=self._keep_log, out=out,
+                                                          want_done=dconst is None), dconst)
         if not (torch.is_tensor(action_id) and action_id.dtype == torch.int32 and action_id.is_contiguous()
                 and action_id.device == self.batch.device):
-            if not torch.is_tensor(action_id):
-                action_id = torch.as_tensor(np.asarray(action_id), device=self.batch.device)
-            action_id = action_id.to(device=self.batch.device, dtype=torch.int32).contiguous()
+            action_id = _as_ids(action_id, self.batch.device, self.n_grids)
         if self.check_asserts:
             self._raise_on_violations(self.engine.check_discrete(action_id, self._table), asserts_only=not self.raise_errors)
         fp = self._fp
@@ -1071,17 +1080,10 @@ class DiscreteBatchedMicrogridEnv(BatchedMicrogridEnv):
                 if action_id.shape != (self.n_grids,) or action_id.get_device() != fp.dev:
                     raise ValueError(f"action_id must be an int32 tensor of shape ({self.n_grids},) on {self.batch.device}")
                 return self._step_fast(fp, fp.fn_discrete, (fp.h, action_id.data_ptr()))
-        want_obs, out = self._obs_target()
-        dconst = self._lockstep_done()
-        obs, reward, done, log, _ = self.engine.step_discrete(action_id, self._table, want_obs=want_obs,
-                                                              want_log=self._keep_log, out=out, want_done=dconst is None)
-        obs = self._obs_after(obs)
-        info = {}
-        if log is not None:
-            self._log_rows.append(log)
-            self._shaped_rows.append(reward.clone())
-            info["log"] = log           # (an expanded priority list never asks a module for more than it can do: nothing to refuse)
-        return self._select_obs(obs), reward, (dconst if dconst is not None else done.view(torch.bool)), info
+        want_obs, out, dconst = self._step_targets()
+        # (an expanded priority list never asks a module for more than it can do: nothing to refuse)
+        return self._step_end(*self.engine.step_discrete(action_id, self._table, want_obs=want_obs, want_log=self._keep_log, out=out,
+                                                         want_done=dconst is None)[:4], dconst)
 
     def sample_action(self, generator=None):
         return torch.randint(0, self.action_space.n, (self.n_grids,), dtype=torch.int32, device=self.batch.device,

@@ -8,6 +8,7 @@ chunks inside the step launches (``refill="chunks"``): 29.5-32 / 33-35 us per 10
 streams (``streams=True``: fork / join events around every bucket, one ``env.step`` each) were measured 2.7x slower than
 back-to-back launches at 33k grids per bucket (host-bound) and only pay for many tiny buckets.
 """
+import ctypes as C
 import os
 
 import numpy as np
@@ -16,12 +17,25 @@ import torch
 from . import _lib
 from .batch import MicrogridBatch
 from .engine import _raw_stream
-from .envs import BatchedMicrogridEnv, DiscreteBatchedMicrogridEnv, ObsViews
+from .envs import BatchedMicrogridEnv, DiscreteBatchedMicrogridEnv, ObsViews, _as_ids
 from .scenario import bucket_by_layout
 
 
 def L_multi(layout):
     return layout.multi
+
+
+def _fleet_step(e0, items, n, normalized):
+    """``mgx_fleet_step`` over the first ``n`` of ``items`` on torch's current stream of the device of ``e0`` (the first item's
+    engine); a failed call raises.  Kept as lean as ``StepEngine._call``: the fast fleet step passes here."""
+    idx = e0._dev_index
+    if e0._only_device or torch.cuda.current_device() == idx:
+        rc = e0._lib.mgx_fleet_step(items, n, 1 if normalized else 0, _raw_stream(idx))
+    else:
+        with torch.cuda.device(idx):
+            rc = e0._lib.mgx_fleet_step(items, n, 1 if normalized else 0, _raw_stream(idx))
+    if rc:
+        _lib.check(rc)
 
 
 class _BoundFleet:
@@ -160,7 +174,6 @@ class BucketedFleet:
         ``reuse_outputs``, on the output slot): the filled-in ``mgx_fleet_item`` array (all but the action pointers), the
         observation views the step returns and the ring state after it.  A fleet that walks its rings in lock-step meets
         3 K such situations, so after the first lap a step costs a dictionary look-up instead of ~25 us of bookkeeping."""
-        import ctypes as C
         states, slot = key
         n = len(self.envs)
         items = (_lib.FleetItem * n)()
@@ -230,48 +243,26 @@ class BucketedFleet:
         for k, (it, env, a) in enumerate(zip(items, envs, actions)):
             e = env.engine
             if it.table:                          # discrete bucket: priority-list ids
-                if not (torch.is_tensor(a) and a.dtype == torch.int32 and a.is_contiguous() and a.device == e.device
-                        and a.shape == (e.N,)):
-                    a = torch.as_tensor(np.asarray(a.cpu() if torch.is_tensor(a) else a), device=e.device).to(torch.int32).contiguous()
+                a = _as_ids(a, e.device)          # (no N: a BucketedFleet step does not check the ids' length)
                 it.action_id = a.data_ptr()
             else:
                 a = e._check_actions(a, ())
                 it.actions = None if a is None else a.data_ptr()
             obs, fresh = obs_plan[k]
-            if fresh:
-                obs = e._obs_buf(None)
-                it.obs = obs.data_ptr()
             dconst = env._lockstep_done()        # lock-step: `done` is a constant tensor, the kernel writes no flags
-            if R:
-                reward, done = fixed_out[k]
-                it.done = None if dconst is not None else done.data_ptr()
-            else:
-                reward = e._empty(e.N)
-                it.reward = reward.data_ptr()
-                if dconst is None:
-                    d8 = e._empty(e.N, dtype=torch.uint8)
-                    it.done = d8.data_ptr()
-                    done = d8.view(torch.bool)
-                else:
-                    it.done = None
-            if dconst is not None:
-                done = dconst
+            # (rotating output buffers: reward and done, as the bool view a step returns, are part of the plan)
+            out = dict(reward=fixed_out[k][0], done=fixed_out[k][1]) if R else None
+            reward, done, row, log, _ = e._step_outputs(out, dconst is None, fresh, env._keep_log)
+            if fresh:
+                obs = row
+                it.obs = obs.data_ptr()
+            it.reward = reward.data_ptr()
+            it.done = None if done is None else done.data_ptr()
             if env._keep_log:
-                log = e._empty(e.log_dim, e.N)
                 it.log = log.data_ptr()
-                info_l.append({"log": log})
-            else:
-                info_l.append({})
-            obs_l.append(obs); reward_l.append(reward); done_l.append(done)
-        e0 = envs[0].engine
-        idx = e0._dev_index
-        if e0._only_device or torch.cuda.current_device() == idx:
-            rc = e0._lib.mgx_fleet_step(items, len(envs), 1 if normalized else 0, _raw_stream(idx))
-        else:
-            with torch.cuda.device(idx):
-                rc = e0._lib.mgx_fleet_step(items, len(envs), 1 if normalized else 0, _raw_stream(idx))
-        if rc:
-            _lib.check(rc)
+            info_l.append({"log": log} if env._keep_log else {})
+            obs_l.append(obs); reward_l.append(reward); done_l.append(dconst if dconst is not None else done.view(torch.bool))
+        _fleet_step(envs[0].engine, items, len(envs), normalized)
         self._n_steps += 1
         for k, env in enumerate(envs):
             if env.engine._t is not None:
@@ -306,22 +297,14 @@ class BucketedFleet:
                 it.done = done_l[k].data_ptr()
             if it.table:                          # discrete bucket: priority-list ids
                 if not (torch.is_tensor(a) and a.dtype == torch.int32 and a.is_contiguous() and a.is_cuda and a.shape == (env.n_grids,)):
-                    a = torch.as_tensor(np.asarray(a.cpu() if torch.is_tensor(a) else a), device=env.batch.device).to(torch.int32).contiguous()
+                    a = _as_ids(a, env.batch.device)
                     keep = (keep or []) + [a]
                 it.action_id = a.data_ptr()
             else:
                 if not (a.dtype == e.action_dtype and a.shape == e._action_shape and a.is_contiguous() and a.is_cuda):
                     a = e._check_actions(a, ())   # raises with the full message
                 it.actions = a.data_ptr()
-        e0 = envs[0].engine
-        idx = e0._dev_index
-        if e0._only_device or torch.cuda.current_device() == idx:
-            rc = e0._lib.mgx_fleet_step(items, n, 1 if normalized else 0, _raw_stream(idx))
-        else:
-            with torch.cuda.device(idx):
-                rc = e0._lib.mgx_fleet_step(items, n, 1 if normalized else 0, _raw_stream(idx))
-        if rc:
-            _lib.check(rc)
+        _fleet_step(envs[0].engine, items, n, normalized)
         self._n_steps += 1
         for env, st in sync:                      # (the ring / state-buffer position after the step: BatchedMicrogridEnv._set_plan_state)
             if st[0] == "v":
@@ -354,7 +337,6 @@ class BucketedFleet:
     def _try_bind(self):
         """Bind every bucket's handle at the fleet's CURRENT position (mgx_env_bind + mgx_env_seek).  Returns the _BoundFleet or None
         (then the per-step plans of _step_fused stay in charge)."""
-        import ctypes as C
         if not self._bind_eligible():
             self._bind_ok = False                         # (until something moves an env: _invalidate_bound)
             return None
@@ -365,7 +347,6 @@ class BucketedFleet:
         done_ok = []
         for k, env in enumerate(envs):
             e = env.engine
-            K = env.obs_prefetch if env._ring is not None else 0
             slots = (_lib.EnvSlot * R)()
             for j in range(R):
                 slots[j].reward = self._out_reward[k][j].data_ptr()
@@ -376,15 +357,7 @@ class BucketedFleet:
                     slots[j].obs = self._out_obs[k][j].data_ptr()
                 else:
                     slots[j].obs = None
-            plan = _lib.EnvPlan()
-            plan.struct_size = C.sizeof(_lib.EnvPlan)
-            plan.n_slots, plan.slots, plan.ring_K = R, slots, K
-            if K:
-                for r in range(3):
-                    plan.rings[r] = env._rings[r].data_ptr()
-            table = getattr(env, "_table", None)
-            if table is not None:
-                plan.table, plan.n_actions = e._table_ptr(table)
+            plan, K = env._env_plan(slots)
             keep.append((slots, plan))
             if e._lib.mgx_env_bind(e._h, C.byref(plan)) or \
                     e._lib.mgx_env_seek(e._h, slot0, env._ring_idx if K else 0, env._ring_pos if K else 0):
@@ -445,7 +418,7 @@ class BucketedFleet:
             a = actions[k]
             if not (torch.is_tensor(a) and a.dtype == adt[k] and a.shape == ashape[k] and a.is_contiguous() and a.is_cuda):
                 if adt[k] == torch.int32 and getattr(envs[k], "_table", None) is not None:
-                    a = torch.as_tensor(np.asarray(a.cpu() if torch.is_tensor(a) else a), device=envs[k].batch.device).to(torch.int32).contiguous()
+                    a = _as_ids(a, envs[k].batch.device)
                 else:
                     a = envs[k].engine._check_actions(a, ())      # converts, or raises with the full message
                 keep = (keep or []) + [a]
@@ -630,50 +603,63 @@ class PerGridWindowEnv:
     def step(self, action, **kw):
         if not self.auto_reset:
             return self.env.step(action, **kw)
+        path, final, res = self._before_launch(lambda: self.env.step(action, **kw))
+        return self._after_launch(path, final, *res)
+
+    # ---- one per-grid-episode step around a launch the caller supplies: env.step here, a PerGridWindowFleet's one mgx_fleet_step call
+    # for all its buckets there (between every bucket's _before_launch and, in bucket order, every bucket's _after_launch) ---------------
+    def _before_launch(self, prepare):
+        """In front of the launch: decide the path, take and set the final-observation buffer, and run ``prepare()`` -- the caller's
+        part that asks the env where its step writes (``_step_targets``), the launch itself included or not -- with the rows set
+        aside where they come from the observe pass behind the restarts.  Paths: "plain" (``auto_reset=False``: nothing around the
+        step); "ring" / "inline" (device draws in place: the step kernel restarts the grids it finishes -- with rings it adds the
+        state columns to the ring's row and the window columns of the restarted grids in the rest of the ring are patched behind it,
+        two launches; without, one launch); "host" (the restarts follow the step: ``mgx_reset_grids_random``, or a torch generator's
+        draws).  Returns (path, final, prepare's result)."""
         env = self.env
-        if self.native and self._device_draws and env._ring is not None:
-            # rings: the step kernel restarts the grids it finishes and adds the state columns to the ring's row; the window columns
-            # of the restarted grids in the rest of the ring are then patched (mgx_patch_windows): two launches
-            final = None
-            if self.final_observation:       # the patch saves the rows it is about to replace (the finished grids' only)
+        path, final, want_rows = "plain", None, env._observations
+        if self.auto_reset and self.native and self._device_draws:
+            path = "ring" if env._ring is not None else "inline"
+            # (rings: the patch saves the rows it is about to replace, the finished grids' only)
+            if self.final_observation and (path == "ring" or want_rows):
                 final = self._next_final_buf()
                 env.engine.set_final_obs(final)
-            obs, reward, done, info = env.step(action, **kw)
-            obs = env._rows_after_restart(done.view(torch.uint8), True)
-            if final is not None:
-                info = dict(info, final_observation=env._select_obs(final))
-            return obs, reward, done, info
-        if self.native and self._device_draws:            # one launch: the step kernel restarts the grids it finishes
-            final = None
-            if self.final_observation and env._observations:
-                final = self._next_final_buf()
-                env.engine.set_final_obs(final)
-            obs, reward, done, info = env.step(action, **kw)
-            if final is not None:
-                info = dict(info, final_observation=env._select_obs(final))
-            return obs, reward, done, info
-        want_rows = env._observations
-        if want_rows and not self.final_observation and env._ring is None:   # the rows come from the observe pass behind the restarts
-            env._observations = False
+        elif self.auto_reset:
+            path = "host"
+            if want_rows and not self.final_observation and env._ring is None:
+                env._observations = False
         try:
-            obs, reward, done, info = env.step(action, **kw)
+            return path, final, prepare()
         finally:
             env._observations = want_rows
-        final = obs.clone() if (self.final_observation and obs is not None) else None     # (a ring view: patched below)
-        if self._device_draws:
-            if self.lengths is None:
-                self.lengths = torch.full_like(self.starts, self.length if self.length is not None else 0)
-            new_obs = env.reset_grids_random(done, self.seed, self.length or 0, lengths_out=self.lengths)
-            self.starts = env.engine._window_start          # updated in place by the kernel
-        else:
-            starts, lengths = self.draw()                  # a draw per grid; only the finished grids take theirs
-            new_obs = env.reset_grids(done, starts, lengths, validate=False)
-            self.starts = torch.where(done, starts, self.starts)
-            if lengths is not None:
-                self.lengths = torch.where(done, lengths, self.lengths)
-        if self.final_observation:
-            info = dict(info, final_observation=final)
-        return (new_obs if new_obs is not None else obs), reward, done, info
+
+    def _after_launch(self, path, final, obs, reward, done, info):
+        """Behind the launch, given what the env's step returned: the ring rows patched, ``info["final_observation"]``, the host
+        restarts -- drawn on the device or by the generator (a draw per grid; only the finished grids take theirs) -- and ``starts`` /
+        ``lengths`` kept current.  Returns what ``step`` returns."""
+        env = self.env
+        if path == "ring":
+            obs = env._rows_after_restart(done.view(torch.uint8), True)
+        elif path == "host":
+            final = obs.clone() if (self.final_observation and obs is not None) else None     # (a ring view: patched below)
+            if self._device_draws:
+                if self.lengths is None:
+                    self.lengths = torch.full_like(self.starts, self.length if self.length is not None else 0)
+                new_obs = env.reset_grids_random(done, self.seed, self.length or 0, lengths_out=self.lengths)
+                self.starts = env.engine._window_start          # updated in place by the kernel
+            else:
+                starts, lengths = self.draw()
+                new_obs = env.reset_grids(done, starts, lengths, validate=False)
+                self.starts = torch.where(done, starts, self.starts)
+                if lengths is not None:
+                    self.lengths = torch.where(done, lengths, self.lengths)
+            if new_obs is not None:
+                obs = new_obs
+            if self.final_observation:
+                info = dict(info, final_observation=final)
+        if path in ("ring", "inline") and final is not None:
+            info = dict(info, final_observation=env._select_obs(final))
+        return obs, reward, done, info
 
     # what differs between the two fused calls in _fused_refusal: the env class the call belongs to, its first line, the lock-step
     # call auto_reset=False points to, whether check_asserts refuses (the continuous env has none) and the wording
@@ -708,12 +694,6 @@ class PerGridWindowEnv:
         if not (self.native and self._device_draws):
             return f"native=False: {k['what']} {k['verb']} in-place episodes"
         return None
-
-    def _rollout_refusal(self):
-        return self._fused_refusal("rollout")
-
-    def _step_k_refusal(self):
-        return self._fused_refusal("step_k")
 
     def _rows_refusal(self):
         """Why ``rollout`` / ``step_k`` write no observation rows on this env (None: they do)."""
@@ -777,9 +757,7 @@ class PerGridWindowEnv:
             raise RuntimeError("rollout() before reset()")
         env = self.env
         dev = self.full.device
-        if not torch.is_tensor(action_id):
-            action_id = torch.as_tensor(np.asarray(action_id), device=dev)
-        ids = action_id.to(device=dev, dtype=torch.uint8).contiguous()
+        ids = _as_ids(action_id, dev, dtype=torch.uint8)
         if ids.dim() == 2:
             if K is not None and int(K) != ids.shape[0]:
                 raise ValueError(f"action_id holds {ids.shape[0]} steps, K = {K}")
@@ -963,13 +941,7 @@ class PerGridWindowFleet:
     def sample_action(self, generator=None):
         return [pe.sample_action(generator=generator) for pe in self.envs]
 
-    def scatter(self, per_bucket):
-        """[tensor [n_b, ...] per bucket] -> one tensor [N, ...] in fleet order (as ``BucketedFleet.scatter``)."""
-        first = per_bucket[0]
-        out = torch.empty((self.n_grids,) + tuple(first.shape[1:]), dtype=first.dtype, device=first.device)
-        for idx, v in zip(self.index, per_bucket):
-            out[idx] = v
-        return out
+    scatter = BucketedFleet.scatter           # [tensor [n_b, ...] per bucket] -> one tensor [N, ...] in fleet order
 
     def step(self, actions, normalized=True):
         """actions: list with one entry per bucket (continuous controls [n_k, A] or priority-list ids [n_k]).  Returns
@@ -985,15 +957,7 @@ class PerGridWindowFleet:
             plans[k] = self._before(pe, actions[k], it)
             used.append(k)
         if used:
-            e0 = self.envs[used[0]].env.engine
-            idx = e0._dev_index
-            if e0._only_device or torch.cuda.current_device() == idx:
-                rc = e0._lib.mgx_fleet_step(items, len(used), 1 if normalized else 0, _raw_stream(idx))
-            else:
-                with torch.cuda.device(idx):
-                    rc = e0._lib.mgx_fleet_step(items, len(used), 1 if normalized else 0, _raw_stream(idx))
-            if rc:
-                _lib.check(rc)
+            _fleet_step(self.envs[used[0]].env.engine, items, len(used), normalized)
         out = []
         for k, pe in enumerate(self.envs):        # bucket order: a torch generator's draws come in the order of the twins' steps
             if plans[k] is None:
@@ -1033,97 +997,43 @@ class PerGridWindowFleet:
         self._refuse_fused("step_k", "actions_list", actions_list, kw)
         return [pe.step_k(a, **kw) for pe, a in zip(self.envs, actions_list)]
 
-    # ---- one bucket's PerGridWindowEnv.step, around the fleet's C call ------------------------------------------------------------
+    # ---- the fleet's own part of one bucket's step, inside PerGridWindowEnv._before_launch / in front of its _after_launch -------------
     def _before(self, pe, action, it):
-        """What ``PerGridWindowEnv.step`` / the env's ``step`` do before their launch, with the launch's arguments written into the
-        ``mgx_fleet_item`` ``it`` instead.  Returns what ``_after`` needs."""
-        import ctypes as C
+        """The arguments of the bucket's launch written into the ``mgx_fleet_item`` ``it`` -- what the env's ``step`` hands its engine
+        call.  Returns (path, final, what ``_after`` needs)."""
         env = pe.env
         e = env.engine
-        final = None
-        path = "plain"
-        want_rows = env._observations
-        if pe.auto_reset:
-            if pe.native and pe._device_draws:
-                path = "ring" if env._ring is not None else "inline"
-                if pe.final_observation and (env._ring is not None or env._observations):
-                    final = pe._next_final_buf()
-                    e.set_final_obs(final)
+
+        def fill():
+            want_obs, out, dconst = env._step_targets()
+            reward, done, obs, _, _ = e._step_outputs(out, dconst is None, want_obs, False)
+            it.struct_size = C.sizeof(_lib.FleetItem)
+            it.handle = e._h.value
+            if isinstance(env, DiscreteBatchedMicrogridEnv):
+                a = action
+                if not (torch.is_tensor(a) and a.dtype == torch.int32 and a.is_contiguous() and a.device == e.device and a.shape == (e.N,)):
+                    a = _as_ids(a, e.device, e.N)
+                it.action_id = a.data_ptr()
+                it.table, it.n_actions = e._table_ptr(env._table)
             else:
-                path = "host"
-                if want_rows and not pe.final_observation and env._ring is None:   # the rows come from the observe pass behind the restarts
-                    env._observations = False
-        try:
-            want_obs, out = env._obs_target()
-        finally:
-            env._observations = want_rows
-        dconst = env._lockstep_done()
-        out = out or {}
-        reward = out.get("reward")
-        if reward is None:
-            reward = e._empty(e.N)
-        done = None
-        if dconst is None:
-            done = out.get("done")
-            if done is None:
-                done = e._empty(e.N, dtype=torch.uint8)
-        obs = e._obs_buf(out.get("obs")) if want_obs else None
-        it.struct_size = C.sizeof(_lib.FleetItem)
-        it.handle = e._h.value
-        if isinstance(env, DiscreteBatchedMicrogridEnv):
-            a = action
-            if not (torch.is_tensor(a) and a.dtype == torch.int32 and a.is_contiguous() and a.device == e.device):
-                a = torch.as_tensor(np.asarray(a.cpu() if torch.is_tensor(a) else a), device=e.device).to(torch.int32).contiguous()
-            if a.shape != (e.N,):
-                raise ValueError(f"action_id must be an int32 tensor of shape ({e.N},) on {e.device}")
-            it.action_id = a.data_ptr()
-            it.table, it.n_actions = e._table_ptr(env._table)
-        else:
-            a = env.control_to_tensor(action).to(e.action_dtype) if isinstance(action, dict) else action
-            a = e._check_actions(a, ())
-            it.actions = None if a is None else a.data_ptr()
-        it.reward = reward.data_ptr()
-        it.done = None if done is None else done.data_ptr()
-        it.obs = None if obs is None else obs.data_ptr()
-        it.log = None
-        return path, final, a, obs, reward, done, dconst, want_rows
+                a = env.control_to_tensor(action).to(e.action_dtype) if isinstance(action, dict) else action
+                a = e._check_actions(a, ())
+                it.actions = None if a is None else a.data_ptr()
+            it.reward = reward.data_ptr()
+            it.done = None if done is None else done.data_ptr()
+            it.obs = None if obs is None else obs.data_ptr()
+            it.log = None
+            return a, obs, reward, done, dconst         # (a: converted controls stay alive until the launch has been issued)
+        return pe._before_launch(fill)
 
     def _after(self, pe, plan):
-        """What ``PerGridWindowEnv.step`` / the env's ``step`` do after their launch: the host counter, the ring walk, the ring patches
-        of the restarted grids, a generator's restarts -- on the caller's stream, in bucket order."""
-        path, final, _, obs, reward, done, dconst, want_rows = plan
+        """The host mirror of the handle's counter (``mgx_fleet_step`` moved it) and the env's own walk behind a step, then the
+        bucket's ``_after_launch`` -- on the caller's stream, in bucket order."""
+        path, final, (_, obs, reward, done, dconst) = plan
         env = pe.env
-        e = env.engine
-        if e._t is not None:
-            e._t += 1                             # the host mirror of the handle's counter (mgx_fleet_step moved it)
-        obs = env._select_obs(env._obs_after(obs))
-        done = dconst if dconst is not None else done.view(torch.bool)
-        info = {}
-        if path == "ring":                        # the restarted grids' window columns in the rest of the ring
-            obs = env._rows_after_restart(done.view(torch.uint8), True)
-            if final is not None:
-                info["final_observation"] = env._select_obs(final)
-        elif path == "inline":
-            if final is not None:
-                info["final_observation"] = env._select_obs(final)
-        elif path == "host":
-            final = obs.clone() if (pe.final_observation and obs is not None) else None
-            if pe._device_draws:
-                if pe.lengths is None:
-                    pe.lengths = torch.full_like(pe.starts, pe.length if pe.length is not None else 0)
-                new_obs = env.reset_grids_random(done, pe.seed, pe.length or 0, lengths_out=pe.lengths)
-                pe.starts = e._window_start
-            else:
-                starts, lengths = pe.draw()
-                new_obs = env.reset_grids(done, starts, lengths, validate=False)
-                pe.starts = torch.where(done, starts, pe.starts)
-                if lengths is not None:
-                    pe.lengths = torch.where(done, lengths, pe.lengths)
-            if pe.final_observation:
-                info["final_observation"] = final
-            if new_obs is not None:
-                obs = new_obs
-        return obs, reward, done, info
+        if env.engine._t is not None:
+            env.engine._t += 1
+        return pe._after_launch(path, final, *env._step_end(obs, reward, done, None, dconst))
 
     def close(self):
         for pe in self.envs:

@@ -122,7 +122,7 @@ class RuleBasedControl:
         # a PerGridWindowEnv (per-grid random episodes with automatic restarts): run_episodes() deploys the lists across restarts
         self.episodes_env = None
         if isinstance(env, PerGridWindowEnv):
-            why = env._rollout_refusal()
+            why = env._fused_refusal("rollout")
             if why is not None:
                 raise ValueError(f"RuleBasedControl over per-grid episodes is not offered with {why}")
             self.episodes_env, env = env, env.env
