@@ -652,6 +652,53 @@ int mgx_step_k_policy_episodes(mgx_handle *h, const mgx_policy *policy, int32_t 
                                double *soc_trace, uint32_t *status_trace, double *actions_out, const mgx_episode_stats *stats,
                                const mgx_episode_rows *rows, mgx_stream stream);
 
+/* EXPLORATION inside the closed-loop launches: epsilon-greedy on the discrete head, additive noise on the continuous head, drawn
+ * on the device from a counter-based generator -- a draw is a function of (seed, grid, step counter, number) alone, so a host loop
+ * reproduces it bit for bit and it does not depend on how a roll-out is cut into launches.  THE RULE (stated here once):
+ *
+ * Draw of grid i at step counter t, number j:  t is the handle's shared counter BEFORE the step (mgx_current_step; step k of a
+ * launch: its value at the call + k), i the grid index the restart draws of mgx_set_auto_reset use.
+ *     r[0 .. 3] = Philox4x32-10(counter words (lo32(i), hi32(i), (uint32)t, 0xE9100000u + j); key (lo32(seed), hi32(seed)))
+ * (the fourth counter word of the series and episode draws is 0x5eed: an exploration seed equal to the auto-reset seed still has a
+ * stream of its own).  U(a, b) = (double)(((uint64)a << 21) ^ (b >> 11)) * 2^-53, in [0, 1): the 53-bit value of every other
+ * uniform draw here.
+ *
+ * Discrete head: ONE draw, j = 0.  u1 = U(r[0], r[1]), u2 = U(r[2], r[3]); e = scale ? epsilon * scale[i] : epsilon;
+ *     if u1 < e:  id = min((int)floor(u2 * (double)n_out), n_out - 1)     (n_out: policy->n_out, the table's rows)
+ *     else:       id = the greedy head of mgx_policy, unchanged
+ * Continuous head: one draw per action column o, j = o.  S = the integer sum of the twelve 10-bit fields at bits [0, 10), [10, 20),
+ * [20, 30) of each of the four words; z = ((double)S - 6138.0) * (1.0 / 1024.0) -- the classical twelve-uniform normal quantised
+ * at 2^-10: mean 0, standard deviation 0.9999995, support [-6138 / 1024, 6138 / 1024] (within +-6); s = scale ? sigma[o] * scale[i] : sigma[o];
+ *     v = y[o] + s * z    (a separate multiply and add);   u[o] = !(v > 0) ? 0.0 : (v > 1 ? 1.0 : v)
+ * With epsilon == 0, or every sigma == 0, the results are those of the calls without exploration, bit for bit. */
+typedef struct mgx_exploration {
+    int32_t struct_size;      /* = sizeof(mgx_exploration) */
+    int32_t reserved;
+    uint64_t seed;            /* Philox key */
+    double epsilon;           /* discrete head, in [0, 1] */
+    double sigma[4];          /* continuous head, one per action column, >= 0; entries beyond mgx_action_dim not read */
+    const double *scale;      /* device [N] or NULL (= 1.0 for every grid): multiplies epsilon and every sigma of grid i */
+} mgx_exploration;
+
+/* mgx_rollout_policy_episodes with the discrete head exploring by the rule of mgx_exploration: one launch of
+ * rollout_policy_explore_episodes_kernel.  action_id_out receives the ids taken, explored ones included.  explore == NULL: the call
+ * IS mgx_rollout_policy_episodes (forwarded).  Every other argument, result and refusal as there; on top MGX_ERR_INVALID for
+ * explore->struct_size != sizeof(mgx_exploration), an epsilon outside [0, 1] or NaN, a negative or NaN sigma[o] for
+ * o < mgx_action_dim (both calls check the whole struct, whichever head they run).
+ * An ADDITION to ABI 9 that leaves MGX_ABI_MINOR at 3: consumers find it by name (dlsym). */
+int mgx_rollout_policy_explore_episodes(mgx_handle *h, const mgx_policy *policy, const mgx_exploration *explore, const int32_t *table,
+                                        int32_t n_actions, int32_t K, double *reward, uint8_t *done, double *soc_trace,
+                                        uint32_t *status_trace, uint8_t *action_id_out, const mgx_episode_stats *stats,
+                                        const mgx_episode_rows *rows, mgx_stream stream);
+
+/* The continuous twin (step_k_policy_explore_episodes_kernel): mgx_step_k_policy_episodes with the noise of mgx_exploration on
+ * every control before its clip.  actions_out receives the controls taken.  explore == NULL: the call IS
+ * mgx_step_k_policy_episodes.  On top of its refusals MGX_ERR_INVALID as mgx_rollout_policy_explore_episodes refuses a mgx_exploration.
+ * An ADDITION to ABI 9 that leaves MGX_ABI_MINOR at 3: consumers find it by name (dlsym). */
+int mgx_step_k_policy_explore_episodes(mgx_handle *h, const mgx_policy *policy, const mgx_exploration *explore, int32_t K,
+                                       double *reward, uint8_t *done, double *soc_trace, uint32_t *status_trace, double *actions_out,
+                                       const mgx_episode_stats *stats, const mgx_episode_rows *rows, mgx_stream stream);
+
 /* raise_errors=True (BaseMicrogridModule.__init__, base_module.py:40; as_source / as_sink, :213-224,265-270; _raise_error,
  * :79-93): the reference refuses a request a module cannot meet with a ValueError instead of clipping it.  mgx_step always
  * clips; mgx_check_step is its DRY RUN -- the same arithmetic on a register copy of the state, nothing stored, the counter

@@ -2139,23 +2139,85 @@ static int policy_dims_refusal(mgx_handle *h, const mgx_policy *policy, int32_t 
     return MGX_OK;
 }
 
-int mgx_rollout_policy_episodes(mgx_handle *h, const mgx_policy *policy, const int32_t *table, int32_t n_actions, int32_t K,
-                                double *reward, uint8_t *done, double *soc_trace, uint32_t *status_trace, uint8_t *action_id_out,
-                                const mgx_episode_stats *stats, const mgx_episode_rows *rows, mgx_stream stream)
+// ... and what they check of a mgx_exploration (NULL: none -- the greedy call); `ex` is what the exploring kernels take by value
+static int exploration_refusal(mgx_handle *h, const mgx_exploration *explore, const char *fn, ExploreArgs &ex)
 {
-    g_err[0] = 0;
-    const char *fn = "mgx_rollout_policy_episodes";
+    if (!explore) return MGX_OK;
+    if (explore->struct_size != (int32_t)sizeof(mgx_exploration))
+        return fail(MGX_ERR_INVALID, "%s: explore->struct_size is %d, sizeof(mgx_exploration) is %d", fn, explore->struct_size,
+                    (int)sizeof(mgx_exploration));
+    if (!(explore->epsilon >= 0.0 && explore->epsilon <= 1.0))
+        return fail(MGX_ERR_INVALID, "%s: explore->epsilon is %g, outside [0, 1]", fn, explore->epsilon);
+    ex = ExploreArgs{explore->seed, explore->epsilon, {0.0, 0.0, 0.0, 0.0}, explore->scale};
+    for (int32_t o = 0; o < h->action_dim && o < 4; o++) {
+        if (!(explore->sigma[o] >= 0.0)) return fail(MGX_ERR_INVALID, "%s: explore->sigma[%d] is %g, negative or NaN", fn, o, explore->sigma[o]);
+        ex.sigma[o] = explore->sigma[o];
+    }
+    return MGX_OK;
+}
+
+// The closed-loop roll-out, greedy (explore == NULL: rollout_policy_episodes_kernel) or exploring
+// (rollout_policy_explore_episodes_kernel): every check, then one launch.
+static int rollout_policy_episodes_impl(mgx_handle *h, const mgx_policy *policy, const mgx_exploration *explore, const int32_t *table,
+                                        int32_t n_actions, int32_t K, double *reward, uint8_t *done, double *soc_trace,
+                                        uint32_t *status_trace, uint8_t *action_id_out, const mgx_episode_stats *stats,
+                                        const mgx_episode_rows *rows, mgx_stream stream, const char *fn)
+{
     if (!h || !policy || !table) return fail(MGX_ERR_INVALID, "%s: NULL argument", fn);
     if (int rc = policy_struct_refusal(policy, fn)) return rc;
     const mgx_episode_rows none{(int32_t)sizeof(mgx_episode_rows), 0, nullptr, nullptr};
     PLWords tab;
     EpisodePolicyLaunch P{};
+    if (int rc = exploration_refusal(h, explore, fn, P.ex)) return rc;
     if (int rc = prepare_episode_launch(h, K, reward, done, soc_trace, status_trace, stats, rows ? rows : &none, stream, fn,
                                         "mgx_rollout_discrete", "mgx_step_lists", table, n_actions, &tab, P.r)) return rc;
     if (int rc = policy_dims_refusal(h, policy, tab.n_actions, 4, "n_actions", fn, P)) return rc;
     P.r.e.tab = &tab; P.actions_out = action_id_out;
-    const bool launched = launch_rollout_policy_episodes_p0(P) || launch_rollout_policy_episodes_p1(P);
-    return finish_episode_launch(h, P.r.e, launched, "rollout_policy_episodes_kernel launch", fn);
+    const bool launched = explore ? launch_rollout_policy_explore_episodes_p0(P) || launch_rollout_policy_explore_episodes_p1(P)
+                                  : launch_rollout_policy_episodes_p0(P) || launch_rollout_policy_episodes_p1(P);
+    return finish_episode_launch(h, P.r.e, launched, explore ? "rollout_policy_explore_episodes_kernel launch" : "rollout_policy_episodes_kernel launch", fn);
+}
+
+int mgx_rollout_policy_episodes(mgx_handle *h, const mgx_policy *policy, const int32_t *table, int32_t n_actions, int32_t K,
+                                double *reward, uint8_t *done, double *soc_trace, uint32_t *status_trace, uint8_t *action_id_out,
+                                const mgx_episode_stats *stats, const mgx_episode_rows *rows, mgx_stream stream)
+{
+    g_err[0] = 0;
+    return rollout_policy_episodes_impl(h, policy, nullptr, table, n_actions, K, reward, done, soc_trace, status_trace, action_id_out, stats,
+                                        rows, stream, "mgx_rollout_policy_episodes");
+}
+
+// an exploring call without a mgx_exploration is the greedy call
+int mgx_rollout_policy_explore_episodes(mgx_handle *h, const mgx_policy *policy, const mgx_exploration *explore, const int32_t *table,
+                                        int32_t n_actions, int32_t K, double *reward, uint8_t *done, double *soc_trace,
+                                        uint32_t *status_trace, uint8_t *action_id_out, const mgx_episode_stats *stats,
+                                        const mgx_episode_rows *rows, mgx_stream stream)
+{
+    g_err[0] = 0;
+    return rollout_policy_episodes_impl(h, policy, explore, table, n_actions, K, reward, done, soc_trace, status_trace, action_id_out, stats,
+                                        rows, stream, explore ? "mgx_rollout_policy_explore_episodes" : "mgx_rollout_policy_episodes");
+}
+
+// The closed-loop continuous K-step, greedy (explore == NULL: step_k_policy_episodes_kernel) or exploring
+// (step_k_policy_explore_episodes_kernel): every check, then one launch.
+static int step_k_policy_episodes_impl(mgx_handle *h, const mgx_policy *policy, const mgx_exploration *explore, int32_t K, double *reward,
+                                       uint8_t *done, double *soc_trace, uint32_t *status_trace, double *actions_out,
+                                       const mgx_episode_stats *stats, const mgx_episode_rows *rows, mgx_stream stream, const char *fn)
+{
+    if (!h || !policy) return fail(MGX_ERR_INVALID, "%s: NULL argument", fn);
+    if (int rc = policy_struct_refusal(policy, fn)) return rc;
+    const mgx_episode_rows none{(int32_t)sizeof(mgx_episode_rows), 0, nullptr, nullptr};
+    EpisodePolicyLaunch P{};
+    if (int rc = exploration_refusal(h, explore, fn, P.ex)) return rc;
+    if (int rc = prepare_episode_launch(h, K, reward, done, soc_trace, status_trace, stats, rows ? rows : &none, stream, fn, "mgx_step_k",
+                                        "mgx_step", nullptr, 0, nullptr, P.r)) return rc;
+    if (h->k.act_f32)
+        return fail(MGX_ERR_UNSUPPORTED, "%s: the handle's action format is float32 (mgx_set_action_format); the policy's controls are doubles", fn);
+    if (int rc = policy_dims_refusal(h, policy, h->action_dim, 1, "mgx_action_dim", fn, P)) return rc;
+    P.actions_out = actions_out;
+    const bool launched = explore ? launch_step_k_policy_explore_episodes_p0(P) || launch_step_k_policy_explore_episodes_p1(P)
+                                  : launch_step_k_policy_episodes_p0(P) || launch_step_k_policy_episodes_p1(P);
+    return finish_episode_launch(h, P.r.e, launched, explore ? "step_k_policy_explore_episodes_kernel launch" : "step_k_policy_episodes_kernel launch", fn);
 }
 
 int mgx_step_k_policy_episodes(mgx_handle *h, const mgx_policy *policy, int32_t K, double *reward, uint8_t *done,
@@ -2163,19 +2225,17 @@ int mgx_step_k_policy_episodes(mgx_handle *h, const mgx_policy *policy, int32_t 
                                const mgx_episode_rows *rows, mgx_stream stream)
 {
     g_err[0] = 0;
-    const char *fn = "mgx_step_k_policy_episodes";
-    if (!h || !policy) return fail(MGX_ERR_INVALID, "%s: NULL argument", fn);
-    if (int rc = policy_struct_refusal(policy, fn)) return rc;
-    const mgx_episode_rows none{(int32_t)sizeof(mgx_episode_rows), 0, nullptr, nullptr};
-    EpisodePolicyLaunch P{};
-    if (int rc = prepare_episode_launch(h, K, reward, done, soc_trace, status_trace, stats, rows ? rows : &none, stream, fn, "mgx_step_k",
-                                        "mgx_step", nullptr, 0, nullptr, P.r)) return rc;
-    if (h->k.act_f32)
-        return fail(MGX_ERR_UNSUPPORTED, "%s: the handle's action format is float32 (mgx_set_action_format); the policy's controls are doubles", fn);
-    if (int rc = policy_dims_refusal(h, policy, h->action_dim, 1, "mgx_action_dim", fn, P)) return rc;
-    P.actions_out = actions_out;
-    const bool launched = launch_step_k_policy_episodes_p0(P) || launch_step_k_policy_episodes_p1(P);
-    return finish_episode_launch(h, P.r.e, launched, "step_k_policy_episodes_kernel launch", fn);
+    return step_k_policy_episodes_impl(h, policy, nullptr, K, reward, done, soc_trace, status_trace, actions_out, stats, rows, stream,
+                                       "mgx_step_k_policy_episodes");
+}
+
+int mgx_step_k_policy_explore_episodes(mgx_handle *h, const mgx_policy *policy, const mgx_exploration *explore, int32_t K,
+                                       double *reward, uint8_t *done, double *soc_trace, uint32_t *status_trace, double *actions_out,
+                                       const mgx_episode_stats *stats, const mgx_episode_rows *rows, mgx_stream stream)
+{
+    g_err[0] = 0;
+    return step_k_policy_episodes_impl(h, policy, explore, K, reward, done, soc_trace, status_trace, actions_out, stats, rows, stream,
+                                       explore ? "mgx_step_k_policy_explore_episodes" : "mgx_step_k_policy_episodes");
 }
 
 int mgx_rollout_lists(mgx_handle *h, const int32_t *action_id, int per_step, const int32_t *lists, int32_t n_lists, int32_t list_len,

@@ -932,11 +932,15 @@ __device__ __forceinline__ double forecast_normal(uint64_t seed, int64_t grid, u
 
 // U[0, 1) of (seed; grid, row): Philox4x32-10 as a counter-based generator (the generator's series and the episode draws of
 // mgx_reset_grids_random use it; pymgrid_amd.generator.synth_uniform_host reproduces it bit for bit)
+__device__ __forceinline__ double uniform53(uint32_t a, uint32_t b)
+{
+    return (double)(((uint64_t)a << 21) ^ (b >> 11)) * (1.0 / 9007199254740992.0);            // 53 bits, [0, 1)
+}
 __device__ __forceinline__ double synth_uniform(uint64_t seed, int64_t grid, int32_t row)
 {
     uint32_t r[4];
     philox4x32_10((uint32_t)grid, (uint32_t)((uint64_t)grid >> 32), (uint32_t)row, 0x5eedu, (uint32_t)seed, (uint32_t)(seed >> 32), r);
-    return (double)(((uint64_t)r[0] << 21) ^ (r[1] >> 11)) * (1.0 / 9007199254740992.0);      // 53 bits, [0, 1)
+    return uniform53(r[0], r[1]);
 }
 
 // One grid's trajectory draw at counter value `counter`, as its own trajectory_func would make it

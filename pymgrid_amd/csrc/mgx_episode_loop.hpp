@@ -11,6 +11,9 @@
 // the form and the figure: the factors, fill, rotation, restart and advance in rollout_episodes_rows_kernel,
 // rollout_policy_episodes_kernel and step_k_policy_episodes_kernel, the advance in step_k_episodes_rows_kernel.  A change to
 // load_lane_factors, fill_row_ring, rotate_ring, restart_lane or advance_row_ring is made there too.
+// The two exploring twins of the policy kernels (rollout_policy_explore_episodes_kernel: mgx_policy_explore_episodes.hip,
+// step_k_policy_explore_episodes_kernel: mgx_step_policy_explore_episodes.hip) are a seventh and eighth loop on the same pieces,
+// compiled the same way; they CALL all five ring helpers (their register figures on them: DESIGN.md's kernel table).
 #pragma once
 #include "mgx_kernels.hpp"
 

@@ -2,7 +2,9 @@
 // mgx_step_k_policy_episodes: mgx_step_policy_episodes.hip): the policy of include/mgx.h (a small fp64 network of plain IEEE
 // operations) staged in LDS once per workgroup and evaluated per lane between "row of the coming step" and "step", and the
 // lane's row strip -- the H = 0 row is built ONCE per step into the wave's tile, read back as the policy's input and, where
-// the launch returns observations, streamed out of the same tile as the row the step before returned.
+// the launch returns observations, streamed out of the same tile as the row the step before returned.  Their exploring twins
+// (mgx_rollout_policy_explore_episodes: mgx_policy_explore_episodes.hip, mgx_step_k_policy_explore_episodes:
+// mgx_step_policy_explore_episodes.hip) add the draw, the epsilon choice and the noise of mgx_exploration, each stated once below.
 // On top of mgx_episode_rows.hpp (the rows) and, through it, mgx_episode_loop.hpp (what all six episode loops share).
 #pragma once
 #include "mgx_episode_rows.hpp"
@@ -134,6 +136,53 @@ __device__ __forceinline__ int32_t policy_argmax(const double (&y)[NO], int32_t 
 // the continuous head: a normalised control
 __device__ __forceinline__ double policy_clip(double y) { return !(y > 0.0) ? 0.0 : (y > 1.0 ? 1.0 : y); }
 
+// ---- exploration: the rule of mgx_exploration (include/mgx.h), for the two exploring kernels (mgx_policy_explore_episodes.hip,
+// mgx_step_policy_explore_episodes.hip).  Every piece is a function of (seed, grid, step counter, number) and of values the step
+// has at hand: a draw is formed where it is used and holds no register across the step. ----
+// mgx_exploration as the kernels see it, by value in their argument struct
+struct ExploreArgs {
+    uint64_t seed;
+    double epsilon, sigma[4];
+    const double *scale;             // [N] or NULL
+};
+
+// scale[i], 1.0 where there is none: x * 1.0 is x bit for bit, so the loops carry one product and no branch on the pointer
+__device__ __forceinline__ double explore_lane_scale(const double *__restrict__ scale, int64_t i) { return scale ? scale[i] : 1.0; }
+
+// the draw: r[0 .. 3] of grid i at step counter t, number j
+__device__ __forceinline__ void explore_draw(uint64_t seed, int64_t i, int32_t t, uint32_t j, uint32_t (&r)[4])
+{
+    philox4x32_10((uint32_t)i, (uint32_t)((uint64_t)i >> 32), (uint32_t)t, 0xE9100000u + j, (uint32_t)seed, (uint32_t)(seed >> 32), r);
+}
+
+// the discrete head: `greedy` (policy_argmax) or, with probability e, one of the `no` REAL ids (not the staged multiple of four)
+__device__ __forceinline__ int32_t policy_epsilon_greedy(int32_t greedy, int32_t no, double e, uint64_t seed, int64_t i, int32_t t)
+{
+    uint32_t r[4];
+    explore_draw(seed, i, t, 0u, r);
+    const double u1 = uniform53(r[0], r[1]), u2 = uniform53(r[2], r[3]);
+    const int32_t k = (int32_t)floor(u2 * (double)no);
+    return u1 < e ? (k < no - 1 ? k : no - 1) : greedy;
+}
+
+// the continuous head's noise for action column j: the twelve 10-bit fields of the draw summed, centred, in units of 2^-10
+__device__ __forceinline__ double explore_normal(uint64_t seed, int64_t i, int32_t t, uint32_t j)
+{
+    uint32_t r[4];
+    explore_draw(seed, i, t, j, r);
+    uint32_t S = 0u;
+#pragma unroll
+    for (int w = 0; w < 4; w++) S += (r[w] & 1023u) + ((r[w] >> 10) & 1023u) + ((r[w] >> 20) & 1023u);
+    return ((double)S - 6138.0) * (1.0 / 1024.0);
+}
+
+// ... and the control it gives: the clip of y + s * z (a multiply, then an add: the build has -ffp-contract=off)
+__device__ __forceinline__ double policy_noisy_clip(double y, double s, uint64_t seed, int64_t i, int32_t t, uint32_t j)
+{
+    const double z = explore_normal(seed, i, t, j);
+    return policy_clip(y + s * z);
+}
+
 // columns of an H = 0 row of layout F
 template <int F>
 constexpr int policy_row_dim() { return 2 + 4 * ((F & F_GENSET) != 0) + 2 * ((F & F_BATTERY) != 0) + 4 * ((F & F_GRID) != 0); }
@@ -210,14 +259,27 @@ struct StepPolicyArgs {
     double *actions_out;             // [K, N, A] or NULL
 };
 
-// ---- host side: what mgx_abi.hip hands the slices of the two translation units ----
+// ... and of the two exploring kernels: the greedy kernel's struct first (its fields keep their offsets), the exploration behind it
+struct RolloutPolicyExploreArgs {
+    RolloutPolicyArgs g;
+    ExploreArgs ex;
+};
+struct StepPolicyExploreArgs {
+    StepPolicyArgs g;
+    ExploreArgs ex;
+};
+
+// ---- host side: what mgx_abi.hip hands the slices of the four translation units ----
 struct EpisodePolicyLaunch {
     EpisodeRowsLaunch r;             // as for the kernels with rows (obs / final_obs may both be NULL here)
     PolicyArgs pol;
     unsigned lds_bytes;              // n_policies * stride doubles: the dynamic LDS of the launch
     void *actions_out;               // the ids (uint8 [K, N]) or controls (double [K, N, A]) the policy chose, or NULL
+    ExploreArgs ex;                  // the exploring kernels alone read it
 };
 bool launch_rollout_policy_episodes_p0(const EpisodePolicyLaunch &L); bool launch_rollout_policy_episodes_p1(const EpisodePolicyLaunch &L);
 bool launch_step_k_policy_episodes_p0(const EpisodePolicyLaunch &L); bool launch_step_k_policy_episodes_p1(const EpisodePolicyLaunch &L);
+bool launch_rollout_policy_explore_episodes_p0(const EpisodePolicyLaunch &L); bool launch_rollout_policy_explore_episodes_p1(const EpisodePolicyLaunch &L);
+bool launch_step_k_policy_explore_episodes_p0(const EpisodePolicyLaunch &L); bool launch_step_k_policy_explore_episodes_p1(const EpisodePolicyLaunch &L);
 
 }  // namespace mgx

@@ -775,12 +775,17 @@ class StepEngine:
         return self._launch_episodes("mgx_step_k_episodes", (_ptr(actions), K, 1 if normalized else 0), K, res, (r, d, s, g), st, out,
                                      obs, final_obs)
 
-    def _launch_policy_episodes(self, symbol, policy, lead, K, res, bufs, taken, st, out, obs, final_obs):
-        """The tail of the closed-loop episode launches: ``symbol`` with the policy's ``mgx_policy``, the call's own arguments ``lead``,
-        the four outputs, the buffer of the actions taken, the statistics and the rows (NULL: none asked for); K steps on."""
+    def _launch_policy_episodes(self, symbol, policy, exploration, lead, K, res, bufs, taken, st, out, obs, final_obs):
+        """The tail of the closed-loop episode launches: ``symbol`` -- with an ``exploration`` its exploring form, which takes the
+        ``mgx_exploration`` behind the policy -- with the policy's ``mgx_policy``, the call's own arguments ``lead``, the four outputs,
+        the buffer of the actions taken, the statistics and the rows (NULL: none asked for); K steps on."""
         pst, keep = policy.c_struct(self.device, self.N)
+        head = (C.byref(pst),)
+        if exploration is not None:
+            xst, keep_x = exploration.c_struct(self.device, self.N)
+            symbol, head = symbol.replace("_policy_", "_policy_explore_"), (C.byref(pst), C.byref(xst))
         rows = self._episode_rows(res, out, K, obs, final_obs)
-        self._call(getattr(self._lib, symbol), C.byref(pst), *lead, *map(_ptr, bufs), _ptr(taken), C.byref(st),
+        self._call(getattr(self._lib, symbol), *head, *lead, *map(_ptr, bufs), _ptr(taken), C.byref(st),
                    None if rows is None else C.byref(rows))
         del keep
         if self._t is not None:
@@ -800,32 +805,36 @@ class StepEngine:
         return t
 
     def rollout_policy_episodes(self, policy, table, K, reward=True, done=False, soc_trace=False, status_trace=False, actions=False,
-                                stats=None, out=None, obs=False, final_obs=False):
+                                stats=None, out=None, obs=False, final_obs=False, exploration=None):
         """``rollout_episodes`` with the loop closed inside the launch (``mgx_rollout_policy_episodes``): the priority-list id of
         every step is ``policy`` (an ``MLPPolicy`` with ``head="discrete"``, ``n_out`` = rows of ``table``) applied to the observation
         row the grid stands on -- what K times ``ids = policy.act(obs); obs, ... = step_discrete(ids, table)`` leaves, bit for bit.
-        ``actions=True``: also the ids taken (uint8 [K, N]).  No forecast horizon, whole rows; everything else as ``rollout_episodes``."""
+        ``actions=True``: also the ids taken (uint8 [K, N]).  No forecast horizon, whole rows; everything else as ``rollout_episodes``.
+        ``exploration`` (``pymgrid_amd.policy.Exploration``): the head explores inside the launch (``mgx_rollout_policy_explore_episodes``)
+        -- what ``ids = policy.act(obs, exploration, counter)`` with the counter before each step leaves, bit for bit."""
         out = out or {}
         K = int(K)
         st = self._episode_stats(stats)
         tptr, n_lists = self._table_ptr(table)
         res, r, d, s, g, _ = self._fused_outputs(out, K, reward, done, soc_trace, status_trace)
         taken = self._actions_out(res, out, actions, (K, self.N), torch.uint8)
-        return self._launch_policy_episodes("mgx_rollout_policy_episodes", policy, (tptr, n_lists, K), K, res, (r, d, s, g),
+        return self._launch_policy_episodes("mgx_rollout_policy_episodes", policy, exploration, (tptr, n_lists, K), K, res, (r, d, s, g),
                                             taken, st, out, obs, final_obs)
 
     def step_k_policy_episodes(self, policy, K, reward=True, done=False, soc_trace=False, status_trace=False, actions=False,
-                               stats=None, out=None, obs=False, final_obs=False):
+                               stats=None, out=None, obs=False, final_obs=False, exploration=None):
         """``step_k_episodes`` with the loop closed inside the launch (``mgx_step_k_policy_episodes``): the controls of every step are
         ``policy`` (an ``MLPPolicy`` with ``head="continuous"``, ``n_out`` = ``action_dim``) applied to the observation row the grid
         stands on, stepped normalised -- what K times ``u = policy.act(obs); obs, ... = step(u, normalized=True)`` leaves, bit for
-        bit.  ``actions=True``: also the controls taken (float64 [K, N, A]).  float64 controls only (``action_dtype``)."""
+        bit.  ``actions=True``: also the controls taken (float64 [K, N, A]).  float64 controls only (``action_dtype``).
+        ``exploration``: noise on the controls inside the launch (``mgx_step_k_policy_explore_episodes``), as for
+        ``rollout_policy_episodes``."""
         out = out or {}
         K = int(K)
         st = self._episode_stats(stats)
         res, r, d, s, g, _ = self._fused_outputs(out, K, reward, done, soc_trace, status_trace)
         taken = self._actions_out(res, out, actions, (K, self.N, self.action_dim), torch.float64)
-        return self._launch_policy_episodes("mgx_step_k_policy_episodes", policy, (K,), K, res, (r, d, s, g), taken, st,
+        return self._launch_policy_episodes("mgx_step_k_policy_episodes", policy, exploration, (K,), K, res, (r, d, s, g), taken, st,
                                             out, obs, final_obs)
 
     def rollout_lists(self, action_id, lists, K, reward=True, done=False, soc_trace=False, status_trace=False, ret_acc=None,

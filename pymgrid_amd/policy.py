@@ -29,6 +29,94 @@ def _f64(name, a, ndim):
     return t.contiguous()
 
 
+EXPLORE_TAG = 0xE9100000    # fourth Philox counter word of exploration draw number 0 (include/mgx.h, mgx_exploration)
+SYNTH_TAG = 0x5EED          # ... of the series and episode draws (pymgrid_amd.generator.synth_uniform_host)
+_M32 = 0xFFFFFFFF
+
+
+def philox_words(seed, grid, counter, tag, device=None):
+    """``r[0 .. 3]`` (int64 tensor ``[4, ...]``, each word in ``[0, 2**32)``) of Philox4x32-10 with the counter words
+    ``(lo32(grid), hi32(grid), uint32(counter), tag)`` and the key ``(lo32(seed), hi32(seed))``, in torch integer arithmetic on
+    ``device``: the device's ``philox4x32_10`` bit for bit.  ``tag = SYNTH_TAG`` gives the words of ``synth_uniform_host``."""
+    grid = torch.as_tensor(grid, device=device).to(torch.int64)
+    counter = torch.as_tensor(counter, device=grid.device).to(torch.int64)
+    grid, counter = torch.broadcast_tensors(grid, counter)
+    c0, c1 = grid & _M32, (grid >> 32) & _M32
+    c2, c3 = counter & _M32, torch.full_like(grid, int(tag) & _M32)
+    k0, k1 = int(seed) & _M32, (int(seed) >> 32) & _M32
+
+    def mul(m, c):               # (hi, lo) words of the 64-bit product m * c, m and c below 2**32: by halves, nothing leaves int64
+        lo, hi = m * (c & 0xFFFF), m * (c >> 16)
+        full_lo = lo + ((hi & 0xFFFF) << 16)
+        return ((hi >> 16) + (full_lo >> 32)) & _M32, full_lo & _M32
+    for _ in range(10):
+        (h0, l0), (h1, l1) = mul(0xD2511F53, c0), mul(0xCD9E8D57, c2)
+        c0, c1, c2, c3 = h1 ^ c1 ^ k0, l1, h0 ^ c3 ^ k1, l0
+        k0, k1 = (k0 + 0x9E3779B9) & _M32, (k1 + 0xBB67AE85) & _M32
+    return torch.stack([c0, c1, c2, c3])
+
+
+def uniform53(a, b):
+    """U[0, 1) out of two Philox words: ``((a << 21) ^ (b >> 11)) * 2**-53``, the 53-bit value of the device's draws."""
+    return ((a << 21) ^ (b >> 11)).to(torch.float64) * (1.0 / 9007199254740992.0)
+
+
+def explore_normal(seed, grid, counter, column, device=None):
+    """``z`` of the continuous head (include/mgx.h, mgx_exploration): the twelve 10-bit fields of draw number ``column`` summed,
+    ``(S - 6138) / 1024`` -- mean 0, standard deviation 0.9999995, a multiple of 2**-10 within +-6."""
+    r = philox_words(seed, grid, counter, EXPLORE_TAG + int(column), device)
+    S = ((r & 1023) + ((r >> 10) & 1023) + ((r >> 20) & 1023)).sum(dim=0)
+    return (S.to(torch.float64) - 6138.0) * (1.0 / 1024.0)
+
+
+class Exploration:
+    """What the exploring closed-loop launches add to an ``MLPPolicy`` (``mgx_exploration``, include/mgx.h): epsilon-greedy on the
+    discrete head, additive noise ``sigma[o] * z`` on control ``o`` of the continuous head before its clip, both drawn from a
+    counter-based generator keyed by ``seed`` -- a draw depends on (seed, grid, step counter, number) alone.  ``sigma``: one value
+    for every action column or up to four, one per column; ``scale`` (float64 ``[N]``, numpy or torch): multiplies ``epsilon`` and
+    every ``sigma`` of grid i (an exploration ladder; 0 switches a grid back to the greedy head).  Validated as the C calls do."""
+
+    def __init__(self, seed, epsilon=0.0, sigma=None, scale=None):
+        self.seed = int(seed)
+        if not 0 <= self.seed < 2 ** 64:
+            raise ValueError(f"seed = {seed}: a 64-bit unsigned key")
+        self.epsilon = float(epsilon)
+        if not 0.0 <= self.epsilon <= 1.0:
+            raise ValueError(f"epsilon = {epsilon}: a probability in [0, 1]")
+        sg = [0.0] if sigma is None else [float(v) for v in np.atleast_1d(np.asarray(sigma, dtype=np.float64))]
+        if len(sg) > MAX_CONTROLS:
+            raise ValueError(f"sigma holds {len(sg)} values: a layout has at most {MAX_CONTROLS} action columns")
+        self._shared_sigma = sigma is None or np.ndim(sigma) == 0
+        if not all(v >= 0.0 for v in sg):
+            raise ValueError(f"sigma = {sigma}: standard deviations are >= 0")
+        self.sigma = tuple(sg * MAX_CONTROLS if self._shared_sigma else sg + [0.0] * (MAX_CONTROLS - len(sg)))
+        self.scale = None
+        if scale is not None:
+            t = scale if torch.is_tensor(scale) else torch.as_tensor(np.asarray(scale))
+            if t.dtype != torch.float64 or t.dim() != 1:
+                raise ValueError(f"scale must be a float64 vector [N], not {t.dtype} {tuple(t.shape)}")
+            self.scale = t.contiguous()
+
+    def scale_on(self, device, n):
+        """``scale`` on ``device`` (None: there is none), checked against the ``n`` grids it names."""
+        if self.scale is None:
+            return None
+        if self.scale.shape[0] != n:
+            raise ValueError(f"scale names {self.scale.shape[0]} grids, not {n}")
+        return self.scale.to(device)
+
+    def c_struct(self, device, n_grids):
+        """``(mgx_exploration, keep-alive)`` with ``scale`` on ``device``."""
+        st = _lib.Exploration()
+        st.struct_size = C.sizeof(_lib.Exploration)
+        st.seed, st.epsilon = self.seed, self.epsilon
+        for o, v in enumerate(self.sigma):
+            st.sigma[o] = v
+        sc = self.scale_on(device, n_grids)
+        st.scale = None if sc is None else sc.data_ptr()
+        return st, sc
+
+
 class MLPPolicy:
     """``y = W2 . relu(W1 . x + b1) + b2`` (``W1 = b1 = None``: the linear policy ``y = W2 . x + b2``) on the observation row ``x``,
     every sum taken in index order with a separate multiply and add; ``relu(h) = h if h > 0 else +0.0``.
@@ -142,18 +230,38 @@ class MLPPolicy:
             x = torch.where(h > 0, h, torch.zeros_like(h))
         return self._layer(me.W2, me.b2, idx, x)
 
-    def act(self, obs):
+    def act(self, obs, exploration=None, counter=None):
         """The actions for observation rows ``obs`` [N, n_in]: priority-list ids (int32 [N]) or normalised controls (float64
-        [N, n_out]) -- what the fused launches take, bit for bit."""
+        [N, n_out]) -- what the fused launches take, bit for bit.  ``exploration`` (an ``Exploration``) with ``counter``, the int the
+        handle's shared step counter holds BEFORE the step (``env.current_step``): the host statement of the rule of
+        ``mgx_exploration`` (include/mgx.h) -- row n of ``obs`` is grid n -- and what the exploring launches take, bit for bit."""
         y = self.outputs(obs)
+        n, dev = y.shape[0], y.device
+        if exploration is not None:
+            if counter is None:
+                raise ValueError("exploration needs `counter`, the handle's step counter before the step (env.current_step)")
+            grid = torch.arange(n, dtype=torch.int64, device=dev)
+            scale = exploration.scale_on(dev, n)
         if self.head == "continuous":
+            if exploration is not None and self.n_out:
+                cols = []
+                for o in range(self.n_out):
+                    s = exploration.sigma[o] if scale is None else exploration.sigma[o] * scale
+                    cols.append(y[:, o] + s * explore_normal(exploration.seed, grid, int(counter), o))
+                y = torch.stack(cols, dim=1)
             return torch.where(~(y > 0), torch.zeros_like(y), torch.where(y > 1, torch.ones_like(y), y))
-        best = torch.full((y.shape[0],), float("-inf"), dtype=torch.float64, device=y.device)
-        ids = torch.zeros(y.shape[0], dtype=torch.int32, device=y.device)
+        best = torch.full((n,), float("-inf"), dtype=torch.float64, device=dev)
+        ids = torch.zeros(n, dtype=torch.int32, device=dev)
         for o in range(self.n_out):
             m = y[:, o] > best
             best = torch.where(m, y[:, o], best)
             ids = torch.where(m, torch.full_like(ids, o), ids)
+        if exploration is not None:
+            r = philox_words(exploration.seed, grid, int(counter), EXPLORE_TAG)
+            u1, u2 = uniform53(r[0], r[1]), uniform53(r[2], r[3])
+            e = exploration.epsilon if scale is None else exploration.epsilon * scale
+            k = torch.clamp((u2 * float(self.n_out)).floor().to(torch.int32), max=self.n_out - 1)
+            ids = torch.where(u1 < e, k, ids)
         return ids
 
     def c_struct(self, device, n_grids):
