@@ -699,6 +699,54 @@ int mgx_step_k_policy_explore_episodes(mgx_handle *h, const mgx_policy *policy, 
                                        double *reward, uint8_t *done, double *soc_trace, uint32_t *status_trace, double *actions_out,
                                        const mgx_episode_stats *stats, const mgx_episode_rows *rows, mgx_stream stream);
 
+/* SAMPLING inside the closed-loop discrete launch: the id of every step is drawn from the policy's own categorical distribution,
+ * softmax(y / tau), and the launch returns the probability of the id taken -- what the on-policy methods (REINFORCE, A2C, PPO)
+ * need; the caller takes the logarithm.  exp is PART OF THE RULE, a fixed sequence of plain IEEE fp64 operations, not a call into
+ * a math library: host and device evaluate the same operations, so fused == stepped stays bit for bit.  THE RULE (stated here once):
+ *
+ * E(d), for -708 <= d <= 0   (every multiply and add separate):
+ *     k = floor(d * 1.4426950408889634 + 0.5)
+ *     r = (d - k * 6.93147180369123816490e-01) - k * 1.90821492927058770002e-10
+ *     p = c[13];  for n = 12 .. 0:  p = p * r + c[n]        c[n]: the double nearest 1/n! --
+ *         c[0 .. 13] = 1.0, 1.0, 0.5, 0.16666666666666666, 0.041666666666666664, 0.008333333333333333, 0.001388888888888889,
+ *                      0.0001984126984126984, 2.48015873015873e-05, 2.7557319223985893e-06, 2.755731922398589e-07,
+ *                      2.505210838544172e-08, 2.08767569878681e-09, 1.6059043836821613e-10
+ *     E = p * 2^k       (2^k built from its bits, (uint64)(k + 1023) << 52: a normal number, since k >= -1021)
+ * E stays below 1 ulp of exp(d), is monotone, never exceeds 1.0 and E(+-0.0) == 1.0.
+ *
+ * Sampling head of grid i at step counter t (i, t, the draw and U(a, b) as mgx_exploration states them), on y[0 .. n_out) of mgx_policy:
+ *     best, g = the greedy head of mgx_policy, unchanged (strict >, from -inf, the lowest index wins, a NaN never wins)
+ *     tau  = scale ? temperature * scale[i] : temperature
+ *     if !(tau > 0):  id = g, prob = 1.0, and no draw is made      (temperature 0 or scale[i] == 0: the greedy launch, bit for bit)
+ *     beta = 1.0 / tau
+ *     for o = 0 .. n_out - 1:  d = (y[o] - best) * beta;  e[o] = (o == g) ? 1.0 : (d >= -708.0 ? E(d) : 0.0)
+ *         (a NaN d gives 0; e[g] is 1.0 by definition, so S >= 1 whatever the logits hold)
+ *     S = 0.0;  for o in order:  S = S + e[o]
+ *     r[0 .. 3] = the draw of (seed, i, t) with number j = 1  (0xE9100000u + 1; the epsilon-greedy draw is j = 0)
+ *     u = U(r[0], r[1]);  v = u * S
+ *     c = 0.0;  id = g;  for o in order:  c = c + e[o];  the FIRST o with v < c becomes id
+ *         (an id with e[o] == 0 can never be taken; if rounding leaves none, id stays g)
+ *     prob = e[id] / S
+ * At the corners: best = +-inf or all-NaN logits leave e[g] = 1.0 as the only weight (every other d is NaN or -inf), so id = g and
+ * prob = 1.0 / S = 1.0; ties at the maximum share the mass, because E(+-0.0) == 1.0. */
+typedef struct mgx_sampling {
+    int32_t struct_size;      /* = sizeof(mgx_sampling) */
+    int32_t reserved;
+    uint64_t seed;            /* Philox key */
+    double temperature;       /* tau >= 0, finite; 0: the greedy head */
+    const double *scale;      /* device [N] or NULL (= 1.0 for every grid): multiplies the temperature of grid i */
+} mgx_sampling;
+
+/* mgx_rollout_policy_episodes with the discrete head sampling by the rule of mgx_sampling: one launch of
+ * rollout_policy_sample_episodes_kernel.  action_id_out receives the ids taken; prob_out: double [K, N], the probability of the id
+ * taken at every step, or NULL.  Every other argument, result and refusal as mgx_rollout_policy_episodes; on top MGX_ERR_INVALID for
+ * a NULL sampling, sampling->struct_size != sizeof(mgx_sampling), a negative, infinite or NaN temperature.
+ * An ADDITION to ABI 9 that leaves MGX_ABI_MINOR at 3: consumers find it by name (dlsym). */
+int mgx_rollout_policy_sample_episodes(mgx_handle *h, const mgx_policy *policy, const mgx_sampling *sampling, const int32_t *table,
+                                       int32_t n_actions, int32_t K, double *reward, uint8_t *done, double *soc_trace,
+                                       uint32_t *status_trace, uint8_t *action_id_out, double *prob_out,
+                                       const mgx_episode_stats *stats, const mgx_episode_rows *rows, mgx_stream stream);
+
 /* raise_errors=True (BaseMicrogridModule.__init__, base_module.py:40; as_source / as_sink, :213-224,265-270; _raise_error,
  * :79-93): the reference refuses a request a module cannot meet with a ValueError instead of clipping it.  mgx_step always
  * clips; mgx_check_step is its DRY RUN -- the same arithmetic on a register copy of the state, nothing stored, the counter

@@ -25,7 +25,8 @@ UNITS = (
     ("mgx_policy_episodes.hip", "MGX_EPISODE_PART", 2),                 # ... the closed-loop roll-out (a policy inside the launch)
     ("mgx_step_policy_episodes.hip", "MGX_EPISODE_PART", 2),            # ... and its continuous twin,
     ("mgx_policy_explore_episodes.hip", "MGX_EPISODE_PART", 2),         # ... the closed-loop roll-out with an exploring head
-    ("mgx_step_policy_explore_episodes.hip", "MGX_EPISODE_PART", 2),    # ... and its continuous twin
+    ("mgx_step_policy_explore_episodes.hip", "MGX_EPISODE_PART", 2),    # ... and its continuous twin,
+    ("mgx_policy_sample_episodes.hip", "MGX_EPISODE_PART", 2),          # ... the closed-loop roll-out with a softmax-sampling head
 )
 # everything a built library is stamped with (source_hash): a file missing here would leave a stale libmgx.so looking current
 SOURCES = [os.path.join(_PKG, "csrc", f) for f in [u[0] for u in UNITS] + ["mgx_kernels.hpp", "mgx_core.hpp", "mgx_episode_loop.hpp", "mgx_episode_rows.hpp", "mgx_policy.hpp"]] + \
@@ -158,6 +159,12 @@ class Exploration(C.Structure):
                 ("sigma", C.c_double * 4), ("scale", C.c_void_p)]
 
 
+class Sampling(C.Structure):
+    """mgx_sampling (include/mgx.h): the sampling head of ``mgx_rollout_policy_sample_episodes`` (``scale`` float64 device [N] or NULL)."""
+    _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32), ("seed", C.c_uint64), ("temperature", C.c_double),
+                ("scale", C.c_void_p)]
+
+
 POLICY_MAX_HIDDEN = 64     # MGX_POLICY_MAX_HIDDEN
 POLICY_LDS_BYTES = 32768   # MGX_POLICY_LDS_BYTES
 
@@ -242,6 +249,9 @@ SYMBOLS = {
     "mgx_step_k_policy_explore_episodes": (C.c_int, [C.c_void_p, C.POINTER(Policy), C.POINTER(Exploration), C.c_int32, C.c_void_p,
                                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(EpisodeStats),
                                                      C.POINTER(EpisodeRows), C.c_void_p]),
+    "mgx_rollout_policy_sample_episodes": (C.c_int, [C.c_void_p, C.POINTER(Policy), C.POINTER(Sampling), c_i32_p, C.c_int32, C.c_int32,
+                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                     C.POINTER(EpisodeStats), C.POINTER(EpisodeRows), C.c_void_p]),
     "mgx_metrics": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "mgx_reset_windows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_void_p]),

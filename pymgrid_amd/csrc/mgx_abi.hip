@@ -2156,26 +2156,45 @@ static int exploration_refusal(mgx_handle *h, const mgx_exploration *explore, co
     return MGX_OK;
 }
 
-// The closed-loop roll-out, greedy (explore == NULL: rollout_policy_episodes_kernel) or exploring
-// (rollout_policy_explore_episodes_kernel): every check, then one launch.
-static int rollout_policy_episodes_impl(mgx_handle *h, const mgx_policy *policy, const mgx_exploration *explore, const int32_t *table,
-                                        int32_t n_actions, int32_t K, double *reward, uint8_t *done, double *soc_trace,
-                                        uint32_t *status_trace, uint8_t *action_id_out, const mgx_episode_stats *stats,
-                                        const mgx_episode_rows *rows, mgx_stream stream, const char *fn)
+// ... and of a mgx_sampling (never NULL here); `sa` is what the sampling kernel takes by value
+static int sampling_refusal(const mgx_sampling *sampling, const char *fn, SampleArgs &sa)
 {
-    if (!h || !policy || !table) return fail(MGX_ERR_INVALID, "%s: NULL argument", fn);
+    if (sampling->struct_size != (int32_t)sizeof(mgx_sampling))
+        return fail(MGX_ERR_INVALID, "%s: sampling->struct_size is %d, sizeof(mgx_sampling) is %d", fn, sampling->struct_size,
+                    (int)sizeof(mgx_sampling));
+    if (!(sampling->temperature >= 0.0 && sampling->temperature < __builtin_inf()))
+        return fail(MGX_ERR_INVALID, "%s: sampling->temperature is %g, negative, infinite or NaN", fn, sampling->temperature);
+    sa = SampleArgs{sampling->seed, sampling->temperature, sampling->scale};
+    return MGX_OK;
+}
+
+// The closed-loop roll-out, greedy (no explore, no sampling: rollout_policy_episodes_kernel), exploring
+// (rollout_policy_explore_episodes_kernel) or sampling (`sample`: rollout_policy_sample_episodes_kernel, which needs a
+// mgx_sampling): every check, then one launch.
+static int rollout_policy_episodes_impl(mgx_handle *h, const mgx_policy *policy, const mgx_exploration *explore, bool sample,
+                                        const mgx_sampling *sampling, const int32_t *table, int32_t n_actions, int32_t K, double *reward,
+                                        uint8_t *done, double *soc_trace, uint32_t *status_trace, uint8_t *action_id_out,
+                                        double *prob_out, const mgx_episode_stats *stats, const mgx_episode_rows *rows,
+                                        mgx_stream stream, const char *fn)
+{
+    if (!h || !policy || !table || (sample && !sampling)) return fail(MGX_ERR_INVALID, "%s: NULL argument", fn);
     if (int rc = policy_struct_refusal(policy, fn)) return rc;
     const mgx_episode_rows none{(int32_t)sizeof(mgx_episode_rows), 0, nullptr, nullptr};
     PLWords tab;
     EpisodePolicyLaunch P{};
     if (int rc = exploration_refusal(h, explore, fn, P.ex)) return rc;
+    if (sample)
+        if (int rc = sampling_refusal(sampling, fn, P.sa)) return rc;
     if (int rc = prepare_episode_launch(h, K, reward, done, soc_trace, status_trace, stats, rows ? rows : &none, stream, fn,
                                         "mgx_rollout_discrete", "mgx_step_lists", table, n_actions, &tab, P.r)) return rc;
     if (int rc = policy_dims_refusal(h, policy, tab.n_actions, 4, "n_actions", fn, P)) return rc;
-    P.r.e.tab = &tab; P.actions_out = action_id_out;
-    const bool launched = explore ? launch_rollout_policy_explore_episodes_p0(P) || launch_rollout_policy_explore_episodes_p1(P)
-                                  : launch_rollout_policy_episodes_p0(P) || launch_rollout_policy_episodes_p1(P);
-    return finish_episode_launch(h, P.r.e, launched, explore ? "rollout_policy_explore_episodes_kernel launch" : "rollout_policy_episodes_kernel launch", fn);
+    P.r.e.tab = &tab; P.actions_out = action_id_out; P.prob_out = prob_out;
+    const bool launched = sample    ? launch_rollout_policy_sample_episodes_p0(P) || launch_rollout_policy_sample_episodes_p1(P)
+                          : explore ? launch_rollout_policy_explore_episodes_p0(P) || launch_rollout_policy_explore_episodes_p1(P)
+                                    : launch_rollout_policy_episodes_p0(P) || launch_rollout_policy_episodes_p1(P);
+    return finish_episode_launch(h, P.r.e, launched,
+                                 sample    ? "rollout_policy_sample_episodes_kernel launch"
+                                 : explore ? "rollout_policy_explore_episodes_kernel launch" : "rollout_policy_episodes_kernel launch", fn);
 }
 
 int mgx_rollout_policy_episodes(mgx_handle *h, const mgx_policy *policy, const int32_t *table, int32_t n_actions, int32_t K,
@@ -2183,8 +2202,8 @@ int mgx_rollout_policy_episodes(mgx_handle *h, const mgx_policy *policy, const i
                                 const mgx_episode_stats *stats, const mgx_episode_rows *rows, mgx_stream stream)
 {
     g_err[0] = 0;
-    return rollout_policy_episodes_impl(h, policy, nullptr, table, n_actions, K, reward, done, soc_trace, status_trace, action_id_out, stats,
-                                        rows, stream, "mgx_rollout_policy_episodes");
+    return rollout_policy_episodes_impl(h, policy, nullptr, false, nullptr, table, n_actions, K, reward, done, soc_trace, status_trace,
+                                        action_id_out, nullptr, stats, rows, stream, "mgx_rollout_policy_episodes");
 }
 
 // an exploring call without a mgx_exploration is the greedy call
@@ -2194,8 +2213,20 @@ int mgx_rollout_policy_explore_episodes(mgx_handle *h, const mgx_policy *policy,
                                         const mgx_episode_rows *rows, mgx_stream stream)
 {
     g_err[0] = 0;
-    return rollout_policy_episodes_impl(h, policy, explore, table, n_actions, K, reward, done, soc_trace, status_trace, action_id_out, stats,
-                                        rows, stream, explore ? "mgx_rollout_policy_explore_episodes" : "mgx_rollout_policy_episodes");
+    return rollout_policy_episodes_impl(h, policy, explore, false, nullptr, table, n_actions, K, reward, done, soc_trace, status_trace,
+                                        action_id_out, nullptr, stats, rows, stream,
+                                        explore ? "mgx_rollout_policy_explore_episodes" : "mgx_rollout_policy_episodes");
+}
+
+// the sampling call: a mgx_sampling is required (temperature 0 is how it asks for the greedy head)
+int mgx_rollout_policy_sample_episodes(mgx_handle *h, const mgx_policy *policy, const mgx_sampling *sampling, const int32_t *table,
+                                       int32_t n_actions, int32_t K, double *reward, uint8_t *done, double *soc_trace,
+                                       uint32_t *status_trace, uint8_t *action_id_out, double *prob_out,
+                                       const mgx_episode_stats *stats, const mgx_episode_rows *rows, mgx_stream stream)
+{
+    g_err[0] = 0;
+    return rollout_policy_episodes_impl(h, policy, nullptr, true, sampling, table, n_actions, K, reward, done, soc_trace, status_trace,
+                                        action_id_out, prob_out, stats, rows, stream, "mgx_rollout_policy_sample_episodes");
 }
 
 // The closed-loop continuous K-step, greedy (explore == NULL: step_k_policy_episodes_kernel) or exploring

@@ -13,7 +13,8 @@
 // load_lane_factors, fill_row_ring, rotate_ring, restart_lane or advance_row_ring is made there too.
 // The two exploring twins of the policy kernels (rollout_policy_explore_episodes_kernel: mgx_policy_explore_episodes.hip,
 // step_k_policy_explore_episodes_kernel: mgx_step_policy_explore_episodes.hip) are a seventh and eighth loop on the same pieces,
-// compiled the same way; they CALL all five ring helpers (their register figures on them: DESIGN.md's kernel table).
+// compiled the same way; they CALL all five ring helpers (their register figures on them: DESIGN.md's kernel table).  So does the
+// sampling twin of the discrete policy kernel (rollout_policy_sample_episodes_kernel: mgx_policy_sample_episodes.hip), a ninth.
 #pragma once
 #include "mgx_kernels.hpp"
 

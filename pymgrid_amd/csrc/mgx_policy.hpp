@@ -4,7 +4,9 @@
 // lane's row strip -- the H = 0 row is built ONCE per step into the wave's tile, read back as the policy's input and, where
 // the launch returns observations, streamed out of the same tile as the row the step before returned.  Their exploring twins
 // (mgx_rollout_policy_explore_episodes: mgx_policy_explore_episodes.hip, mgx_step_k_policy_explore_episodes:
-// mgx_step_policy_explore_episodes.hip) add the draw, the epsilon choice and the noise of mgx_exploration, each stated once below.
+// mgx_step_policy_explore_episodes.hip) add the draw, the epsilon choice and the noise of mgx_exploration, each stated once below;
+// the sampling twin of the discrete launch (mgx_rollout_policy_sample_episodes: mgx_policy_sample_episodes.hip) the exp and the
+// softmax-sampling head of mgx_sampling.
 // On top of mgx_episode_rows.hpp (the rows) and, through it, mgx_episode_loop.hpp (what all six episode loops share).
 #pragma once
 #include "mgx_episode_rows.hpp"
@@ -117,11 +119,12 @@ __device__ __forceinline__ void policy_outputs(const double *w, int32_t nh, int3
     }
 }
 
-// the discrete head: the lowest o whose y[o] is strictly greater than everything before it, from -inf (a NaN never wins)
+// the discrete head: the lowest o whose y[o] is strictly greater than everything before it, from -inf (a NaN never wins);
+// `best`: that greatest value (-inf where nothing won)
 template <int NO>
-__device__ __forceinline__ int32_t policy_argmax(const double (&y)[NO], int32_t no)
+__device__ __forceinline__ int32_t policy_argmax(const double (&y)[NO], int32_t no, double &best)
 {
-    double best = -__builtin_inf();
+    best = -__builtin_inf();
     int32_t id = 0;
 #pragma unroll
     for (int o = 0; o < NO; o++)
@@ -131,6 +134,12 @@ __device__ __forceinline__ int32_t policy_argmax(const double (&y)[NO], int32_t 
             id = m ? o : id;
         }
     return id;
+}
+template <int NO>
+__device__ __forceinline__ int32_t policy_argmax(const double (&y)[NO], int32_t no)
+{
+    double best;
+    return policy_argmax<NO>(y, no, best);
 }
 
 // the continuous head: a normalised control
@@ -181,6 +190,88 @@ __device__ __forceinline__ double policy_noisy_clip(double y, double s, uint64_t
 {
     const double z = explore_normal(seed, i, t, j);
     return policy_clip(y + s * z);
+}
+
+// ---- sampling: the rule of mgx_sampling (include/mgx.h), for rollout_policy_sample_episodes_kernel (mgx_policy_sample_episodes.hip) ----
+// mgx_sampling as the kernel sees it, by value in its argument struct
+struct SampleArgs {
+    uint64_t seed;
+    double temperature;
+    const double *scale;             // [N] or NULL
+};
+
+// what a lane carries across the loop: beta = 1 / tau, or -1.0 where !(tau > 0) -- the lane takes the greedy id (a beta is never negative)
+__device__ __forceinline__ double sample_lane_beta(const SampleArgs &sa, int64_t i)
+{
+    const double tau = sa.temperature * explore_lane_scale(sa.scale, i);
+    return tau > 0.0 ? 1.0 / tau : -1.0;
+}
+
+// E(d) for -708 <= d <= 0: exp as a fixed sequence of IEEE operations (the build has -ffp-contract=off), no libm
+__device__ __forceinline__ double policy_exp(double d)
+{
+    const double k = floor(d * 1.4426950408889634 + 0.5);
+    const double r = (d - k * 6.93147180369123816490e-01) - k * 1.90821492927058770002e-10;
+    double p = 1.6059043836821613e-10;                                                   // the doubles nearest 1/n!, n = 13 .. 0
+    p = p * r + 2.08767569878681e-09;
+    p = p * r + 2.505210838544172e-08;
+    p = p * r + 2.755731922398589e-07;
+    p = p * r + 2.7557319223985893e-06;
+    p = p * r + 2.48015873015873e-05;
+    p = p * r + 0.0001984126984126984;
+    p = p * r + 0.001388888888888889;
+    p = p * r + 0.008333333333333333;
+    p = p * r + 0.041666666666666664;
+    p = p * r + 0.16666666666666666;
+    p = p * r + 0.5;
+    p = p * r + 1.0;
+    p = p * r + 1.0;
+    return p * __longlong_as_double((long long)((uint64_t)((int32_t)k + 1023) << 52));  // 2^k, k in [-1021, 0]: a normal number
+}
+
+// the sampling head: the weights e[o] written OVER y[o] (static indices, no second array), their sum, then -- only now, so that the
+// draw holds no register beside the outputs -- the draw and the inverse CDF.  Returns the id taken, `prob` its probability.
+// `no`: the REAL ids; the outputs go in the groups of four of policy_outputs (a padding output weighs 0.0 and is never taken).
+template <int NO>
+__device__ __forceinline__ int32_t policy_sample(double (&y)[NO], int32_t no, double beta, uint64_t seed, int64_t i, int32_t t, double &prob)
+{
+    constexpr int G = NO < 4 ? NO : 4;
+    double best;
+    const int32_t g = policy_argmax<NO>(y, no, best);
+    const double b = beta >= 0.0 ? beta : 0.0;                                            // (a greedy lane: weights nobody reads, d in range)
+    double S = 0.0;
+#pragma unroll
+    for (int c = 0; c < NO; c += G) {
+        if (c < no) {
+#pragma unroll
+            for (int o = c; o < c + G; o++) {
+                const double d = (y[o] - best) * b;
+                const bool in = d >= -708.0;                                              // (false for a NaN)
+                const double e = policy_exp(in ? d : -708.0);
+                y[o] = o < no ? (o == g ? 1.0 : (in ? e : 0.0)) : 0.0;
+                S = S + y[o];
+            }
+        } else {
+#pragma unroll
+            for (int o = c; o < c + G; o++) y[o] = 0.0;
+        }
+    }
+    uint32_t r[4];
+    explore_draw(seed, i, t, 1u, r);
+    const double v = uniform53(r[0], r[1]) * S;
+    double c = 0.0, e_id = 1.0;
+    int32_t id = g;
+    bool open = beta >= 0.0;                                                              // (a greedy lane takes nothing)
+#pragma unroll
+    for (int o = 0; o < NO; o++) {
+        c = c + y[o];
+        const bool take = open && v < c;
+        id = take ? o : id;
+        e_id = take ? y[o] : e_id;
+        open = open && !take;
+    }
+    prob = beta >= 0.0 ? e_id / S : 1.0;
+    return id;
 }
 
 // columns of an H = 0 row of layout F
@@ -269,17 +360,27 @@ struct StepPolicyExploreArgs {
     ExploreArgs ex;
 };
 
-// ---- host side: what mgx_abi.hip hands the slices of the four translation units ----
+// ... and of the sampling kernel: the same way, the sampling and the stream of probabilities behind the greedy kernel's struct
+struct RolloutPolicySampleArgs {
+    RolloutPolicyArgs g;
+    SampleArgs sa;
+    double *prob_out;                // [K, N] or NULL
+};
+
+// ---- host side: what mgx_abi.hip hands the slices of the five translation units ----
 struct EpisodePolicyLaunch {
     EpisodeRowsLaunch r;             // as for the kernels with rows (obs / final_obs may both be NULL here)
     PolicyArgs pol;
     unsigned lds_bytes;              // n_policies * stride doubles: the dynamic LDS of the launch
     void *actions_out;               // the ids (uint8 [K, N]) or controls (double [K, N, A]) the policy chose, or NULL
     ExploreArgs ex;                  // the exploring kernels alone read it
+    SampleArgs sa;                   // ... the sampling kernel alone these two
+    double *prob_out;
 };
 bool launch_rollout_policy_episodes_p0(const EpisodePolicyLaunch &L); bool launch_rollout_policy_episodes_p1(const EpisodePolicyLaunch &L);
 bool launch_step_k_policy_episodes_p0(const EpisodePolicyLaunch &L); bool launch_step_k_policy_episodes_p1(const EpisodePolicyLaunch &L);
 bool launch_rollout_policy_explore_episodes_p0(const EpisodePolicyLaunch &L); bool launch_rollout_policy_explore_episodes_p1(const EpisodePolicyLaunch &L);
 bool launch_step_k_policy_explore_episodes_p0(const EpisodePolicyLaunch &L); bool launch_step_k_policy_explore_episodes_p1(const EpisodePolicyLaunch &L);
+bool launch_rollout_policy_sample_episodes_p0(const EpisodePolicyLaunch &L); bool launch_rollout_policy_sample_episodes_p1(const EpisodePolicyLaunch &L);
 
 }  // namespace mgx

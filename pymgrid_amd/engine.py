@@ -775,51 +775,65 @@ class StepEngine:
         return self._launch_episodes("mgx_step_k_episodes", (_ptr(actions), K, 1 if normalized else 0), K, res, (r, d, s, g), st, out,
                                      obs, final_obs)
 
-    def _launch_policy_episodes(self, symbol, policy, exploration, lead, K, res, bufs, taken, st, out, obs, final_obs):
+    def _launch_policy_episodes(self, symbol, policy, exploration, lead, K, res, bufs, taken, st, out, obs, final_obs, sampling=None,
+                                probs=None):
         """The tail of the closed-loop episode launches: ``symbol`` -- with an ``exploration`` its exploring form, which takes the
-        ``mgx_exploration`` behind the policy -- with the policy's ``mgx_policy``, the call's own arguments ``lead``, the four outputs,
-        the buffer of the actions taken, the statistics and the rows (NULL: none asked for); K steps on."""
+        ``mgx_exploration`` behind the policy, with a ``sampling`` its sampling form, which takes the ``mgx_sampling`` there and the
+        buffer ``probs`` behind the actions taken -- with the policy's ``mgx_policy``, the call's own arguments ``lead``, the four
+        outputs, the buffer of the actions taken, the statistics and the rows (NULL: none asked for); K steps on."""
+        if exploration is not None and sampling is not None:
+            raise ValueError("exploration= and sampling= exclude each other: the sampling head draws from the policy's own distribution")
         pst, keep = policy.c_struct(self.device, self.N)
-        head = (C.byref(pst),)
+        head, behind = (C.byref(pst),), ()
         if exploration is not None:
             xst, keep_x = exploration.c_struct(self.device, self.N)
             symbol, head = symbol.replace("_policy_", "_policy_explore_"), (C.byref(pst), C.byref(xst))
+        if sampling is not None:
+            xst, keep_x = sampling.c_struct(self.device, self.N)
+            symbol, head, behind = symbol.replace("_policy_", "_policy_sample_"), (C.byref(pst), C.byref(xst)), (_ptr(probs),)
         rows = self._episode_rows(res, out, K, obs, final_obs)
-        self._call(getattr(self._lib, symbol), *head, *lead, *map(_ptr, bufs), _ptr(taken), C.byref(st),
+        self._call(getattr(self._lib, symbol), *head, *lead, *map(_ptr, bufs), _ptr(taken), *behind, C.byref(st),
                    None if rows is None else C.byref(rows))
         del keep
         if self._t is not None:
             self._t += K
         return res
 
-    def _actions_out(self, res, out, want, shape, dtype):
-        """The buffer of the actions a closed-loop launch took (``actions=True``): from ``out["actions"]`` or allocated."""
+    def _actions_out(self, res, out, want, shape, dtype, name="actions"):
+        """The buffer of the actions a closed-loop launch took (``actions=True``): from ``out["actions"]`` or allocated; under
+        ``name="probs"`` the buffer of their probabilities."""
         if not want:
             return None
-        t = out.get("actions")
+        t = out.get(name)
         if t is None:
             t = self._empty(*shape, dtype=dtype)
         elif t.dtype != dtype or t.device != self.device or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
-            raise ValueError(f"out['actions'] must be a contiguous {dtype} tensor {list(shape)} on {self.device}")
-        res["actions"] = t
+            raise ValueError(f"out[{name!r}] must be a contiguous {dtype} tensor {list(shape)} on {self.device}")
+        res[name] = t
         return t
 
     def rollout_policy_episodes(self, policy, table, K, reward=True, done=False, soc_trace=False, status_trace=False, actions=False,
-                                stats=None, out=None, obs=False, final_obs=False, exploration=None):
+                                stats=None, out=None, obs=False, final_obs=False, exploration=None, sampling=None, probs=False):
         """``rollout_episodes`` with the loop closed inside the launch (``mgx_rollout_policy_episodes``): the priority-list id of
         every step is ``policy`` (an ``MLPPolicy`` with ``head="discrete"``, ``n_out`` = rows of ``table``) applied to the observation
         row the grid stands on -- what K times ``ids = policy.act(obs); obs, ... = step_discrete(ids, table)`` leaves, bit for bit.
         ``actions=True``: also the ids taken (uint8 [K, N]).  No forecast horizon, whole rows; everything else as ``rollout_episodes``.
         ``exploration`` (``pymgrid_amd.policy.Exploration``): the head explores inside the launch (``mgx_rollout_policy_explore_episodes``)
-        -- what ``ids = policy.act(obs, exploration, counter)`` with the counter before each step leaves, bit for bit."""
+        -- what ``ids = policy.act(obs, exploration, counter)`` with the counter before each step leaves, bit for bit.
+        ``sampling`` (``pymgrid_amd.policy.Sampling``; not together with ``exploration``): the ids are drawn from the policy's
+        softmax inside the launch (``mgx_rollout_policy_sample_episodes``) -- what ``policy.act(obs, sampling, counter)`` leaves, bit
+        for bit; ``probs=True`` then also returns the probability of every id taken (float64 [K, N])."""
         out = out or {}
         K = int(K)
+        if probs and sampling is None:
+            raise ValueError("probs=True goes with sampling=: the other heads take their id with certainty or by a uniform draw")
         st = self._episode_stats(stats)
         tptr, n_lists = self._table_ptr(table)
         res, r, d, s, g, _ = self._fused_outputs(out, K, reward, done, soc_trace, status_trace)
         taken = self._actions_out(res, out, actions, (K, self.N), torch.uint8)
+        pr = self._actions_out(res, out, probs, (K, self.N), torch.float64, name="probs")
         return self._launch_policy_episodes("mgx_rollout_policy_episodes", policy, exploration, (tptr, n_lists, K), K, res, (r, d, s, g),
-                                            taken, st, out, obs, final_obs)
+                                            taken, st, out, obs, final_obs, sampling=sampling, probs=pr)
 
     def step_k_policy_episodes(self, policy, K, reward=True, done=False, soc_trace=False, status_trace=False, actions=False,
                                stats=None, out=None, obs=False, final_obs=False, exploration=None):

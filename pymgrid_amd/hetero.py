@@ -804,7 +804,7 @@ class PerGridWindowEnv:
             raise RuntimeError(f"{kind}_policy() before reset()")
 
     def rollout_policy(self, policy, K, reward=True, done=False, soc_trace=False, status_trace=False, actions=False,
-                       observations=False, final_observations=False, out=None, exploration=None):
+                       observations=False, final_observations=False, out=None, exploration=None, sampling=None, probs=False):
         """``rollout`` with the loop CLOSED inside the launch (``mgx_rollout_policy_episodes``; ``discrete=True``): the id of every step
         is ``policy`` (``pymgrid_amd.policy.MLPPolicy``, ``head="discrete"``, one output per priority list) applied to the
         observation the grid's last step -- or reset, or restart inside the launch -- returned, in the env's ``obs_dtype``.  K steps
@@ -813,24 +813,33 @@ class PerGridWindowEnv:
         ``observations`` / ``final_observations`` and ``out=`` as for ``rollout``.  Needs what ``rollout`` with observations needs: no
         forecast horizon, no ``observation_keys``.  ``exploration`` (``pymgrid_amd.policy.Exploration``): epsilon-greedy inside the
         launch (``mgx_rollout_policy_explore_episodes``); the stepped twin is
-        ``ids = policy.act(obs, exploration, counter=env.current_step)`` before every ``step(ids)``."""
+        ``ids = policy.act(obs, exploration, counter=env.current_step)`` before every ``step(ids)``.  ``sampling``
+        (``pymgrid_amd.policy.Sampling``; not together with ``exploration``): the ids are drawn from ``softmax(y / temperature)`` inside
+        the launch (``mgx_rollout_policy_sample_episodes``), ``probs=True`` also returns the probability of every id taken (float64
+        ``[K, N]``; its ``torch.log`` is the log-probability the on-policy methods need); the stepped twin is
+        ``ids, prob = policy.act(obs, sampling, counter=env.current_step, return_prob=True)``."""
         env = self.env
         self._check_fused("rollout", True, policy=True)
         self._check_policy("rollout", policy, "discrete", int(np.asarray(env._table).shape[0]), "the env's priority-list table")
         self._check_exploration(exploration)
+        self._check_exploration(sampling, "sampling")
         return self._launch_fused(lambda **kw: env.engine.rollout_policy_episodes(policy, env._table, int(K), **kw), observations,
                                   final_observations, reward=reward, done=done, soc_trace=soc_trace, status_trace=status_trace,
-                                  actions=actions, out=out, exploration=exploration)
+                                  actions=actions, out=out, exploration=exploration, sampling=sampling, probs=probs)
 
     def step_k_policy(self, policy, K, reward=True, done=False, soc_trace=False, status_trace=False, actions=False,
-                      observations=False, final_observations=False, out=None, exploration=None):
+                      observations=False, final_observations=False, out=None, exploration=None, sampling=None):
         """``step_k`` with the loop CLOSED inside the launch (``mgx_step_k_policy_episodes``; ``discrete=False``, float64 controls):
         the controls of every step are ``policy`` (``MLPPolicy``, ``head="continuous"``, one output per action column) applied to the
         observation the grid's last step returned, stepped as ``step(u, normalized=True)``.  K steps leave exactly what K times
         ``u = policy.act(obs); obs, r, done, _ = step(u)`` leave, bit for bit; ``actions=True`` also returns the controls taken
         (float64 ``[K, N, A]``), which the open-loop ``step_k`` replays.  Everything else as ``rollout_policy``; ``exploration``: its
-        noise on every control before the clip (``mgx_step_k_policy_explore_episodes``)."""
+        noise on every control before the clip (``mgx_step_k_policy_explore_episodes``).  ``sampling`` is refused: it is the
+        discrete head's (a Gaussian policy on this head is ``exploration`` with its ``sigma``)."""
         e = self.env.engine
+        if sampling is not None:
+            raise ValueError("PerGridWindowEnv.step_k_policy takes no sampling=: softmax sampling is offered on the discrete head "
+                             "(rollout_policy); the continuous head explores with Exploration(sigma=...)")
         self._check_fused("step_k", True, policy=True)
         self._check_policy("step_k", policy, "continuous", e.action_dim, "the layout's action columns")
         self._check_exploration(exploration)
@@ -840,10 +849,10 @@ class PerGridWindowEnv:
                                   reward=reward, done=done, soc_trace=soc_trace, status_trace=status_trace, actions=actions, out=out,
                                   exploration=exploration)
 
-    def _check_exploration(self, exploration):
-        """... and of an ``exploration``: a ``scale`` that does not name the env's grids."""
+    def _check_exploration(self, exploration, name="exploration"):
+        """... and of an ``exploration`` (or a ``sampling``, under that ``name``): a ``scale`` that does not name the env's grids."""
         if exploration is not None and exploration.scale is not None and exploration.scale.shape[0] != self.env.engine.N:
-            raise ValueError(f"exploration.scale names {exploration.scale.shape[0]} grids, the env {self.env.engine.N}")
+            raise ValueError(f"{name}.scale names {exploration.scale.shape[0]} grids, the env {self.env.engine.N}")
 
     def _next_final_buf(self):
         """One of FINAL_BUFFERS rotating [N, D] buffers for ``info["final_observation"]`` (valid for FINAL_BUFFERS - 1 further steps)."""

@@ -117,6 +117,55 @@ class Exploration:
         return st, sc
 
 
+EXP_COEFFS = (1.0, 1.0, 0.5, 0.16666666666666666, 0.041666666666666664, 0.008333333333333333, 0.001388888888888889,
+              0.0001984126984126984, 2.48015873015873e-05, 2.7557319223985893e-06, 2.755731922398589e-07, 2.505210838544172e-08,
+              2.08767569878681e-09, 1.6059043836821613e-10)      # the doubles nearest 1/n!, n = 0 .. 13 (include/mgx.h, mgx_sampling)
+EXP_MIN = -708.0
+
+
+def policy_exp(d):
+    """``E(d)`` of ``mgx_sampling`` (include/mgx.h) for a float64 tensor ``-708 <= d <= 0``: the device's ``policy_exp`` operation by
+    operation -- separate multiplies and adds, the scale ``2**k`` built from its bits -- so the two agree bit for bit."""
+    k = torch.floor(d * 1.4426950408889634 + 0.5)
+    r = (d - k * 6.93147180369123816490e-01) - k * 1.90821492927058770002e-10
+    p = torch.full_like(d, EXP_COEFFS[13])
+    for n in range(12, -1, -1):
+        p = p * r + EXP_COEFFS[n]
+    return p * ((k.to(torch.int64) + 1023) << 52).view(torch.float64)
+
+
+class Sampling:
+    """What the sampling closed-loop launch adds to a discrete ``MLPPolicy`` (``mgx_sampling``, include/mgx.h): the id of every step is
+    drawn from ``softmax(y / temperature)`` by a counter-based draw keyed by ``seed``, and the launch returns the probability of the id
+    taken.  ``scale`` (float64 ``[N]``, numpy or torch) multiplies the temperature of grid i (a ladder; 0 switches a grid back to the
+    greedy head, as ``temperature=0`` does for all).  Validated as the C call does."""
+
+    def __init__(self, seed, temperature=1.0, scale=None):
+        self.seed = int(seed)
+        if not 0 <= self.seed < 2 ** 64:
+            raise ValueError(f"seed = {seed}: a 64-bit unsigned key")
+        self.temperature = float(temperature)
+        if not 0.0 <= self.temperature < float("inf"):
+            raise ValueError(f"temperature = {temperature}: finite and >= 0")
+        self.scale = None
+        if scale is not None:
+            t = scale if torch.is_tensor(scale) else torch.as_tensor(np.asarray(scale))
+            if t.dtype != torch.float64 or t.dim() != 1:
+                raise ValueError(f"scale must be a float64 vector [N], not {t.dtype} {tuple(t.shape)}")
+            self.scale = t.contiguous()
+
+    scale_on = Exploration.scale_on
+
+    def c_struct(self, device, n_grids):
+        """``(mgx_sampling, keep-alive)`` with ``scale`` on ``device``."""
+        st = _lib.Sampling()
+        st.struct_size = C.sizeof(_lib.Sampling)
+        st.seed, st.temperature = self.seed, self.temperature
+        sc = self.scale_on(device, n_grids)
+        st.scale = None if sc is None else sc.data_ptr()
+        return st, sc
+
+
 class MLPPolicy:
     """``y = W2 . relu(W1 . x + b1) + b2`` (``W1 = b1 = None``: the linear policy ``y = W2 . x + b2``) on the observation row ``x``,
     every sum taken in index order with a separate multiply and add; ``relu(h) = h if h > 0 else +0.0``.
@@ -230,11 +279,22 @@ class MLPPolicy:
             x = torch.where(h > 0, h, torch.zeros_like(h))
         return self._layer(me.W2, me.b2, idx, x)
 
-    def act(self, obs, exploration=None, counter=None):
+    def act(self, obs, exploration=None, counter=None, return_prob=False):
         """The actions for observation rows ``obs`` [N, n_in]: priority-list ids (int32 [N]) or normalised controls (float64
         [N, n_out]) -- what the fused launches take, bit for bit.  ``exploration`` (an ``Exploration``) with ``counter``, the int the
         handle's shared step counter holds BEFORE the step (``env.current_step``): the host statement of the rule of
-        ``mgx_exploration`` (include/mgx.h) -- row n of ``obs`` is grid n -- and what the exploring launches take, bit for bit."""
+        ``mgx_exploration`` (include/mgx.h) -- row n of ``obs`` is grid n -- and what the exploring launches take, bit for bit.
+        A ``Sampling`` in its place (discrete head only): the rule of ``mgx_sampling``, what the sampling launch takes;
+        ``return_prob=True`` then returns ``(ids, prob)``, ``prob`` (float64 [N]) the probability of the id taken."""
+        if isinstance(exploration, Sampling):
+            if self.head != "discrete":
+                raise ValueError("sampling is offered on the discrete head (the continuous head explores with Exploration.sigma)")
+            if counter is None:
+                raise ValueError("sampling needs `counter`, the handle's step counter before the step (env.current_step)")
+            ids, prob = self._sample(self.outputs(obs), exploration, int(counter))
+            return (ids, prob) if return_prob else ids
+        if return_prob:
+            raise ValueError("return_prob=True goes with a Sampling")
         y = self.outputs(obs)
         n, dev = y.shape[0], y.device
         if exploration is not None:
@@ -250,12 +310,7 @@ class MLPPolicy:
                     cols.append(y[:, o] + s * explore_normal(exploration.seed, grid, int(counter), o))
                 y = torch.stack(cols, dim=1)
             return torch.where(~(y > 0), torch.zeros_like(y), torch.where(y > 1, torch.ones_like(y), y))
-        best = torch.full((n,), float("-inf"), dtype=torch.float64, device=dev)
-        ids = torch.zeros(n, dtype=torch.int32, device=dev)
-        for o in range(self.n_out):
-            m = y[:, o] > best
-            best = torch.where(m, y[:, o], best)
-            ids = torch.where(m, torch.full_like(ids, o), ids)
+        ids, _ = self._greedy(y)
         if exploration is not None:
             r = philox_words(exploration.seed, grid, int(counter), EXPLORE_TAG)
             u1, u2 = uniform53(r[0], r[1]), uniform53(r[2], r[3])
@@ -263,6 +318,56 @@ class MLPPolicy:
             k = torch.clamp((u2 * float(self.n_out)).floor().to(torch.int32), max=self.n_out - 1)
             ids = torch.where(u1 < e, k, ids)
         return ids
+
+    def _greedy(self, y):
+        """``(ids, best)`` of the discrete head on ``y`` [N, n_out]."""
+        n, dev = y.shape[0], y.device
+        best = torch.full((n,), float("-inf"), dtype=torch.float64, device=dev)
+        ids = torch.zeros(n, dtype=torch.int32, device=dev)
+        for o in range(self.n_out):
+            m = y[:, o] > best
+            best = torch.where(m, y[:, o], best)
+            ids = torch.where(m, torch.full_like(ids, o), ids)
+        return ids, best
+
+    def sample_weights(self, y, sampling):
+        """``(e, S, g, live)`` of the sampling head (``mgx_sampling``) on the outputs ``y`` [N, n_out]: the unnormalised weights
+        ``e`` [N, n_out], their sum in index order, the greedy ids and which grids sample at all (``tau > 0``; the others' weights
+        are not used)."""
+        n, dev = y.shape[0], y.device
+        g, best = self._greedy(y)
+        scale = sampling.scale_on(dev, n)
+        tau = torch.full((n,), sampling.temperature, dtype=torch.float64, device=dev)
+        if scale is not None:
+            tau = tau * scale
+        live = tau > 0
+        beta = 1.0 / torch.where(live, tau, torch.ones_like(tau))
+        cols = []
+        S = torch.zeros(n, dtype=torch.float64, device=dev)
+        for o in range(self.n_out):
+            d = (y[:, o] - best) * beta
+            ok = d >= EXP_MIN                                          # (False for a NaN)
+            e = torch.where(ok, policy_exp(torch.where(ok, d, torch.full_like(d, EXP_MIN))), torch.zeros_like(d))
+            cols.append(torch.where(g == o, torch.ones_like(e), e))
+            S = S + cols[-1]
+        return torch.stack(cols, dim=1), S, g, live
+
+    def _sample(self, y, sampling, counter):
+        """``(ids, prob)`` by the rule of ``mgx_sampling``: inverse CDF on the unnormalised weights with draw number 1."""
+        n, dev = y.shape[0], y.device
+        e, S, g, live = self.sample_weights(y, sampling)
+        r = philox_words(sampling.seed, torch.arange(n, dtype=torch.int64, device=dev), counter, EXPLORE_TAG + 1)
+        v = uniform53(r[0], r[1]) * S
+        c = torch.zeros_like(S)
+        ids, e_id = g.clone(), torch.ones_like(S)
+        open_ = torch.ones(n, dtype=torch.bool, device=dev)
+        for o in range(self.n_out):
+            c = c + e[:, o]
+            take = open_ & (v < c)
+            ids = torch.where(take, torch.full_like(ids, o), ids)
+            e_id = torch.where(take, e[:, o], e_id)
+            open_ = open_ & ~take
+        return torch.where(live, ids, g), torch.where(live, e_id / S, torch.ones_like(S))
 
     def c_struct(self, device, n_grids):
         """``(mgx_policy, keep-alive)`` with the parameters on ``device``."""
