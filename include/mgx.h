@@ -747,6 +747,60 @@ int mgx_rollout_policy_sample_episodes(mgx_handle *h, const mgx_policy *policy, 
                                        uint32_t *status_trace, uint8_t *action_id_out, double *prob_out,
                                        const mgx_episode_stats *stats, const mgx_episode_rows *rows, mgx_stream stream);
 
+/* A CRITIC beside the actor of the sampling launch: a value head on the trunk of a mgx_policy -- what A2C and PPO need of a
+ * collector on top of the ids and their probabilities.  THE RULE (stated here once), with n_mid = n_hidden ? n_hidden : n_in of
+ * the policy it goes with, v the policy's hidden vector after its ReLU (n_hidden > 0) or x (n_hidden = 0), ps the grid's
+ * parameter set by mgx_policy's own rule (policy_index, an index outside [0, n_policies): set 0):
+ *     V(x) = b[ps];  for j = 0 .. n_mid - 1 in order:  V = V + w[ps, j] * v[j]          (multiply and add separate)
+ * x is the H = 0 observation row as the handle's observation format holds it (a float32 row widened back): V is exactly one more
+ * output row of the same network. */
+typedef struct mgx_critic {
+    int32_t struct_size;      /* = sizeof(mgx_critic) */
+    int32_t reserved;
+    const double *w;          /* device [P, n_mid] */
+    const double *b;          /* device [P] */
+} mgx_critic;
+
+/* mgx_rollout_policy_sample_episodes with a critic: one launch of rollout_policy_critic_episodes_kernel.  Each of the three
+ * outputs may be NULL:
+ *   value_out        double [K, N]: V of the row the id of step k was chosen on (the row the policy reads at step k; after a
+ *                    restart inside the launch the first row of the new episode)
+ *   final_value_out  double [K, N]: V of the row mgx_episode_rows.final_obs[k, i, :] holds, written ONLY where step k restarted
+ *                    grid i -- every other entry keeps the caller's bytes (final_obs's rule), whether or not rows->final_obs is
+ *                    given.  Episodes end by their length, a time limit: the target at `done` bootstraps from this value
+ *   last_value_out   double [N]: V of the row the last step returned (obs[K - 1, i, :]), the bootstrap of a roll-out cut here
+ * Everything else the call leaves -- state, counter, episode arrays, draws, statistics, ids, probabilities, traces, rows -- is bit
+ * for bit what mgx_rollout_policy_sample_episodes leaves with the same policy and sampling: the critic changes no decision, and
+ * temperature == 0 stays the greedy head.  Refusals as the sampling call's; on top MGX_ERR_INVALID for a NULL critic,
+ * critic->struct_size != sizeof(mgx_critic), a NULL w or b, and MGX_ERR_UNSUPPORTED where the staged sets pass
+ * MGX_POLICY_LDS_BYTES: the critic adds 1 + n_mid doubles to a set, the launch stages
+ *     n_policies * 8 * even(m + 1 + (n_hidden ? n_hidden * (n_in + 2 + m) : n_in * (m + 1))) bytes,   m = n_out rounded up to a
+ * multiple of 4 (MGX_POLICY_LDS_BYTES states the formula without a critic).  Nothing is launched when the call is refused.
+ * An ADDITION to ABI 9 that leaves MGX_ABI_MINOR at 3: consumers find it by name (dlsym). */
+int mgx_rollout_policy_critic_episodes(mgx_handle *h, const mgx_policy *policy, const mgx_sampling *sampling, const mgx_critic *critic,
+                                       const int32_t *table, int32_t n_actions, int32_t K, double *reward, uint8_t *done,
+                                       double *soc_trace, uint32_t *status_trace, uint8_t *action_id_out, double *prob_out,
+                                       double *value_out, double *final_value_out, double *last_value_out,
+                                       const mgx_episode_stats *stats, const mgx_episode_rows *rows, mgx_stream stream);
+
+/* Generalised advantage estimation over the [K, N] outputs of such a launch, handle-free on the current device (as
+ * mgx_generate_columns): one launch of gae_kernel, one lane per grid walking k backwards.  reward, value, advantage, returns:
+ * double [K, N]; done: uint8 [K, N] in the byte form the launches write; final_value: double [K, N] or NULL (read only where done);
+ * last_value: double [N]; returns may be NULL.  THE RULE (stated here once; multiply and add separate):
+ *     c = gamma * lambda                       (one multiply, done once on the host)
+ *     per grid i:  next = last_value[i];  carry = 0.0
+ *     for k = K - 1 down to 0:
+ *         d     = done[k, i] != 0
+ *         nv    = d ? (final_value ? final_value[k, i] : 0.0) : next
+ *         delta = (reward[k, i] + gamma * nv) - value[k, i]
+ *         A     = d ? delta : delta + c * carry        (a select: a NaN carry does not cross an episode boundary)
+ *         advantage[k, i] = A;  returns[k, i] = A + value[k, i]
+ *         carry = A;  next = value[k, i]
+ * MGX_ERR_INVALID: N <= 0, K <= 0, a NULL reward / done / value / last_value / advantage, gamma or lambda outside [0, 1] or NaN.
+ * Outputs must not overlap inputs (not checked).  An ADDITION to ABI 9 that leaves MGX_ABI_MINOR at 3. */
+int mgx_gae(int64_t N, int32_t K, const double *reward, const uint8_t *done, const double *value, const double *final_value,
+            const double *last_value, double gamma, double lambda, double *advantage, double *returns, mgx_stream stream);
+
 /* raise_errors=True (BaseMicrogridModule.__init__, base_module.py:40; as_source / as_sink, :213-224,265-270; _raise_error,
  * :79-93): the reference refuses a request a module cannot meet with a ValueError instead of clipping it.  mgx_step always
  * clips; mgx_check_step is its DRY RUN -- the same arithmetic on a register copy of the state, nothing stored, the counter

@@ -27,9 +27,11 @@ UNITS = (
     ("mgx_policy_explore_episodes.hip", "MGX_EPISODE_PART", 2),         # ... the closed-loop roll-out with an exploring head
     ("mgx_step_policy_explore_episodes.hip", "MGX_EPISODE_PART", 2),    # ... and its continuous twin,
     ("mgx_policy_sample_episodes.hip", "MGX_EPISODE_PART", 2),          # ... the closed-loop roll-out with a softmax-sampling head
+    ("mgx_policy_critic_episodes.hip", "MGX_EPISODE_PART", 2),          # ... and that one with a critic beside the actor,
+    ("mgx_gae.hip", None, 1),                                           # the advantages of what such launches return (mgx_gae)
 )
 # everything a built library is stamped with (source_hash): a file missing here would leave a stale libmgx.so looking current
-SOURCES = [os.path.join(_PKG, "csrc", f) for f in [u[0] for u in UNITS] + ["mgx_kernels.hpp", "mgx_core.hpp", "mgx_episode_loop.hpp", "mgx_episode_rows.hpp", "mgx_policy.hpp"]] + \
+SOURCES = [os.path.join(_PKG, "csrc", f) for f in [u[0] for u in UNITS] + ["mgx_kernels.hpp", "mgx_core.hpp", "mgx_episode_loop.hpp", "mgx_episode_rows.hpp", "mgx_policy.hpp", "mgx_gae.hpp"]] + \
           [os.path.join(_ROOT, "include", "mgx.h")]
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-fPIC"]
@@ -165,6 +167,12 @@ class Sampling(C.Structure):
                 ("scale", C.c_void_p)]
 
 
+class Critic(C.Structure):
+    """mgx_critic (include/mgx.h): the value head of ``mgx_rollout_policy_critic_episodes`` (float64 device arrays ``w`` [P, n_mid],
+    ``b`` [P])."""
+    _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32), ("w", C.c_void_p), ("b", C.c_void_p)]
+
+
 POLICY_MAX_HIDDEN = 64     # MGX_POLICY_MAX_HIDDEN
 POLICY_LDS_BYTES = 32768   # MGX_POLICY_LDS_BYTES
 
@@ -252,6 +260,12 @@ SYMBOLS = {
     "mgx_rollout_policy_sample_episodes": (C.c_int, [C.c_void_p, C.POINTER(Policy), C.POINTER(Sampling), c_i32_p, C.c_int32, C.c_int32,
                                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                      C.POINTER(EpisodeStats), C.POINTER(EpisodeRows), C.c_void_p]),
+    "mgx_rollout_policy_critic_episodes": (C.c_int, [C.c_void_p, C.POINTER(Policy), C.POINTER(Sampling), C.POINTER(Critic), c_i32_p,
+                                                     C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(EpisodeStats),
+                                                     C.POINTER(EpisodeRows), C.c_void_p]),
+    "mgx_gae": (C.c_int, [C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double,
+                          C.c_void_p, C.c_void_p, C.c_void_p]),
     "mgx_metrics": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "mgx_reset_windows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -6,6 +6,7 @@
 #include "mgx_kernels.hpp"
 #include "mgx_episode_rows.hpp"
 #include "mgx_policy.hpp"
+#include "mgx_gae.hpp"
 
 #include <cstdarg>
 #include <cstdio>
@@ -2116,9 +2117,9 @@ static int policy_struct_refusal(const mgx_policy *policy, const char *fn)
 // ... and behind it, on a handle the launch accepts (`n_out`: the table's n_actions / the handle's action_dim, `out_name`: which).
 // The rows the policy reads are the rows the launch would write: the same refusals whether or not the caller takes them, so
 // `rows` NULL goes through prepare_episode_launch as a mgx_episode_rows without buffers.  `pad`: the multiple the staged sets round
-// n_out up to.
+// n_out up to.  `critic`: the sets are staged with a mgx_critic (policy_critic_set_doubles: 1 + n_mid doubles more each).
 static int policy_dims_refusal(mgx_handle *h, const mgx_policy *policy, int32_t n_out, int32_t pad, const char *out_name, const char *fn,
-                               EpisodePolicyLaunch &P)
+                               EpisodePolicyLaunch &P, bool critic = false)
 {
     const int32_t D = h->k.obs_dim;
     const int32_t row = 2 + 4 * ((h->flags & F_GENSET) != 0) + 2 * ((h->flags & F_BATTERY) != 0) + 4 * ((h->flags & F_GRID) != 0);
@@ -2128,7 +2129,8 @@ static int policy_dims_refusal(mgx_handle *h, const mgx_policy *policy, int32_t 
     if (policy->n_hidden > MGX_POLICY_MAX_HIDDEN)
         return fail(MGX_ERR_UNSUPPORTED, "%s: policy->n_hidden is %d, at most MGX_POLICY_MAX_HIDDEN = %d", fn, policy->n_hidden, MGX_POLICY_MAX_HIDDEN);
     const int32_t n_staged = (n_out + pad - 1) / pad * pad;      // (the discrete kernel takes its outputs in groups: policy_outputs)
-    const int64_t stride = (policy_set_doubles(D, policy->n_hidden, n_staged) + 1) & ~1;
+    const int64_t stride = ((critic ? policy_critic_set_doubles(D, policy->n_hidden, n_staged)       // (with a critic)
+                                    : policy_set_doubles(D, policy->n_hidden, n_staged)) + 1) & ~1;
     const int64_t bytes = (int64_t)policy->n_policies * stride * (int64_t)sizeof(double);
     if (bytes > MGX_POLICY_LDS_BYTES)
         return fail(MGX_ERR_UNSUPPORTED, "%s: %d parameter sets of %lld bytes each take %lld bytes of LDS, at most MGX_POLICY_LDS_BYTES = %d",
@@ -2168,14 +2170,31 @@ static int sampling_refusal(const mgx_sampling *sampling, const char *fn, Sample
     return MGX_OK;
 }
 
+// ... and of a mgx_critic with the three outputs of the critic call (never NULL here, its `critic` may be)
+struct CriticCall {
+    const mgx_critic *critic;
+    double *value_out, *final_value_out, *last_value_out;
+};
+static int critic_refusal(const CriticCall &cc, const char *fn, EpisodePolicyLaunch &P)
+{
+    const mgx_critic *critic = cc.critic;
+    if (!critic) return fail(MGX_ERR_INVALID, "%s: NULL argument", fn);
+    if (critic->struct_size != (int32_t)sizeof(mgx_critic))
+        return fail(MGX_ERR_INVALID, "%s: critic->struct_size is %d, sizeof(mgx_critic) is %d", fn, critic->struct_size, (int)sizeof(mgx_critic));
+    if (!critic->w || !critic->b) return fail(MGX_ERR_INVALID, "%s: NULL critic weights", fn);
+    P.cr = CriticArgs{critic->w, critic->b};
+    P.value_out = cc.value_out; P.final_value_out = cc.final_value_out; P.last_value_out = cc.last_value_out;
+    return MGX_OK;
+}
+
 // The closed-loop roll-out, greedy (no explore, no sampling: rollout_policy_episodes_kernel), exploring
-// (rollout_policy_explore_episodes_kernel) or sampling (`sample`: rollout_policy_sample_episodes_kernel, which needs a
-// mgx_sampling): every check, then one launch.
+// (rollout_policy_explore_episodes_kernel), sampling (`sample`: rollout_policy_sample_episodes_kernel, which needs a
+// mgx_sampling) or sampling with a critic (`cc`, with `sample`: rollout_policy_critic_episodes_kernel): every check, then one launch.
 static int rollout_policy_episodes_impl(mgx_handle *h, const mgx_policy *policy, const mgx_exploration *explore, bool sample,
                                         const mgx_sampling *sampling, const int32_t *table, int32_t n_actions, int32_t K, double *reward,
                                         uint8_t *done, double *soc_trace, uint32_t *status_trace, uint8_t *action_id_out,
                                         double *prob_out, const mgx_episode_stats *stats, const mgx_episode_rows *rows,
-                                        mgx_stream stream, const char *fn)
+                                        mgx_stream stream, const char *fn, const CriticCall *cc = nullptr)
 {
     if (!h || !policy || !table || (sample && !sampling)) return fail(MGX_ERR_INVALID, "%s: NULL argument", fn);
     if (int rc = policy_struct_refusal(policy, fn)) return rc;
@@ -2185,15 +2204,19 @@ static int rollout_policy_episodes_impl(mgx_handle *h, const mgx_policy *policy,
     if (int rc = exploration_refusal(h, explore, fn, P.ex)) return rc;
     if (sample)
         if (int rc = sampling_refusal(sampling, fn, P.sa)) return rc;
+    if (cc)
+        if (int rc = critic_refusal(*cc, fn, P)) return rc;
     if (int rc = prepare_episode_launch(h, K, reward, done, soc_trace, status_trace, stats, rows ? rows : &none, stream, fn,
                                         "mgx_rollout_discrete", "mgx_step_lists", table, n_actions, &tab, P.r)) return rc;
-    if (int rc = policy_dims_refusal(h, policy, tab.n_actions, 4, "n_actions", fn, P)) return rc;
+    if (int rc = policy_dims_refusal(h, policy, tab.n_actions, 4, "n_actions", fn, P, cc != nullptr)) return rc;
     P.r.e.tab = &tab; P.actions_out = action_id_out; P.prob_out = prob_out;
-    const bool launched = sample    ? launch_rollout_policy_sample_episodes_p0(P) || launch_rollout_policy_sample_episodes_p1(P)
+    const bool launched = cc        ? launch_rollout_policy_critic_episodes_p0(P) || launch_rollout_policy_critic_episodes_p1(P)
+                          : sample  ? launch_rollout_policy_sample_episodes_p0(P) || launch_rollout_policy_sample_episodes_p1(P)
                           : explore ? launch_rollout_policy_explore_episodes_p0(P) || launch_rollout_policy_explore_episodes_p1(P)
                                     : launch_rollout_policy_episodes_p0(P) || launch_rollout_policy_episodes_p1(P);
     return finish_episode_launch(h, P.r.e, launched,
-                                 sample    ? "rollout_policy_sample_episodes_kernel launch"
+                                 cc        ? "rollout_policy_critic_episodes_kernel launch"
+                                 : sample  ? "rollout_policy_sample_episodes_kernel launch"
                                  : explore ? "rollout_policy_explore_episodes_kernel launch" : "rollout_policy_episodes_kernel launch", fn);
 }
 
@@ -2227,6 +2250,19 @@ int mgx_rollout_policy_sample_episodes(mgx_handle *h, const mgx_policy *policy, 
     g_err[0] = 0;
     return rollout_policy_episodes_impl(h, policy, nullptr, true, sampling, table, n_actions, K, reward, done, soc_trace, status_trace,
                                         action_id_out, prob_out, stats, rows, stream, "mgx_rollout_policy_sample_episodes");
+}
+
+// the sampling call with a critic: a mgx_sampling and a mgx_critic are required
+int mgx_rollout_policy_critic_episodes(mgx_handle *h, const mgx_policy *policy, const mgx_sampling *sampling, const mgx_critic *critic,
+                                       const int32_t *table, int32_t n_actions, int32_t K, double *reward, uint8_t *done,
+                                       double *soc_trace, uint32_t *status_trace, uint8_t *action_id_out, double *prob_out,
+                                       double *value_out, double *final_value_out, double *last_value_out,
+                                       const mgx_episode_stats *stats, const mgx_episode_rows *rows, mgx_stream stream)
+{
+    g_err[0] = 0;
+    const CriticCall cc{critic, value_out, final_value_out, last_value_out};
+    return rollout_policy_episodes_impl(h, policy, nullptr, true, sampling, table, n_actions, K, reward, done, soc_trace, status_trace,
+                                        action_id_out, prob_out, stats, rows, stream, "mgx_rollout_policy_critic_episodes", &cc);
 }
 
 // The closed-loop continuous K-step, greedy (explore == NULL: step_k_policy_episodes_kernel) or exploring
@@ -2634,6 +2670,22 @@ int mgx_generate_columns(const mgx_gen *a, mgx_stream stream)
         return fail(MGX_ERR_DEVICE, "mgx_generate_columns: no HIP device available -- this engine has no CPU path");
     generate_columns_kernel<<<blocks_for(a->n_grids), BLOCK, 0, (hipStream_t)stream>>>(*a);
     return launched("generate_columns_kernel launch");
+}
+
+// generalised advantage estimation over [K, N] outputs (gae_kernel: mgx_gae.hip); handle-free, on the current device
+int mgx_gae(int64_t N, int32_t K, const double *reward, const uint8_t *done, const double *value, const double *final_value,
+            const double *last_value, double gamma, double lambda, double *advantage, double *returns, mgx_stream stream)
+{
+    g_err[0] = 0;
+    if (!reward || !done || !value || !last_value || !advantage) return fail(MGX_ERR_INVALID, "mgx_gae: NULL argument");
+    if (N <= 0 || K <= 0) return fail(MGX_ERR_INVALID, "mgx_gae: N = %lld, K = %d: both must be positive", (long long)N, K);
+    if (!(gamma >= 0.0 && gamma <= 1.0) || !(lambda >= 0.0 && lambda <= 1.0))
+        return fail(MGX_ERR_INVALID, "mgx_gae: gamma = %g, lambda = %g: both lie in [0, 1]", gamma, lambda);
+    int ndev = 0;
+    hipError_t e = hipGetDeviceCount(&ndev);
+    if (e != hipSuccess || ndev <= 0) return fail(MGX_ERR_DEVICE, "mgx_gae: no HIP device available -- this engine has no CPU path");
+    launch_gae(GaeArgs{N, K, reward, done, value, final_value, last_value, gamma, gamma * lambda, advantage, returns}, (hipStream_t)stream);
+    return launched("gae_kernel launch");
 }
 
 int mgx_normalise_series(mgx_handle *h, void *load_n, void *pv_n, void *grid_n, int32_t *clipped, mgx_stream stream)

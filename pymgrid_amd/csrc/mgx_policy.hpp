@@ -6,7 +6,8 @@
 // (mgx_rollout_policy_explore_episodes: mgx_policy_explore_episodes.hip, mgx_step_k_policy_explore_episodes:
 // mgx_step_policy_explore_episodes.hip) add the draw, the epsilon choice and the noise of mgx_exploration, each stated once below;
 // the sampling twin of the discrete launch (mgx_rollout_policy_sample_episodes: mgx_policy_sample_episodes.hip) the exp and the
-// softmax-sampling head of mgx_sampling.
+// softmax-sampling head of mgx_sampling; the critic twin of that one (mgx_rollout_policy_critic_episodes:
+// mgx_policy_critic_episodes.hip) the value head of mgx_critic, in functions of its own.
 // On top of mgx_episode_rows.hpp (the rows) and, through it, mgx_episode_loop.hpp (what all six episode loops share).
 #pragma once
 #include "mgx_episode_rows.hpp"
@@ -274,6 +275,132 @@ __device__ __forceinline__ int32_t policy_sample(double (&y)[NO], int32_t no, do
     return id;
 }
 
+// ---- the critic: the rule of mgx_critic (include/mgx.h), for rollout_policy_critic_episodes_kernel (mgx_policy_critic_episodes.hip).
+// New functions beside the ones above, which the greedy, exploring and sampling kernels keep to themselves. ----
+// mgx_critic as the kernel sees it, by value in its argument struct
+struct CriticArgs {
+    const double *w, *b;             // [P, n_mid], [P]
+};
+
+// One parameter set WITH a critic as it lies in LDS (doubles), for a row of D values -- the set of policy_set_doubles with the
+// critic's bias beside b2 and its weight in the record of the unit (or input) it multiplies, at a static offset:
+//   n_hidden > 0:  b2[0 .. n_out), b | per hidden unit u: W1[u, 0 .. D), b1[u], w[u], W2[0 .. n_out, u]
+//   n_hidden = 0:  b2[0 .. n_out), b | per input j: w[j], W2[0 .. n_out, j]
+// -- 1 + n_mid doubles more than the set without one.
+__host__ __device__ inline int32_t policy_critic_set_doubles(int32_t D, int32_t n_hidden, int32_t n_out)
+{
+    return policy_set_doubles(D, n_hidden, n_out) + 1 + (n_hidden > 0 ? n_hidden : D);
+}
+
+// stage_policy for that image (`pa.stride` is the stride of the sets with a critic); ends in the workgroup's barrier
+__device__ __forceinline__ void stage_policy_critic(const PolicyArgs &pa, const CriticArgs &cr, int32_t D, double *lds)
+{
+    const int32_t nh = pa.n_hidden, no = pa.n_out, nr = pa.n_real;
+    const int32_t rec = nh > 0 ? D + 2 + no : 1 + no;
+    const int32_t used = policy_critic_set_doubles(D, nh, no);
+    const int32_t total = pa.n_policies * pa.stride;
+    for (int32_t e = (int32_t)threadIdx.x; e < total; e += BLOCK_K) {
+        const int32_t ps = e / pa.stride, r = e - ps * pa.stride;
+        double v = 0.0;                                          // (a padding output; the padding double of an odd set)
+        if (r < no) {
+            if (r < nr) v = pa.b2[ps * nr + r];
+        } else if (r == no) {
+            v = cr.b[ps];
+        } else if (r < used) {
+            const int32_t q = r - no - 1;
+            const int32_t u = q / rec, c = q - u * rec;          // (the unit, or the input of a linear policy)
+            if (nh > 0) {
+                if (c < D) v = pa.w1[(ps * nh + u) * D + c];
+                else if (c == D) v = pa.b1[ps * nh + u];
+                else if (c == D + 1) v = cr.w[ps * nh + u];
+                else if (c - D - 2 < nr) v = pa.w2[(ps * nr + (c - D - 2)) * nh + u];
+            } else {
+                if (c == 0) v = cr.w[ps * D + u];
+                else if (c - 1 < nr) v = pa.w2[(ps * nr + (c - 1)) * D + u];
+            }
+        }
+        lds[e] = v;
+    }
+    __syncthreads();
+}
+
+// policy_outputs on a set with a critic: y[0 .. no) as there, operation by operation, and V of mgx_critic as one more running sum
+// beside them -- a hidden unit is folded into it while h is live, an input of a linear policy while its weights are walked.
+template <int D, int NO>
+__device__ __forceinline__ void policy_outputs_value(const double *w, int32_t nh, int32_t no, const double (&x)[D], double (&y)[NO], double &V)
+{
+    constexpr int G = NO < 4 ? NO : 4;
+    static_assert(NO % G == 0, "whole groups");
+#pragma unroll
+    for (int o = 0; o < NO; o++) y[o] = 0.0;
+#pragma unroll
+    for (int c = 0; c < NO; c += G)
+        if (c < no) {
+#pragma unroll
+            for (int o = c; o < c + G; o++) y[o] = w[o];
+        }
+    double val = w[no];
+    w += no + 1;
+    if (nh > 0) {
+        const int32_t rec = D + 2 + no;
+#pragma nounroll
+        for (int32_t u = 0; u < nh; u++) {
+            double h = w[D];
+#pragma unroll
+            for (int j = 0; j < D; j++) h = h + w[j] * x[j];
+            h = h > 0.0 ? h : 0.0;                                // (NaN and -0.0 become +0.0)
+            val = val + w[D + 1] * h;
+#pragma unroll
+            for (int c = 0; c < NO; c += G)
+                if (c < no) {
+#pragma unroll
+                    for (int o = c; o < c + G; o++) y[o] = y[o] + w[D + 2 + o] * h;
+                }
+            w += rec;
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < D; j++) {
+            val = val + w[0] * x[j];
+#pragma unroll
+            for (int c = 0; c < NO; c += G)
+                if (c < no) {
+#pragma unroll
+                    for (int o = c; o < c + G; o++) y[o] = y[o] + w[1 + o] * x[j];
+                }
+            w += no + 1;
+        }
+    }
+    V = val;
+}
+
+// ... and V alone, on the same set with the same operations: the final row of an episode, the row the last step returned
+template <int D>
+__device__ __forceinline__ double policy_value(const double *w, int32_t nh, int32_t no, const double (&x)[D])
+{
+    double val = w[no];
+    w += no + 1;
+    if (nh > 0) {
+        const int32_t rec = D + 2 + no;
+#pragma nounroll
+        for (int32_t u = 0; u < nh; u++) {
+            double h = w[D];
+#pragma unroll
+            for (int j = 0; j < D; j++) h = h + w[j] * x[j];
+            h = h > 0.0 ? h : 0.0;
+            val = val + w[D + 1] * h;
+            w += rec;
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < D; j++) {
+            val = val + w[0] * x[j];
+            w += no + 1;
+        }
+    }
+    return val;
+}
+
 // columns of an H = 0 row of layout F
 template <int F>
 constexpr int policy_row_dim() { return 2 + 4 * ((F & F_GENSET) != 0) + 2 * ((F & F_BATTERY) != 0) + 4 * ((F & F_GRID) != 0); }
@@ -367,20 +494,31 @@ struct RolloutPolicySampleArgs {
     double *prob_out;                // [K, N] or NULL
 };
 
-// ---- host side: what mgx_abi.hip hands the slices of the five translation units ----
+// ... and of the critic kernel: the sampling kernel's struct first, the critic and its three outputs behind it
+struct RolloutPolicyCriticArgs {
+    RolloutPolicySampleArgs s;
+    CriticArgs cr;
+    double *value_out, *final_value_out;   // [K, N] or NULL
+    double *last_value_out;                // [N] or NULL
+};
+
+// ---- host side: what mgx_abi.hip hands the slices of the six translation units ----
 struct EpisodePolicyLaunch {
     EpisodeRowsLaunch r;             // as for the kernels with rows (obs / final_obs may both be NULL here)
     PolicyArgs pol;
     unsigned lds_bytes;              // n_policies * stride doubles: the dynamic LDS of the launch
     void *actions_out;               // the ids (uint8 [K, N]) or controls (double [K, N, A]) the policy chose, or NULL
     ExploreArgs ex;                  // the exploring kernels alone read it
-    SampleArgs sa;                   // ... the sampling kernel alone these two
+    SampleArgs sa;                   // ... the sampling kernel and the critic kernel these two,
     double *prob_out;
+    CriticArgs cr;                   // ... the critic kernel alone the rest (lds_bytes / pol.stride then hold policy_critic_set_doubles)
+    double *value_out, *final_value_out, *last_value_out;
 };
 bool launch_rollout_policy_episodes_p0(const EpisodePolicyLaunch &L); bool launch_rollout_policy_episodes_p1(const EpisodePolicyLaunch &L);
 bool launch_step_k_policy_episodes_p0(const EpisodePolicyLaunch &L); bool launch_step_k_policy_episodes_p1(const EpisodePolicyLaunch &L);
 bool launch_rollout_policy_explore_episodes_p0(const EpisodePolicyLaunch &L); bool launch_rollout_policy_explore_episodes_p1(const EpisodePolicyLaunch &L);
 bool launch_step_k_policy_explore_episodes_p0(const EpisodePolicyLaunch &L); bool launch_step_k_policy_explore_episodes_p1(const EpisodePolicyLaunch &L);
 bool launch_rollout_policy_sample_episodes_p0(const EpisodePolicyLaunch &L); bool launch_rollout_policy_sample_episodes_p1(const EpisodePolicyLaunch &L);
+bool launch_rollout_policy_critic_episodes_p0(const EpisodePolicyLaunch &L); bool launch_rollout_policy_critic_episodes_p1(const EpisodePolicyLaunch &L);
 
 }  // namespace mgx

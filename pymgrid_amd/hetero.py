@@ -16,7 +16,7 @@ import torch
 
 from . import _lib
 from .batch import MicrogridBatch
-from .engine import _raw_stream
+from .engine import CRITIC_NEEDS_SAMPLING, _raw_stream
 from .envs import BatchedMicrogridEnv, DiscreteBatchedMicrogridEnv, ObsViews, _as_ids
 from .scenario import bucket_by_layout
 
@@ -804,7 +804,8 @@ class PerGridWindowEnv:
             raise RuntimeError(f"{kind}_policy() before reset()")
 
     def rollout_policy(self, policy, K, reward=True, done=False, soc_trace=False, status_trace=False, actions=False,
-                       observations=False, final_observations=False, out=None, exploration=None, sampling=None, probs=False):
+                       observations=False, final_observations=False, out=None, exploration=None, sampling=None, probs=False,
+                       critic=None, values=False):
         """``rollout`` with the loop CLOSED inside the launch (``mgx_rollout_policy_episodes``; ``discrete=True``): the id of every step
         is ``policy`` (``pymgrid_amd.policy.MLPPolicy``, ``head="discrete"``, one output per priority list) applied to the
         observation the grid's last step -- or reset, or restart inside the launch -- returned, in the env's ``obs_dtype``.  K steps
@@ -817,15 +818,27 @@ class PerGridWindowEnv:
         (``pymgrid_amd.policy.Sampling``; not together with ``exploration``): the ids are drawn from ``softmax(y / temperature)`` inside
         the launch (``mgx_rollout_policy_sample_episodes``), ``probs=True`` also returns the probability of every id taken (float64
         ``[K, N]``; its ``torch.log`` is the log-probability the on-policy methods need); the stepped twin is
-        ``ids, prob = policy.act(obs, sampling, counter=env.current_step, return_prob=True)``."""
+        ``ids, prob = policy.act(obs, sampling, counter=env.current_step, return_prob=True)``.  ``critic``
+        (``pymgrid_amd.policy.ValueHead``; needs ``sampling`` -- ``Sampling(seed, temperature=0)`` is the greedy head): a value head on
+        the policy's trunk, evaluated inside the same launch (``mgx_rollout_policy_critic_episodes``) without changing anything else;
+        ``values=True`` returns ``values`` ``[K, N]`` (V of the observation every id was chosen on), ``final_values`` ``[K, N]`` (V of
+        ``final_obs[k]``, written where ``done[k]`` only: zeros elsewhere when allocated, yours through ``out=``) and ``last_value``
+        ``[N]`` (V of ``obs[-1]``) -- with ``reward`` and ``done`` what ``pymgrid_amd.gae`` turns into advantages and returns."""
         env = self.env
+        if critic is not None and sampling is None:
+            raise ValueError(CRITIC_NEEDS_SAMPLING)
+        if values and critic is None:
+            raise ValueError("values= goes with critic=: a ValueHead on the policy's trunk")
         self._check_fused("rollout", True, policy=True)
         self._check_policy("rollout", policy, "discrete", int(np.asarray(env._table).shape[0]), "the env's priority-list table")
         self._check_exploration(exploration)
         self._check_exploration(sampling, "sampling")
+        if critic is not None:
+            critic.check(policy)
         return self._launch_fused(lambda **kw: env.engine.rollout_policy_episodes(policy, env._table, int(K), **kw), observations,
                                   final_observations, reward=reward, done=done, soc_trace=soc_trace, status_trace=status_trace,
-                                  actions=actions, out=out, exploration=exploration, sampling=sampling, probs=probs)
+                                  actions=actions, out=out, exploration=exploration, sampling=sampling, probs=probs, critic=critic,
+                                  values=values)
 
     def step_k_policy(self, policy, K, reward=True, done=False, soc_trace=False, status_trace=False, actions=False,
                       observations=False, final_observations=False, out=None, exploration=None, sampling=None):

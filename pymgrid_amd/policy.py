@@ -382,3 +382,145 @@ class MLPPolicy:
         st.n_policies, st.n_in, st.n_hidden, st.n_out = me.n_policies, me.n_in, me.n_hidden, me.n_out
         st.w1, st.b1, st.w2, st.b2, st.policy_index = ptr(me.W1), ptr(me.b1), ptr(me.W2), ptr(me.b2), ptr(me.policy_index)
         return st, (me, spare)
+
+
+class ValueHead:
+    """A critic beside a discrete ``MLPPolicy`` (``mgx_critic``, include/mgx.h): one more output row on the policy's trunk,
+    ``V(x) = b + sum over j in order of w[j] * v[j]`` with ``v`` the policy's hidden vector after its ReLU, or ``x`` for a linear
+    policy -- a separate multiply and add each.  ``w`` float64 ``[n_mid]`` or ``[P, n_mid]`` (``n_mid`` = the policy's ``n_hidden``,
+    or its ``n_in`` without a hidden layer), ``b`` a float64 scalar or ``[P]``; the parameter set of a grid is the policy's own
+    (``policy_index``).  The sampling launch evaluates it inside the kernel (``critic=`` of ``rollout_policy``); ``value`` is the same
+    rule on the host.  Validated as the C call does."""
+
+    def __init__(self, w, b):
+        self.w = _f64("w", w, 2)
+        if self.w is None or b is None:
+            raise ValueError("w and b are required")
+        tb = b if torch.is_tensor(b) else torch.as_tensor(np.asarray(b))
+        if tb.dtype != torch.float64:
+            raise ValueError(f"b must be float64 (the critic is evaluated in float64 on host and device), not {tb.dtype}")
+        if tb.dim() > 1:
+            raise ValueError(f"b must be a scalar or a vector [P]; it has shape {tuple(tb.shape)}")
+        self.b = tb.reshape(-1).contiguous()
+        self.n_policies, self.n_mid = int(self.w.shape[0]), int(self.w.shape[1])
+        if self.n_policies < 1 or self.n_mid < 1:
+            raise ValueError(f"w {tuple(self.w.shape)}: an empty critic")
+        if self.b.shape[0] != self.n_policies:
+            raise ValueError(f"b {tuple(self.b.shape)} does not fit w {tuple(self.w.shape)}: b [P]")
+        if self.w.device != self.b.device:
+            raise ValueError(f"the parameters lie on different devices: {sorted(map(str, (self.w.device, self.b.device)))}")
+
+    def check(self, policy):
+        """Whether the head fits ``policy``: a discrete ``MLPPolicy`` with as many parameter sets and ``n_mid`` trunk outputs."""
+        if not isinstance(policy, MLPPolicy) or policy.head != "discrete":
+            raise ValueError("a ValueHead goes with a discrete MLPPolicy (the sampling launch)")
+        n_mid = policy.n_hidden or policy.n_in
+        if self.n_mid != n_mid or self.n_policies != policy.n_policies:
+            raise ValueError(f"w {tuple(self.w.shape)} does not fit the policy: [P, n_mid] = [{policy.n_policies}, {n_mid}]")
+
+    def lds_bytes(self, policy):
+        """Bytes of the parameter sets as the critic launch stages them (include/mgx.h, ``mgx_rollout_policy_critic_episodes``)."""
+        m = (policy.n_out + 3) // 4 * 4
+        per_set = m + 1 + (policy.n_hidden * (policy.n_in + 2 + m) if policy.n_hidden else policy.n_in * (m + 1))
+        return policy.n_policies * ((per_set + 1) // 2 * 2) * 8
+
+    def value(self, policy, obs):
+        """``V`` (float64 [N]) for observation rows ``obs`` [N, n_in] (float32 rows are widened): the host statement of the rule,
+        what the critic launch writes bit for bit -- row n of ``obs`` is grid n."""
+        self.check(policy)
+        if not torch.is_tensor(obs):
+            obs = torch.as_tensor(np.asarray(obs))
+        if obs.dim() != 2 or obs.shape[1] != policy.n_in or obs.dtype not in (torch.float32, torch.float64):
+            raise ValueError(f"obs must be float32 or float64 rows [N, {policy.n_in}], not {obs.dtype} {tuple(obs.shape)}")
+        me = policy.to(obs.device)
+        x = obs.to(torch.float64)
+        idx = me._sets(x.shape[0], x.device)
+        if me.n_hidden:
+            h = MLPPolicy._layer(me.W1, me.b1, idx, x)
+            x = torch.where(h > 0, h, torch.zeros_like(h))
+        return MLPPolicy._layer(self.w.to(x.device).unsqueeze(1), self.b.to(x.device).unsqueeze(1), idx, x)[:, 0]
+
+    def c_struct(self, device, n_grids):
+        """``(mgx_critic, keep-alive)`` with the parameters on ``device``."""
+        w, b = self.w.to(device), self.b.to(device)
+        st = _lib.Critic()
+        st.struct_size = C.sizeof(_lib.Critic)
+        st.w, st.b = w.data_ptr(), b.data_ptr()
+        return st, (w, b)
+
+
+def _gae_args(reward, done, value, last_value, final_value, gamma, lam):
+    """The checks ``gae`` and ``gae_host`` share; ``done`` comes back as it was given (bool or uint8)."""
+    gamma, lam = float(gamma), float(lam)
+    if not 0.0 <= gamma <= 1.0 or not 0.0 <= lam <= 1.0:
+        raise ValueError(f"gamma = {gamma}, lam = {lam}: both lie in [0, 1]")
+    for name, t in (("reward", reward), ("value", value), ("last_value", last_value), ("final_value", final_value)):
+        if t is None and name == "final_value":
+            continue
+        if not torch.is_tensor(t) or t.dtype != torch.float64:
+            raise ValueError(f"{name} must be a float64 tensor, not {getattr(t, 'dtype', type(t))}")
+    if not torch.is_tensor(done) or done.dtype not in (torch.bool, torch.uint8):
+        raise ValueError(f"done must be a bool or uint8 tensor, not {getattr(done, 'dtype', type(done))}")
+    if reward.dim() != 2 or reward.shape[0] < 1 or reward.shape[1] < 1:
+        raise ValueError(f"reward must be [K, N] with K, N >= 1, not {tuple(reward.shape)}")
+    K, N = reward.shape
+    for name, t, shape in (("done", done, (K, N)), ("value", value, (K, N)), ("last_value", last_value, (N,)),
+                           ("final_value", final_value, (K, N))):
+        if t is not None and tuple(t.shape) != shape:
+            raise ValueError(f"{name} must have shape {list(shape)}, not {list(t.shape)}")
+        if t is not None and t.device != reward.device:
+            raise ValueError(f"{name} lies on {t.device}, reward on {reward.device}")
+    return int(K), int(N), gamma, lam
+
+
+def gae_host(reward, done, value, last_value, final_value=None, gamma=0.99, lam=0.95):
+    """The rule of ``mgx_gae`` (include/mgx.h) in torch, on any device, operation by operation: ``{"advantages", "returns"}``
+    (float64 [K, N]).  ``reward`` / ``value`` / ``final_value`` [K, N], ``done`` bool or uint8 [K, N], ``last_value`` [N]; where
+    ``done[k]`` the step bootstraps from ``final_value[k]`` (``None``: 0.0) and the advantage behind it is not carried across."""
+    K, N, gamma, lam = _gae_args(reward, done, value, last_value, final_value, gamma, lam)
+    c = gamma * lam
+    adv, ret = torch.empty_like(reward), torch.empty_like(reward)
+    nxt, carry = last_value, torch.zeros_like(last_value)
+    for k in range(K - 1, -1, -1):
+        d = done[k] != 0
+        nv = torch.where(d, final_value[k] if final_value is not None else torch.zeros_like(nxt), nxt)
+        delta = (reward[k] + gamma * nv) - value[k]
+        A = torch.where(d, delta, delta + c * carry)
+        adv[k], ret[k] = A, A + value[k]
+        carry, nxt = A, value[k]
+    return {"advantages": adv, "returns": ret}
+
+
+def gae(reward, done, value, last_value, final_value=None, gamma=0.99, lam=0.95, out=None):
+    """Generalised advantage estimation over the ``[K, N]`` outputs of a critic launch in ONE kernel (``mgx_gae``; one lane per
+    grid, backwards over k): ``{"advantages", "returns"}``, float64 ``[K, N]`` -- ``gae_host``'s values bit for bit.  Device
+    tensors: ``done`` bool or uint8, the rest contiguous float64; ``final_value`` (``out["final_values"]`` of the launch) is read
+    only where ``done``, ``None`` bootstraps 0.0 there.  ``out``: a dict with your own ``advantages`` and / or ``returns`` (they
+    must not overlap the inputs); ``out={"returns": None}`` skips the returns."""
+    K, N, gamma, lam = _gae_args(reward, done, value, last_value, final_value, gamma, lam)
+    dev = reward.device
+    for name, t in (("reward", reward), ("done", done), ("value", value), ("last_value", last_value), ("final_value", final_value)):
+        if t is not None and not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
+    if dev.type != "cuda":
+        raise ValueError(f"gae runs on the GPU (mgx_gae); the tensors lie on {dev} -- gae_host states the same rule anywhere")
+    out = out or {}
+    unknown = set(out) - {"advantages", "returns"}
+    if unknown:
+        raise ValueError(f"unknown outputs {sorted(unknown)}")
+    res = {}
+    for name in ("advantages", "returns"):
+        if name in out and out[name] is None and name == "returns":
+            continue
+        t = out.get(name)
+        if t is None:
+            t = torch.empty((K, N), dtype=torch.float64, device=dev)
+        elif not torch.is_tensor(t) or t.dtype != torch.float64 or t.device != dev or not t.is_contiguous() or tuple(t.shape) != (K, N):
+            raise ValueError(f"out[{name!r}] must be a contiguous float64 tensor {[K, N]} on {dev}")
+        res[name] = t
+    d8 = done.view(torch.uint8) if done.dtype == torch.bool else done
+    ptr = lambda t: None if t is None else t.data_ptr()     # noqa: E731
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().mgx_gae(N, K, ptr(reward), ptr(d8), ptr(value), ptr(final_value), ptr(last_value), gamma, lam,
+                                      ptr(res["advantages"]), ptr(res.get("returns")), torch.cuda.current_stream(dev).cuda_stream))
+    return res
