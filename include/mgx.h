@@ -801,6 +801,88 @@ int mgx_rollout_policy_critic_episodes(mgx_handle *h, const mgx_policy *policy, 
 int mgx_gae(int64_t N, int32_t K, const double *reward, const uint8_t *done, const double *value, const double *final_value,
             const double *last_value, double gamma, double lambda, double *advantage, double *returns, mgx_stream stream);
 
+/* A GAUSSIAN policy head inside the closed-loop continuous launch: every control is drawn from N(y[o], s[o]^2) -- a true normal
+ * draw, not the lattice of mgx_exploration -- and the launch returns the pre-clip action and its exact log-density, what the
+ * on-policy methods need on the continuous head.  As exp in mgx_sampling, log, sine and cosine are PART OF THE RULE: fixed sequences
+ * of plain IEEE fp64 operations (every multiply and add separate), no call into a math library, so fused == stepped stays bit for
+ * bit.  The division is the correctly rounded IEEE one on both sides.  The SQUARE ROOT is a fixed sequence too, S below: with the
+ * library roots the device/host parity test passed on L and on the quarter turn and failed on the pair.  THE RULE (stated here once):
+ *
+ * L(a), for a positive NORMAL double a (within 4 ulp of log(a); L(1.0) == 0.0 exactly):
+ *     e = the unbiased exponent of a, m = its mantissa as a double in [1, 2)     (both out of the bits of a)
+ *     if m > 1.4142135623730951:  m = m * 0.5,  e = e + 1
+ *     t = (m - 1.0) / (m + 1.0);  w = t * t
+ *     p = c[10];  for n = 9 .. 0:  p = p * w + c[n]        c[n]: the double nearest 2 / (2n + 1) --
+ *         c[0 .. 10] = 2.0, 0.6666666666666666, 0.4, 0.2857142857142857, 0.2222222222222222, 0.18181818181818182,
+ *                      0.15384615384615385, 0.13333333333333333, 0.11764705882352941, 0.10526315789473684, 0.09523809523809523
+ *     L = e * 6.93147180369123816490e-01 + (e * 1.90821492927058770002e-10 + t * p)      (e as a double; the ln 2 constants of E)
+ *
+ * Quarter turn: (sin, cos) of the angle f * pi / 2, for f an exact multiple of 2^-52 in [0, 1) (within 2^-51 of sin and cos):
+ *     hi = f > 0.5;  g = hi ? 1.0 - f : f        (exact)
+ *     x = g * 1.5707963267948966;  w = x * x
+ *     q = a[6];  for n = 5 .. 0:  q = q * w + a[n];   s = x * (q * w + 1.0)       a[n]: the double nearest (-1)^(n+1) / (2n + 3)! --
+ *         a[0 .. 6] = -0.16666666666666666, 0.008333333333333333, -0.0001984126984126984, 2.7557319223985893e-06,
+ *                     -2.505210838544172e-08, 1.6059043836821613e-10, -7.647163731819816e-13
+ *     c = b[7];  for n = 6 .. 0:  c = c * w + b[n];   c = c * w + 1.0             b[n]: the double nearest (-1)^(n+1) / (2n + 2)! --
+ *         b[0 .. 7] = -0.5, 0.041666666666666664, -0.001388888888888889, 2.48015873015873e-05, -2.755731922398589e-07,
+ *                     2.08767569878681e-09, -1.1470745597729725e-11, 4.779477332387385e-14
+ *     (sin, cos) = hi ? (c, s) : (s, c)
+ *
+ * S(v), for a finite double v (within 1 ulp of sqrt(v) for v > 0; multiplies and adds only):
+ *     if !(v > 0):  S = 0.0                       (v = -2.0 * L(1.0) is -0.0)
+ *     y = the double whose bits are 0x5FE6EB50C7B537A9 - (bits(v) >> 1)          (1 / sqrt(v) within 3.5 %)
+ *     h = 0.5 * v;  four times:  y = y * (1.5 - (h * y) * y)
+ *     r = v * y;  S = r + (0.5 * y) * (v - r * r)
+ *
+ * Normal pair number p of grid i at step counter t (i, t, the draw and U(a, b) as mgx_exploration states them): ONE draw,
+ * r[0 .. 3] = the draw of (seed, i, t) with number j = 8 + p (numbers 0 .. 3 are the exploring head's, 1 the softmax head's):
+ *     u1 = 1.0 - U(r[0], r[1])                   (exact, in (0, 1])
+ *     R  = S(-2.0 * L(u1))                       (at most 8.58)
+ *     a64 = (uint64)r[2] << 32 | r[3];  q = a64 >> 62;  f = (double)((a64 >> 10) & (2^52 - 1)) * 2^-52
+ *     (s, c) = the quarter turn of f, turned by the quadrant:
+ *         q = 0: (sn, cs) = (s, c);   q = 1: (c, -s);   q = 2: (-s, -c);   q = 3: (-c, s)
+ *     z[2p] = R * cs;  z[2p + 1] = R * sn
+ * Pair 0 serves action columns 0 and 1, pair 1 columns 2 and 3; a pair whose second column does not exist (mgx_action_dim 1 or 3)
+ * drops its sine.
+ *
+ * Head of grid i, on y[0 .. n_out) of mgx_policy:
+ *     s[o] = scale ? sigma[o] * scale[i] : sigma[o];   column o is LIVE if s[o] > 0   (false for a NaN)
+ *     raw[o] = live ? y[o] + s[o] * z[o] : y[o]        (a separate multiply and add)
+ *     u[o] = !(raw[o] > 0) ? 0.0 : (raw[o] > 1 ? 1.0 : raw[o])                         (the clip of mgx_policy, unchanged)
+ * The draw of a pair without a live column is not made.  With every sigma == 0 (or scale[i] == 0) the controls are those of
+ * mgx_step_k_policy_episodes, bit for bit.  A scale[i] must leave a live s[o] a normal finite number: L reads exponent and mantissa.
+ *
+ * Log-probability, of the PRE-CLIP action raw (as PPO implementations take it where the environment clips):
+ *     C = 0.0;  for each live o in order:  C = C + (L(s[o]) + 0.9189385332046727)      (log(2 pi) / 2; once per grid and launch)
+ *     Q = 0.0;  for each live o in order:  Q = Q + z[o] * z[o]
+ *     logp = (-0.5 * Q) - C
+ * NaN logits give raw = NaN, the control 0.0 and a finite logp (it depends on z and s alone). */
+typedef struct mgx_gaussian {
+    int32_t struct_size;      /* = sizeof(mgx_gaussian) */
+    int32_t reserved;
+    uint64_t seed;            /* Philox key */
+    double sigma[4];          /* one per action column: 0 (the column stays greedy) or a positive, finite, normal number */
+    const double *scale;      /* device [N] or NULL (= 1.0 for every grid): multiplies every sigma of grid i */
+} mgx_gaussian;
+
+/* mgx_step_k_policy_episodes with the Gaussian head of mgx_gaussian, and with `critic` the value head of mgx_critic: one launch of
+ * step_k_policy_gaussian_episodes_kernel.  actions_out: double [K, N, A], the clipped controls taken; raw_actions_out: double
+ * [K, N, A], the pre-clip actions raw; logp_out: double [K, N], their log-probability; each may be NULL.  critic == NULL: no values
+ * -- value_out, final_value_out and last_value_out must then be NULL.  With a critic the three follow
+ * mgx_rollout_policy_critic_episodes word for word (each may be NULL; untouched entries of final_value_out keep the caller's
+ * bytes), and every other result is bit for bit what the call without a critic leaves.  Refusals as
+ * mgx_step_k_policy_explore_episodes; on top MGX_ERR_INVALID for a NULL gaussian, gaussian->struct_size != sizeof(mgx_gaussian), a
+ * sigma[o] (all four are checked) that is negative, NaN, infinite or positive and subnormal, a value output given without a
+ * critic, and a mgx_critic as mgx_rollout_policy_critic_episodes refuses it; MGX_ERR_UNSUPPORTED where the staged sets -- with a
+ * critic n_policies * 8 * even(m + 1 + (n_hidden ? n_hidden * (n_in + 2 + m) : n_in * (m + 1))) bytes, m = n_out -- pass
+ * MGX_POLICY_LDS_BYTES.  What needs no handle (the structs, the value outputs) is checked first.  Nothing is launched when the call
+ * is refused.  An ADDITION to ABI 9 that leaves MGX_ABI_MINOR at 3: consumers find it by name (dlsym). */
+int mgx_step_k_policy_gaussian_episodes(mgx_handle *h, const mgx_policy *policy, const mgx_gaussian *gaussian,
+                                        const mgx_critic *critic, int32_t K, double *reward, uint8_t *done, double *soc_trace,
+                                        uint32_t *status_trace, double *actions_out, double *raw_actions_out, double *logp_out,
+                                        double *value_out, double *final_value_out, double *last_value_out,
+                                        const mgx_episode_stats *stats, const mgx_episode_rows *rows, mgx_stream stream);
+
 /* raise_errors=True (BaseMicrogridModule.__init__, base_module.py:40; as_source / as_sink, :213-224,265-270; _raise_error,
  * :79-93): the reference refuses a request a module cannot meet with a ValueError instead of clipping it.  mgx_step always
  * clips; mgx_check_step is its DRY RUN -- the same arithmetic on a register copy of the state, nothing stored, the counter

@@ -28,6 +28,7 @@ UNITS = (
     ("mgx_step_policy_explore_episodes.hip", "MGX_EPISODE_PART", 2),    # ... and its continuous twin,
     ("mgx_policy_sample_episodes.hip", "MGX_EPISODE_PART", 2),          # ... the closed-loop roll-out with a softmax-sampling head
     ("mgx_policy_critic_episodes.hip", "MGX_EPISODE_PART", 2),          # ... and that one with a critic beside the actor,
+    ("mgx_step_policy_gaussian_episodes.hip", "MGX_EPISODE_PART", 2),   # ... the continuous closed loop with a Gaussian head (+ critic),
     ("mgx_gae.hip", None, 1),                                           # the advantages of what such launches return (mgx_gae)
 )
 # everything a built library is stamped with (source_hash): a file missing here would leave a stale libmgx.so looking current
@@ -173,6 +174,12 @@ class Critic(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32), ("w", C.c_void_p), ("b", C.c_void_p)]
 
 
+class Gaussian(C.Structure):
+    """mgx_gaussian (include/mgx.h): the Gaussian head of ``mgx_step_k_policy_gaussian_episodes`` (``scale`` float64 device [N] or NULL)."""
+    _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32), ("seed", C.c_uint64), ("sigma", C.c_double * 4),
+                ("scale", C.c_void_p)]
+
+
 POLICY_MAX_HIDDEN = 64     # MGX_POLICY_MAX_HIDDEN
 POLICY_LDS_BYTES = 32768   # MGX_POLICY_LDS_BYTES
 
@@ -264,6 +271,8 @@ SYMBOLS = {
                                                      C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(EpisodeStats),
                                                      C.POINTER(EpisodeRows), C.c_void_p]),
+    "mgx_step_k_policy_gaussian_episodes": (C.c_int, [C.c_void_p, C.POINTER(Policy), C.POINTER(Gaussian), C.POINTER(Critic), C.c_int32]
+                                            + [C.c_void_p] * 10 + [C.POINTER(EpisodeStats), C.POINTER(EpisodeRows), C.c_void_p]),
     "mgx_gae": (C.c_int, [C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double,
                           C.c_void_p, C.c_void_p, C.c_void_p]),
     "mgx_metrics": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),

@@ -2265,26 +2265,65 @@ int mgx_rollout_policy_critic_episodes(mgx_handle *h, const mgx_policy *policy, 
                                         action_id_out, prob_out, stats, rows, stream, "mgx_rollout_policy_critic_episodes", &cc);
 }
 
-// The closed-loop continuous K-step, greedy (explore == NULL: step_k_policy_episodes_kernel) or exploring
-// (step_k_policy_explore_episodes_kernel): every check, then one launch.
+// ... and of a mgx_gaussian with the two streams of the Gaussian call and its critic call (never NULL here, its `gaussian` and the
+// `critic` of its `cc` may be): what needs no handle -- all four sigmas are checked, whatever the handle's action_dim
+struct GaussianCall {
+    const mgx_gaussian *gaussian;
+    const CriticCall *cc;
+    double *raw_out, *logp_out;
+};
+static int gaussian_refusal(const GaussianCall &gc, const char *fn, EpisodePolicyLaunch &P)
+{
+    const mgx_gaussian *gs = gc.gaussian;
+    if (gs->struct_size != (int32_t)sizeof(mgx_gaussian))
+        return fail(MGX_ERR_INVALID, "%s: gaussian->struct_size is %d, sizeof(mgx_gaussian) is %d", fn, gs->struct_size, (int)sizeof(mgx_gaussian));
+    P.gs = GaussianArgs{gs->seed, {0.0, 0.0, 0.0, 0.0}, gs->scale};
+    for (int32_t o = 0; o < 4; o++) {
+        const double v = gs->sigma[o];
+        if (!(v == 0.0 || (v >= 2.2250738585072014e-308 && v < __builtin_inf())))      // (DBL_MIN: L needs a normal number)
+            return fail(MGX_ERR_INVALID, "%s: gaussian->sigma[%d] is %g: 0 or a positive, finite, normal number", fn, o, v);
+        P.gs.sigma[o] = v == 0.0 ? 0.0 : v;                                              // (-0.0 becomes +0.0)
+    }
+    P.raw_out = gc.raw_out; P.logp_out = gc.logp_out;
+    const CriticCall &cc = *gc.cc;
+    if (!cc.critic) {
+        if (cc.value_out || cc.final_value_out || cc.last_value_out)
+            return fail(MGX_ERR_INVALID, "%s: a value output without a critic", fn);
+        return MGX_OK;
+    }
+    P.critic = true;
+    return critic_refusal(cc, fn, P);
+}
+
+// The closed-loop continuous K-step, greedy (explore == NULL: step_k_policy_episodes_kernel), exploring
+// (step_k_policy_explore_episodes_kernel) or Gaussian (`gc`: step_k_policy_gaussian_episodes_kernel, which needs a mgx_gaussian and
+// takes a critic): every check, then one launch.
 static int step_k_policy_episodes_impl(mgx_handle *h, const mgx_policy *policy, const mgx_exploration *explore, int32_t K, double *reward,
                                        uint8_t *done, double *soc_trace, uint32_t *status_trace, double *actions_out,
-                                       const mgx_episode_stats *stats, const mgx_episode_rows *rows, mgx_stream stream, const char *fn)
+                                       const mgx_episode_stats *stats, const mgx_episode_rows *rows, mgx_stream stream, const char *fn,
+                                       const GaussianCall *gc = nullptr)
 {
-    if (!h || !policy) return fail(MGX_ERR_INVALID, "%s: NULL argument", fn);
+    if ((!h && !gc) || !policy || (gc && !gc->gaussian)) return fail(MGX_ERR_INVALID, "%s: NULL argument", fn);
     if (int rc = policy_struct_refusal(policy, fn)) return rc;
     const mgx_episode_rows none{(int32_t)sizeof(mgx_episode_rows), 0, nullptr, nullptr};
     EpisodePolicyLaunch P{};
+    if (gc) {                                                    // (what needs no handle first)
+        if (int rc = gaussian_refusal(*gc, fn, P)) return rc;
+        if (!h) return fail(MGX_ERR_INVALID, "%s: NULL argument", fn);
+    }
     if (int rc = exploration_refusal(h, explore, fn, P.ex)) return rc;
     if (int rc = prepare_episode_launch(h, K, reward, done, soc_trace, status_trace, stats, rows ? rows : &none, stream, fn, "mgx_step_k",
                                         "mgx_step", nullptr, 0, nullptr, P.r)) return rc;
     if (h->k.act_f32)
         return fail(MGX_ERR_UNSUPPORTED, "%s: the handle's action format is float32 (mgx_set_action_format); the policy's controls are doubles", fn);
-    if (int rc = policy_dims_refusal(h, policy, h->action_dim, 1, "mgx_action_dim", fn, P)) return rc;
+    if (int rc = policy_dims_refusal(h, policy, h->action_dim, 1, "mgx_action_dim", fn, P, P.critic)) return rc;
     P.actions_out = actions_out;
-    const bool launched = explore ? launch_step_k_policy_explore_episodes_p0(P) || launch_step_k_policy_explore_episodes_p1(P)
-                                  : launch_step_k_policy_episodes_p0(P) || launch_step_k_policy_episodes_p1(P);
-    return finish_episode_launch(h, P.r.e, launched, explore ? "step_k_policy_explore_episodes_kernel launch" : "step_k_policy_episodes_kernel launch", fn);
+    const bool launched = gc        ? launch_step_k_policy_gaussian_episodes_p0(P) || launch_step_k_policy_gaussian_episodes_p1(P)
+                          : explore ? launch_step_k_policy_explore_episodes_p0(P) || launch_step_k_policy_explore_episodes_p1(P)
+                                    : launch_step_k_policy_episodes_p0(P) || launch_step_k_policy_episodes_p1(P);
+    return finish_episode_launch(h, P.r.e, launched,
+                                 gc        ? "step_k_policy_gaussian_episodes_kernel launch"
+                                 : explore ? "step_k_policy_explore_episodes_kernel launch" : "step_k_policy_episodes_kernel launch", fn);
 }
 
 int mgx_step_k_policy_episodes(mgx_handle *h, const mgx_policy *policy, int32_t K, double *reward, uint8_t *done,
@@ -2303,6 +2342,20 @@ int mgx_step_k_policy_explore_episodes(mgx_handle *h, const mgx_policy *policy, 
     g_err[0] = 0;
     return step_k_policy_episodes_impl(h, policy, explore, K, reward, done, soc_trace, status_trace, actions_out, stats, rows, stream,
                                        explore ? "mgx_step_k_policy_explore_episodes" : "mgx_step_k_policy_episodes");
+}
+
+// the Gaussian call: a mgx_gaussian is required, the critic with its three outputs is not
+int mgx_step_k_policy_gaussian_episodes(mgx_handle *h, const mgx_policy *policy, const mgx_gaussian *gaussian,
+                                        const mgx_critic *critic, int32_t K, double *reward, uint8_t *done, double *soc_trace,
+                                        uint32_t *status_trace, double *actions_out, double *raw_actions_out, double *logp_out,
+                                        double *value_out, double *final_value_out, double *last_value_out,
+                                        const mgx_episode_stats *stats, const mgx_episode_rows *rows, mgx_stream stream)
+{
+    g_err[0] = 0;
+    const CriticCall cc{critic, value_out, final_value_out, last_value_out};
+    const GaussianCall gc{gaussian, &cc, raw_actions_out, logp_out};
+    return step_k_policy_episodes_impl(h, policy, nullptr, K, reward, done, soc_trace, status_trace, actions_out, stats, rows, stream,
+                                       "mgx_step_k_policy_gaussian_episodes", &gc);
 }
 
 int mgx_rollout_lists(mgx_handle *h, const int32_t *action_id, int per_step, const int32_t *lists, int32_t n_lists, int32_t list_len,

@@ -7,7 +7,9 @@
 // mgx_step_policy_explore_episodes.hip) add the draw, the epsilon choice and the noise of mgx_exploration, each stated once below;
 // the sampling twin of the discrete launch (mgx_rollout_policy_sample_episodes: mgx_policy_sample_episodes.hip) the exp and the
 // softmax-sampling head of mgx_sampling; the critic twin of that one (mgx_rollout_policy_critic_episodes:
-// mgx_policy_critic_episodes.hip) the value head of mgx_critic, in functions of its own.
+// mgx_policy_critic_episodes.hip) the value head of mgx_critic, in functions of its own; the Gaussian twin of the continuous launch
+// (mgx_step_k_policy_gaussian_episodes: mgx_step_policy_gaussian_episodes.hip) the log, the quarter turn, the normal pair and the
+// head of mgx_gaussian.
 // On top of mgx_episode_rows.hpp (the rows) and, through it, mgx_episode_loop.hpp (what all six episode loops share).
 #pragma once
 #include "mgx_episode_rows.hpp"
@@ -401,6 +403,150 @@ __device__ __forceinline__ double policy_value(const double *w, int32_t nh, int3
     return val;
 }
 
+// ---- the Gaussian head: the rule of mgx_gaussian (include/mgx.h), for step_k_policy_gaussian_episodes_kernel
+// (mgx_step_policy_gaussian_episodes.hip).  New functions beside the ones above; log, sine and cosine are fixed sequences of IEEE
+// operations (the build has -ffp-contract=off), and so is the square root (policy_sqrt); the division is the correctly rounded one. ----
+// mgx_gaussian as the kernel sees it, by value in its argument struct
+struct GaussianArgs {
+    uint64_t seed;
+    double sigma[4];
+    const double *scale;             // [N] or NULL
+};
+
+// L(a) for a positive normal a: exponent and mantissa out of the bits, m folded into (sqrt(1/2), sqrt(2)], 2 atanh(t) by Horner
+__device__ __forceinline__ double policy_log(double a)
+{
+    const uint64_t bits = (uint64_t)__double_as_longlong(a);
+    int32_t e = (int32_t)((bits >> 52) & 0x7ffu) - 1023;
+    double m = __longlong_as_double((long long)((bits & 0x000fffffffffffffull) | 0x3ff0000000000000ull));
+    const bool big = m > 1.4142135623730951;
+    m = big ? m * 0.5 : m;
+    e = big ? e + 1 : e;
+    const double t = (m - 1.0) / (m + 1.0);
+    const double w = t * t;
+    double p = 0.09523809523809523;                                                      // the doubles nearest 2 / (2n + 1), n = 10 .. 0
+    p = p * w + 0.10526315789473684;
+    p = p * w + 0.11764705882352941;
+    p = p * w + 0.13333333333333333;
+    p = p * w + 0.15384615384615385;
+    p = p * w + 0.18181818181818182;
+    p = p * w + 0.2222222222222222;
+    p = p * w + 0.2857142857142857;
+    p = p * w + 0.4;
+    p = p * w + 0.6666666666666666;
+    p = p * w + 2.0;
+    const double ed = (double)e;
+    return ed * 6.93147180369123816490e-01 + (ed * 1.90821492927058770002e-10 + t * p);
+}
+
+// (sin, cos) of f quarter turns, f a multiple of 2^-52 in [0, 1): folded at the eighth of a turn, two Horner sums in x^2
+__device__ __forceinline__ void policy_quarter_turn(double f, double &sn, double &cs)
+{
+    const bool hi = f > 0.5;
+    const double g = hi ? 1.0 - f : f;
+    const double x = g * 1.5707963267948966;
+    const double w = x * x;
+    double q = -7.647163731819816e-13;                                                   // the doubles nearest -+1/k!, k = 15, 13 .. 3
+    q = q * w + 1.6059043836821613e-10;
+    q = q * w + -2.505210838544172e-08;
+    q = q * w + 2.7557319223985893e-06;
+    q = q * w + -0.0001984126984126984;
+    q = q * w + 0.008333333333333333;
+    q = q * w + -0.16666666666666666;
+    const double s = x * (q * w + 1.0);
+    double c = 4.779477332387385e-14;                                                    // ... k = 16, 14 .. 2, then the constant 1.0
+    c = c * w + -1.1470745597729725e-11;
+    c = c * w + 2.08767569878681e-09;
+    c = c * w + -2.755731922398589e-07;
+    c = c * w + 2.48015873015873e-05;
+    c = c * w + -0.001388888888888889;
+    c = c * w + 0.041666666666666664;
+    c = c * w + -0.5;
+    c = c * w + 1.0;
+    sn = hi ? c : s;
+    cs = hi ? s : c;
+}
+
+// S(v): the square root as a fixed sequence -- 1 / sqrt(v) from its bits, four Newton steps of multiplies and adds, one correction
+__device__ __forceinline__ double policy_sqrt(double v)
+{
+    const bool pos = v > 0.0;
+    const double a = pos ? v : 1.0;
+    double y = __longlong_as_double((long long)(0x5FE6EB50C7B537A9ull - ((uint64_t)__double_as_longlong(a) >> 1)));
+    const double h = 0.5 * a;
+    y = y * (1.5 - (h * y) * y);
+    y = y * (1.5 - (h * y) * y);
+    y = y * (1.5 - (h * y) * y);
+    y = y * (1.5 - (h * y) * y);
+    const double r = a * y;
+    const double S = r + (0.5 * y) * (a - r * r);
+    return pos ? S : 0.0;
+}
+
+// normal pair p of grid i at step counter t: z0 = z[2p] = R cos, z1 = z[2p + 1] = R sin (Box-Muller on draw number 8 + p)
+__device__ __forceinline__ void gaussian_pair(uint64_t seed, int64_t i, int32_t t, uint32_t p, double &z0, double &z1)
+{
+    uint32_t r[4];
+    explore_draw(seed, i, t, 8u + p, r);
+    const double u1 = 1.0 - uniform53(r[0], r[1]);                                        // (exact; in (0, 1])
+    const double R = policy_sqrt(-2.0 * policy_log(u1));
+    const uint64_t a64 = (uint64_t)r[2] << 32 | r[3];
+    const uint32_t q = (uint32_t)(a64 >> 62);
+    const double f = (double)((a64 >> 10) & 0x000fffffffffffffull) * (1.0 / 4503599627370496.0);
+    double s, c;
+    policy_quarter_turn(f, s, c);
+    const double sn = q == 0u ? s : (q == 1u ? c : (q == 2u ? -s : -c));
+    const double cs = q == 0u ? c : (q == 1u ? -s : (q == 2u ? -c : s));
+    z0 = R * cs;
+    z1 = R * sn;
+}
+
+// C_i of the lane, formed once in the prologue: the sum over the live columns (s > 0) of L(s) + log(2 pi) / 2, in column order
+template <int A, class SIGMA>
+__device__ __forceinline__ double gaussian_lane_const(SIGMA sigma, double sc)
+{
+    double C = 0.0;
+#pragma unroll
+    for (int o = 0; o < A; o++) {
+        const double s = sigma(o) * sc;
+        const bool live = s > 0.0;
+        const double term = policy_log(live ? s : 1.0) + 0.9189385332046727;
+        C = live ? C + term : C;
+    }
+    return C;
+}
+
+// the Gaussian head on y[0 .. A): raw[o] = y[o] + s[o] * z[o] on the live columns (y[o] on the others), a pair's draw only where
+// one of its columns is live; every raw[o] goes to `sink(o, raw)` as soon as its pair is known (o a constant once the loop is
+// unrolled), so that nothing of a pair outlives it.  Returns logp = (-0.5 * Q) - C, Q the sum of z[o]^2 over the live columns in
+// order.  `sigma(o)`: where the kernel reads sigma[o] (the kernarg segment), `sc`: the lane's scale, `C`: its gaussian_lane_const.
+template <int A, int NO, class SIGMA, class SINK>
+__device__ __forceinline__ double policy_gaussian_head(const double (&y)[NO], SIGMA sigma, double sc, double C, uint64_t seed, int64_t i,
+                                                       int32_t t, SINK sink)
+{
+    double Q = 0.0;
+#pragma unroll
+    for (int p = 0; 2 * p < A; p++) {
+        const bool two = 2 * p + 1 < A;                                                   // (false: the pair's second column does not exist)
+        const int o0 = 2 * p, o1 = two ? 2 * p + 1 : 2 * p;
+        const double s0 = sigma(o0) * sc;
+        const double s1 = two ? sigma(o1) * sc : 0.0;
+        const bool l0 = s0 > 0.0, l1 = s1 > 0.0;
+        double r0 = y[o0], r1 = y[o1];
+        if (l0 || l1) {
+            double z0, z1;
+            gaussian_pair(seed, i, t, (uint32_t)p, z0, z1);
+            r0 = l0 ? r0 + s0 * z0 : r0;
+            Q = l0 ? Q + z0 * z0 : Q;
+            r1 = l1 ? r1 + s1 * z1 : r1;
+            Q = l1 ? Q + z1 * z1 : Q;
+        }
+        sink(o0, r0);
+        if (two) sink(o1, r1);
+    }
+    return (-0.5 * Q) - C;
+}
+
 // columns of an H = 0 row of layout F
 template <int F>
 constexpr int policy_row_dim() { return 2 + 4 * ((F & F_GENSET) != 0) + 2 * ((F & F_BATTERY) != 0) + 4 * ((F & F_GRID) != 0); }
@@ -502,6 +648,18 @@ struct RolloutPolicyCriticArgs {
     double *last_value_out;                // [N] or NULL
 };
 
+// ... and of the Gaussian kernel: the greedy continuous kernel's struct first, the head, its two streams, the critic and its three
+// outputs behind it (the critic's fields are read by the CRITIC forms alone)
+struct StepPolicyGaussianArgs {
+    StepPolicyArgs g;
+    GaussianArgs gs;
+    double *raw_out;                 // [K, N, A] or NULL
+    double *logp_out;                // [K, N] or NULL
+    CriticArgs cr;
+    double *value_out, *final_value_out;   // [K, N] or NULL
+    double *last_value_out;                // [N] or NULL
+};
+
 // ---- host side: what mgx_abi.hip hands the slices of the six translation units ----
 struct EpisodePolicyLaunch {
     EpisodeRowsLaunch r;             // as for the kernels with rows (obs / final_obs may both be NULL here)
@@ -513,6 +671,9 @@ struct EpisodePolicyLaunch {
     double *prob_out;
     CriticArgs cr;                   // ... the critic kernel alone the rest (lds_bytes / pol.stride then hold policy_critic_set_doubles)
     double *value_out, *final_value_out, *last_value_out;
+    GaussianArgs gs;                 // ... the Gaussian kernel these, `cr` and the three outputs above with `critic`
+    double *raw_out, *logp_out;
+    bool critic;
 };
 bool launch_rollout_policy_episodes_p0(const EpisodePolicyLaunch &L); bool launch_rollout_policy_episodes_p1(const EpisodePolicyLaunch &L);
 bool launch_step_k_policy_episodes_p0(const EpisodePolicyLaunch &L); bool launch_step_k_policy_episodes_p1(const EpisodePolicyLaunch &L);
@@ -520,5 +681,6 @@ bool launch_rollout_policy_explore_episodes_p0(const EpisodePolicyLaunch &L); bo
 bool launch_step_k_policy_explore_episodes_p0(const EpisodePolicyLaunch &L); bool launch_step_k_policy_explore_episodes_p1(const EpisodePolicyLaunch &L);
 bool launch_rollout_policy_sample_episodes_p0(const EpisodePolicyLaunch &L); bool launch_rollout_policy_sample_episodes_p1(const EpisodePolicyLaunch &L);
 bool launch_rollout_policy_critic_episodes_p0(const EpisodePolicyLaunch &L); bool launch_rollout_policy_critic_episodes_p1(const EpisodePolicyLaunch &L);
+bool launch_step_k_policy_gaussian_episodes_p0(const EpisodePolicyLaunch &L); bool launch_step_k_policy_gaussian_episodes_p1(const EpisodePolicyLaunch &L);
 
 }  // namespace mgx

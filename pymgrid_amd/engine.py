@@ -30,6 +30,8 @@ except AttributeError:                 # pragma: no cover
 VALUE_OUTPUTS = ("values", "final_values", "last_value")      # what a critic launch returns on request (values=)
 CRITIC_NEEDS_SAMPLING = ("critic= goes with sampling=: the critic sits beside the actor of the sampling launch -- "
                          "Sampling(seed, temperature=0) is the greedy head")
+CRITIC_NEEDS_GAUSSIAN = ("critic= goes with sampling=: the critic sits beside the actor of the Gaussian launch -- "
+                         "GaussianSampling(seed, 0.0) is the greedy head")
 
 
 class StepEngine:
@@ -867,14 +869,32 @@ class StepEngine:
         return self._launch_policy_episodes("mgx_rollout_policy_episodes", policy, exploration, (tptr, n_lists, K), K, res, (r, d, s, g),
                                             taken, st, out, obs, final_obs, sampling=sampling, probs=pr, critic=critic, values=vals)
 
+    GAUSSIAN_KEYWORDS = ("sampling", "logp", "raw_actions", "critic", "values")
+
     def step_k_policy_episodes(self, policy, K, reward=True, done=False, soc_trace=False, status_trace=False, actions=False,
-                               stats=None, out=None, obs=False, final_obs=False, exploration=None):
+                               stats=None, out=None, obs=False, final_obs=False, exploration=None, **gaussian):
         """``step_k_episodes`` with the loop closed inside the launch (``mgx_step_k_policy_episodes``): the controls of every step are
         ``policy`` (an ``MLPPolicy`` with ``head="continuous"``, ``n_out`` = ``action_dim``) applied to the observation row the grid
         stands on, stepped normalised -- what K times ``u = policy.act(obs); obs, ... = step(u, normalized=True)`` leaves, bit for
         bit.  ``actions=True``: also the controls taken (float64 [K, N, A]).  float64 controls only (``action_dtype``).
         ``exploration``: noise on the controls inside the launch (``mgx_step_k_policy_explore_episodes``), as for
-        ``rollout_policy_episodes``."""
+        ``rollout_policy_episodes``.
+        The keywords of the Gaussian head -- ``sampling=`` (a ``GaussianSampling``), ``logp=``, ``raw_actions=``, ``critic=``,
+        ``values=`` (``GAUSSIAN_KEYWORDS``) -- are taken by name and handed to ``step_k_policy_gaussian_episodes``, which states them
+        (the explicit parameters of this call are those of the greedy and the exploring launch); any other name is a TypeError."""
+        unknown = set(gaussian) - set(self.GAUSSIAN_KEYWORDS)
+        if unknown:
+            raise TypeError(f"step_k_policy_episodes() got an unexpected keyword argument {sorted(unknown)[0]!r}")
+        if gaussian.get("sampling") is not None:
+            return self.step_k_policy_gaussian_episodes(policy, gaussian.pop("sampling"), K, reward=reward, done=done, soc_trace=soc_trace,
+                                                        status_trace=status_trace, actions=actions, stats=stats, out=out, obs=obs,
+                                                        final_obs=final_obs, exploration=exploration, **gaussian)
+        if gaussian.get("logp") or gaussian.get("raw_actions"):
+            raise ValueError("logp=True / raw_actions=True go with sampling=: a GaussianSampling")
+        if gaussian.get("critic") is not None:
+            raise ValueError(CRITIC_NEEDS_GAUSSIAN)
+        if gaussian.get("values"):
+            raise ValueError("values= goes with critic=: a ValueHead on the policy's trunk")
         out = out or {}
         K = int(K)
         st = self._episode_stats(stats)
@@ -882,6 +902,51 @@ class StepEngine:
         taken = self._actions_out(res, out, actions, (K, self.N, self.action_dim), torch.float64)
         return self._launch_policy_episodes("mgx_step_k_policy_episodes", policy, exploration, (K,), K, res, (r, d, s, g), taken, st,
                                             out, obs, final_obs)
+
+    def step_k_policy_gaussian_episodes(self, policy, sampling, K, reward=True, done=False, soc_trace=False, status_trace=False,
+                                        actions=False, stats=None, out=None, obs=False, final_obs=False, exploration=None, logp=False,
+                                        raw_actions=False, critic=None, values=False):
+        """``step_k_policy_episodes`` with a Gaussian head (``mgx_step_k_policy_gaussian_episodes``): ``sampling`` is a
+        ``pymgrid_amd.policy.GaussianSampling`` (not together with ``exploration``) and the controls are drawn from ``N(y, s**2)``
+        inside the launch -- what ``policy.act(obs, sampling, counter, return_logp=True, return_raw=True)`` leaves, bit for bit;
+        ``logp=True`` returns the log-probability of every draw (float64 [K, N]), ``raw_actions=True`` the pre-clip actions (float64
+        [K, N, A]).  ``critic`` (a ``ValueHead`` with ``head="continuous"``) and ``values`` as for ``rollout_policy_episodes``:
+        ``values`` / ``final_values`` / ``last_value``, and nothing else changes."""
+        out = out or {}
+        K = int(K)
+        from .policy import GaussianSampling
+        if exploration is not None:
+            raise ValueError("exploration= and sampling= exclude each other: the Gaussian head draws from the policy's own distribution")
+        if not isinstance(sampling, GaussianSampling):
+            raise ValueError("sampling= of the continuous head is a GaussianSampling (softmax sampling is the discrete head's)")
+        if values and critic is None:
+            raise ValueError("values= goes with critic=: a ValueHead on the policy's trunk")
+        names = VALUE_OUTPUTS if values is True else tuple(values or ())
+        if set(names) - set(VALUE_OUTPUTS):
+            raise ValueError(f"values names {sorted(set(names) - set(VALUE_OUTPUTS))}: True or any of {VALUE_OUTPUTS}")
+        if critic is not None:
+            critic.check(policy)
+        st = self._episode_stats(stats)
+        res, r, d, s, g, _ = self._fused_outputs(out, K, reward, done, soc_trace, status_trace)
+        taken = self._actions_out(res, out, actions, (K, self.N, self.action_dim), torch.float64)
+        raw = self._actions_out(res, out, raw_actions, (K, self.N, self.action_dim), torch.float64, name="raw_actions")
+        lp = self._actions_out(res, out, logp, (K, self.N), torch.float64, name="logp")
+        fresh = "final_values" in names and out.get("final_values") is None
+        vals = tuple(self._actions_out(res, out, name in names, (self.N,) if name == "last_value" else (K, self.N), torch.float64, name=name)
+                     for name in VALUE_OUTPUTS)
+        if fresh:
+            res["final_values"].zero_()          # (only the entries of the grids a step restarts are written)
+        pst, keep = policy.c_struct(self.device, self.N)
+        gst, keep_g = sampling.c_struct(self.device, self.N)
+        cst, keep_c = critic.c_struct(self.device, self.N) if critic is not None else (None, None)
+        rows = self._episode_rows(res, out, K, obs, final_obs)
+        self._call(self._lib.mgx_step_k_policy_gaussian_episodes, C.byref(pst), C.byref(gst), None if cst is None else C.byref(cst), K,
+                   *map(_ptr, (r, d, s, g)), _ptr(taken), _ptr(raw), _ptr(lp), *map(_ptr, vals), C.byref(st),
+                   None if rows is None else C.byref(rows))
+        del keep, keep_g, keep_c
+        if self._t is not None:
+            self._t += K
+        return res
 
     def rollout_lists(self, action_id, lists, K, reward=True, done=False, soc_trace=False, status_trace=False, ret_acc=None,
                       log=False, out=None):

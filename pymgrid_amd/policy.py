@@ -166,6 +166,131 @@ class Sampling:
         return st, sc
 
 
+LN2_HI, LN2_LO = 6.93147180369123816490e-01, 1.90821492927058770002e-10     # the two ln 2 constants of E and L
+SQRT2, HALF_PI, HALF_LOG_2PI = 1.4142135623730951, 1.5707963267948966, 0.9189385332046727
+LOG_COEFFS = tuple(2.0 / (2 * n + 1) for n in range(11))           # the doubles nearest 2 / (2n + 1) (include/mgx.h, mgx_gaussian)
+SIN_COEFFS = (-0.16666666666666666, 0.008333333333333333, -0.0001984126984126984, 2.7557319223985893e-06, -2.505210838544172e-08,
+              1.6059043836821613e-10, -7.647163731819816e-13)      # ... nearest -+1/k!, k = 3, 5 .. 15
+COS_COEFFS = (-0.5, 0.041666666666666664, -0.001388888888888889, 2.48015873015873e-05, -2.755731922398589e-07, 2.08767569878681e-09,
+              -1.1470745597729725e-11, 4.779477332387385e-14)      # ... nearest -+1/k!, k = 2, 4 .. 16
+GAUSS_DRAW = 8              # draw number of normal pair 0 (numbers 0 .. 3: the exploring head, 1: softmax sampling)
+
+
+def policy_log(a):
+    """``L(a)`` of ``mgx_gaussian`` (include/mgx.h) for a float64 tensor of positive normal numbers: the device's ``policy_log``
+    operation by operation -- exponent and mantissa out of the bits, one division, separate multiplies and adds -- so the two agree
+    bit for bit.  Within 4 ulp of ``torch.log``; ``policy_log(1.0) == 0.0``."""
+    bits = a.contiguous().view(torch.int64)
+    e = ((bits >> 52) & 0x7FF) - 1023
+    m = ((bits & ((1 << 52) - 1)) | (1023 << 52)).view(torch.float64)
+    big = m > SQRT2
+    m = torch.where(big, m * 0.5, m)
+    e = (e + big.to(torch.int64)).to(torch.float64)
+    t = (m - 1.0) / (m + 1.0)
+    w = t * t
+    p = torch.full_like(t, LOG_COEFFS[10])
+    for n in range(9, -1, -1):
+        p = p * w + LOG_COEFFS[n]
+    return e * LN2_HI + (e * LN2_LO + t * p)
+
+
+def policy_quarter_turn(f):
+    """``(sin, cos)`` of ``f`` quarter turns (the angle ``f * pi / 2``) by the rule of ``mgx_gaussian`` (include/mgx.h), for a
+    float64 tensor of multiples of 2**-52 in [0, 1): the device's ``policy_quarter_turn`` operation by operation."""
+    hi = f > 0.5
+    g = torch.where(hi, 1.0 - f, f)
+    x = g * HALF_PI
+    w = x * x
+    q = torch.full_like(x, SIN_COEFFS[6])
+    for n in range(5, -1, -1):
+        q = q * w + SIN_COEFFS[n]
+    s = x * (q * w + 1.0)
+    c = torch.full_like(x, COS_COEFFS[7])
+    for n in range(6, -1, -1):
+        c = c * w + COS_COEFFS[n]
+    c = c * w + 1.0
+    return torch.where(hi, c, s), torch.where(hi, s, c)
+
+
+RSQRT_MAGIC = 0x5FE6EB50C7B537A9
+
+
+def policy_sqrt(v):
+    """``S(v)`` of ``mgx_gaussian`` (include/mgx.h) for a finite float64 tensor: the square root as a fixed sequence of multiplies and
+    adds -- ``1 / sqrt(v)`` from its bits, four Newton steps, one correction -- so host and device agree bit for bit; within 1 ulp of
+    ``torch.sqrt``, 0.0 where ``not v > 0``."""
+    pos = v > 0
+    a = torch.where(pos, v, torch.ones_like(v))
+    y = (RSQRT_MAGIC - (a.contiguous().view(torch.int64) >> 1)).view(torch.float64)
+    h = 0.5 * a
+    for _ in range(4):
+        y = y * (1.5 - (h * y) * y)
+    r = a * y
+    return torch.where(pos, r + (0.5 * y) * (a - r * r), torch.zeros_like(v))
+
+
+def gaussian_uniforms(seed, grid, counter, pair, device=None):
+    """``(u1, q, f)`` of normal pair ``pair`` (``mgx_gaussian``): the radius' uniform in (0, 1], the quadrant (int64, 0 .. 3) and the
+    fraction of a quarter turn, out of draw number ``GAUSS_DRAW + pair``."""
+    r = philox_words(seed, grid, counter, EXPLORE_TAG + GAUSS_DRAW + int(pair), device)
+    u1 = 1.0 - uniform53(r[0], r[1])
+    q = r[2] >> 30                                                  # (bits 63, 62 of a64 = r[2] << 32 | r[3])
+    f = ((((r[2] & 0x3FFFFFFF) << 22) | (r[3] >> 10)).to(torch.float64)) * (1.0 / 4503599627370496.0)
+    return u1, q, f
+
+
+def gaussian_pair(seed, grid, counter, pair, device=None):
+    """``(z[2 * pair], z[2 * pair + 1])`` of ``mgx_gaussian`` (include/mgx.h): two independent standard normal draws of grid
+    ``grid`` at step counter ``counter`` by Box-Muller on the rule's own logarithm, sine and cosine -- the device's
+    ``gaussian_pair`` bit for bit."""
+    u1, q, f = gaussian_uniforms(seed, grid, counter, pair, device)
+    R = policy_sqrt(-2.0 * policy_log(u1))
+    s, c = policy_quarter_turn(f)
+    sin = torch.where(q == 0, s, torch.where(q == 1, c, torch.where(q == 2, -s, -c)))
+    cos = torch.where(q == 0, c, torch.where(q == 1, -s, torch.where(q == 2, -c, s)))
+    return R * cos, R * sin
+
+
+class GaussianSampling:
+    """What the Gaussian closed-loop launch adds to a continuous ``MLPPolicy`` (``mgx_gaussian``, include/mgx.h): control ``o`` is
+    drawn from ``N(y[o], s[o]**2)``, ``s[o] = sigma[o] * scale[i]``, by a counter-based Box-Muller draw keyed by ``seed``, clipped
+    as the greedy head clips; the launch returns the pre-clip action and its exact log-density.  ``sigma``: one value for every
+    action column or up to four, one per column (0: that column stays greedy and drops out of the log-probability); ``scale``
+    (float64 ``[N]``, numpy or torch) multiplies every sigma of grid i (0 switches a grid back to the greedy head).  Validated as
+    the C call does: a sigma is 0 or a positive NORMAL float64 (the rule's logarithm reads exponent and mantissa)."""
+
+    def __init__(self, seed, sigma, scale=None):
+        self.seed = int(seed)
+        if not 0 <= self.seed < 2 ** 64:
+            raise ValueError(f"seed = {seed}: a 64-bit unsigned key")
+        sg = [float(v) for v in np.atleast_1d(np.asarray(sigma, dtype=np.float64))]
+        if not 1 <= len(sg) <= MAX_CONTROLS:
+            raise ValueError(f"sigma holds {len(sg)} values: one, or one per action column (at most {MAX_CONTROLS})")
+        if not all(v == 0.0 or np.finfo(np.float64).tiny <= v < float("inf") for v in sg):
+            raise ValueError(f"sigma = {sigma}: standard deviations are 0 or positive, finite and not subnormal")
+        shared = np.ndim(sigma) == 0
+        self.sigma = tuple(sg * MAX_CONTROLS if shared else sg + [0.0] * (MAX_CONTROLS - len(sg)))
+        self.scale = None
+        if scale is not None:
+            t = scale if torch.is_tensor(scale) else torch.as_tensor(np.asarray(scale))
+            if t.dtype != torch.float64 or t.dim() != 1:
+                raise ValueError(f"scale must be a float64 vector [N], not {t.dtype} {tuple(t.shape)}")
+            self.scale = t.contiguous()
+
+    scale_on = Exploration.scale_on
+
+    def c_struct(self, device, n_grids):
+        """``(mgx_gaussian, keep-alive)`` with ``scale`` on ``device``."""
+        st = _lib.Gaussian()
+        st.struct_size = C.sizeof(_lib.Gaussian)
+        st.seed = self.seed
+        for o, v in enumerate(self.sigma):
+            st.sigma[o] = v
+        sc = self.scale_on(device, n_grids)
+        st.scale = None if sc is None else sc.data_ptr()
+        return st, sc
+
+
 class MLPPolicy:
     """``y = W2 . relu(W1 . x + b1) + b2`` (``W1 = b1 = None``: the linear policy ``y = W2 . x + b2``) on the observation row ``x``,
     every sum taken in index order with a separate multiply and add; ``relu(h) = h if h > 0 else +0.0``.
@@ -279,13 +404,28 @@ class MLPPolicy:
             x = torch.where(h > 0, h, torch.zeros_like(h))
         return self._layer(me.W2, me.b2, idx, x)
 
-    def act(self, obs, exploration=None, counter=None, return_prob=False):
+    def act(self, obs, exploration=None, counter=None, return_prob=False, return_logp=False, return_raw=False):
         """The actions for observation rows ``obs`` [N, n_in]: priority-list ids (int32 [N]) or normalised controls (float64
         [N, n_out]) -- what the fused launches take, bit for bit.  ``exploration`` (an ``Exploration``) with ``counter``, the int the
         handle's shared step counter holds BEFORE the step (``env.current_step``): the host statement of the rule of
         ``mgx_exploration`` (include/mgx.h) -- row n of ``obs`` is grid n -- and what the exploring launches take, bit for bit.
         A ``Sampling`` in its place (discrete head only): the rule of ``mgx_sampling``, what the sampling launch takes;
-        ``return_prob=True`` then returns ``(ids, prob)``, ``prob`` (float64 [N]) the probability of the id taken."""
+        ``return_prob=True`` then returns ``(ids, prob)``, ``prob`` (float64 [N]) the probability of the id taken.
+        A ``GaussianSampling`` (continuous head only): the rule of ``mgx_gaussian``, what the Gaussian launch takes;
+        ``return_logp=True`` / ``return_raw=True`` then return ``(u, logp, raw)`` (the ones asked for, in this order): ``logp``
+        (float64 [N]) the log-density of the pre-clip action ``raw`` (float64 [N, n_out])."""
+        if isinstance(exploration, GaussianSampling):
+            if self.head != "continuous":
+                raise ValueError("a GaussianSampling goes with the continuous head (the discrete head samples with Sampling)")
+            if counter is None:
+                raise ValueError("sampling needs `counter`, the handle's step counter before the step (env.current_step)")
+            if return_prob:
+                raise ValueError("return_prob=True goes with a Sampling (a density has no probability: return_logp=True)")
+            u, logp, raw = self._gaussian(self.outputs(obs), exploration, int(counter))
+            res = (u,) + ((logp,) if return_logp else ()) + ((raw,) if return_raw else ())
+            return res if len(res) > 1 else u
+        if return_logp or return_raw:
+            raise ValueError("return_logp=True / return_raw=True go with a GaussianSampling")
         if isinstance(exploration, Sampling):
             if self.head != "discrete":
                 raise ValueError("sampling is offered on the discrete head (the continuous head explores with Exploration.sigma)")
@@ -369,6 +509,28 @@ class MLPPolicy:
             open_ = open_ & ~take
         return torch.where(live, ids, g), torch.where(live, e_id / S, torch.ones_like(S))
 
+    def _gaussian(self, y, gs, counter):
+        """``(u, logp, raw)`` by the rule of ``mgx_gaussian`` on the outputs ``y`` [N, n_out]: ``raw = y + s * z`` on the live
+        columns (``s > 0``), its clip, and the log-density of ``raw`` over the live columns."""
+        n, dev = y.shape[0], y.device
+        grid = torch.arange(n, dtype=torch.int64, device=dev)
+        scale = gs.scale_on(dev, n)
+        zero = torch.zeros(n, dtype=torch.float64, device=dev)
+        s = [zero + gs.sigma[o] if scale is None else gs.sigma[o] * scale for o in range(self.n_out)]
+        live = [v > 0 for v in s]
+        Cn = zero
+        for o in range(self.n_out):
+            Cn = torch.where(live[o], Cn + (policy_log(torch.where(live[o], s[o], torch.ones_like(zero))) + HALF_LOG_2PI), Cn)
+        Q, cols = zero, []
+        for p in range((self.n_out + 1) // 2):
+            for o, z in zip((2 * p, 2 * p + 1), gaussian_pair(gs.seed, grid, counter, p)):
+                if o < self.n_out:
+                    cols.append(torch.where(live[o], y[:, o] + s[o] * z, y[:, o]))
+                    Q = torch.where(live[o], Q + z * z, Q)
+        raw = torch.stack(cols, dim=1) if cols else y
+        u = torch.where(~(raw > 0), torch.zeros_like(raw), torch.where(raw > 1, torch.ones_like(raw), raw))
+        return u, (-0.5 * Q) - Cn, raw
+
     def c_struct(self, device, n_grids):
         """``(mgx_policy, keep-alive)`` with the parameters on ``device``."""
         me = self.to(device)
@@ -385,14 +547,18 @@ class MLPPolicy:
 
 
 class ValueHead:
-    """A critic beside a discrete ``MLPPolicy`` (``mgx_critic``, include/mgx.h): one more output row on the policy's trunk,
+    """A critic beside an ``MLPPolicy`` (``mgx_critic``, include/mgx.h): one more output row on the policy's trunk,
     ``V(x) = b + sum over j in order of w[j] * v[j]`` with ``v`` the policy's hidden vector after its ReLU, or ``x`` for a linear
     policy -- a separate multiply and add each.  ``w`` float64 ``[n_mid]`` or ``[P, n_mid]`` (``n_mid`` = the policy's ``n_hidden``,
     or its ``n_in`` without a hidden layer), ``b`` a float64 scalar or ``[P]``; the parameter set of a grid is the policy's own
     (``policy_index``).  The sampling launch evaluates it inside the kernel (``critic=`` of ``rollout_policy``); ``value`` is the same
-    rule on the host.  Validated as the C call does."""
+    rule on the host.  Validated as the C call does.  ``head`` names the head of the policy it sits
+    beside: "discrete" (the sampling launch) or "continuous" (the Gaussian launch, ``critic=`` of ``step_k_policy``)."""
 
-    def __init__(self, w, b):
+    def __init__(self, w, b, head="discrete"):
+        if head not in ("discrete", "continuous"):
+            raise ValueError(f"head must be 'discrete' or 'continuous', not {head!r}")
+        self.head = head
         self.w = _f64("w", w, 2)
         if self.w is None or b is None:
             raise ValueError("w and b are required")
@@ -411,16 +577,17 @@ class ValueHead:
             raise ValueError(f"the parameters lie on different devices: {sorted(map(str, (self.w.device, self.b.device)))}")
 
     def check(self, policy):
-        """Whether the head fits ``policy``: a discrete ``MLPPolicy`` with as many parameter sets and ``n_mid`` trunk outputs."""
-        if not isinstance(policy, MLPPolicy) or policy.head != "discrete":
-            raise ValueError("a ValueHead goes with a discrete MLPPolicy (the sampling launch)")
+        """Whether the head fits ``policy``: an ``MLPPolicy`` of the same ``head`` with as many parameter sets and ``n_mid`` trunk outputs."""
+        if not isinstance(policy, MLPPolicy) or policy.head != self.head:
+            raise ValueError(f"a ValueHead with head={self.head!r} goes with an MLPPolicy of that head (the sampling launch; "
+                             "head='continuous': the Gaussian launch)")
         n_mid = policy.n_hidden or policy.n_in
         if self.n_mid != n_mid or self.n_policies != policy.n_policies:
             raise ValueError(f"w {tuple(self.w.shape)} does not fit the policy: [P, n_mid] = [{policy.n_policies}, {n_mid}]")
 
     def lds_bytes(self, policy):
         """Bytes of the parameter sets as the critic launch stages them (include/mgx.h, ``mgx_rollout_policy_critic_episodes``)."""
-        m = (policy.n_out + 3) // 4 * 4
+        m = (policy.n_out + 3) // 4 * 4 if policy.head == "discrete" else policy.n_out
         per_set = m + 1 + (policy.n_hidden * (policy.n_in + 2 + m) if policy.n_hidden else policy.n_in * (m + 1))
         return policy.n_policies * ((per_set + 1) // 2 * 2) * 8
 
