@@ -227,7 +227,9 @@ enum mgx_tunable {
     MGX_TUNE_LAUNCH_THREADS = 9,   /* mode (0 / 1 / 2) handles created afterwards start with: mgx_set_launch_threads (default 1) */
     MGX_TUNE_MULTI_STATIC = 10,    /* 0: mgx_step_k of small general layouts never takes a compile-time-count specialisation (A/B, tests) */
     MGX_TUNE_FLEET_EPISODES = 11,  /* 0: mgx_fleet_step steps in-place-episode items beside its launches (default 1: one launch for them) */
-    MGX_TUNE_COUNT_ = 12
+    MGX_TUNE_STEP_K_HOT = 12,      /* 0: mgx_step_k never takes step_k_hot_kernel, the kernel of its own the lock-step reward + SoC launch on
+                                    * factorised series without a GridModule has (default 1; same values either way: A/B, tests) */
+    MGX_TUNE_COUNT_ = 13
 };
 int mgx_set_tunable(int32_t id, int64_t value);                                /* MGX_ERR_INVALID: unknown id / value out of range */
 int mgx_get_tunable(int32_t id, int64_t *value, int64_t *default_value);       /* either pointer may be NULL */

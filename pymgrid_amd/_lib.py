@@ -18,6 +18,7 @@ LIB_PATH = os.environ.get("MGX_LIB") or os.path.join(_PKG, "libmgx.so")   # MGX_
 UNITS = (
     ("mgx_abi.hip", None, 1),                                           # the host side + the small kernels
     ("mgx_fused.hip", "MGX_FUSED_PART", 6),                             # MGX_FUSED_PARTS: the K-step kernels
+    ("mgx_step_hot.hip", None, 1),                                      # the lock-step hot K-step launch in a kernel of its own
     ("mgx_episodes.hip", "MGX_EPISODE_PART", 2),                        # MGX_EPISODE_PARTS: the roll-out over in-place episodes,
     ("mgx_step_episodes.hip", "MGX_EPISODE_PART", 2),                   # ... the continuous K-step over them,
     ("mgx_episode_rows.hip", "MGX_EPISODE_PART", 2),                    # ... the roll-out with observation rows
@@ -32,7 +33,7 @@ UNITS = (
     ("mgx_gae.hip", None, 1),                                           # the advantages of what such launches return (mgx_gae)
 )
 # everything a built library is stamped with (source_hash): a file missing here would leave a stale libmgx.so looking current
-SOURCES = [os.path.join(_PKG, "csrc", f) for f in [u[0] for u in UNITS] + ["mgx_kernels.hpp", "mgx_core.hpp", "mgx_episode_loop.hpp", "mgx_episode_rows.hpp", "mgx_policy.hpp", "mgx_gae.hpp"]] + \
+SOURCES = [os.path.join(_PKG, "csrc", f) for f in [u[0] for u in UNITS] + ["mgx_kernels.hpp", "mgx_core.hpp", "mgx_step_hot.hpp", "mgx_episode_loop.hpp", "mgx_episode_rows.hpp", "mgx_policy.hpp", "mgx_gae.hpp"]] + \
           [os.path.join(_ROOT, "include", "mgx.h")]
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-fPIC"]
@@ -48,6 +49,8 @@ ABI_MINOR = 3
 # enum mgx_tunable (process-wide launch-shape knobs; set_tunable / get_tunable below)
 TUNABLES = ("win_threads", "win_group", "win_pairs", "win_min_lds", "prefetch_pool", "multi_generic", "multi_small_own",
             "grid_major_copy", "fleet_byvalue", "launch_threads", "multi_static", "fleet_episodes")
+# ... and the ones added since that set of twelve was fixed (their ids continue: MGX_TUNE_STEP_K_HOT = 12)
+TUNABLES_ADDED = ("step_k_hot",)
 MAX_INSTANCES = 8          # MGX_MAX_INSTANCES: gensets / batteries / grids per microgrid
 
 
@@ -480,11 +483,11 @@ def check(rc):
 
 def set_tunable(name, value):
     """mgx_set_tunable by name (TUNABLES): process-wide launch-shape knobs -- the library reads no environment variables."""
-    check(lib().mgx_set_tunable(TUNABLES.index(name), int(value)))
+    check(lib().mgx_set_tunable((TUNABLES + TUNABLES_ADDED).index(name), int(value)))
 
 
 def get_tunable(name):
     """(current value, default) of a tunable."""
     v, d = C.c_int64(), C.c_int64()
-    check(lib().mgx_get_tunable(TUNABLES.index(name), C.byref(v), C.byref(d)))
+    check(lib().mgx_get_tunable((TUNABLES + TUNABLES_ADDED).index(name), C.byref(v), C.byref(d)))
     return v.value, d.value

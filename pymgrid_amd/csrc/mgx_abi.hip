@@ -4,6 +4,7 @@
 //   hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -c mgx_abi.hip ; ... -c -DMGX_FUSED_PART=p mgx_fused.hip (p = 0..4)
 //   hipcc --offload-arch=gfx950 -fPIC -shared *.o -o libmgx.so
 #include "mgx_kernels.hpp"
+#include "mgx_step_hot.hpp"
 #include "mgx_episode_rows.hpp"
 #include "mgx_policy.hpp"
 #include "mgx_gae.hpp"
@@ -119,6 +120,7 @@ const int64_t kTuneDefault[MGX_TUNE_COUNT_] = {
     /* MGX_TUNE_LAUNCH_THREADS  */ 1,      // 0 / 1 / 2: see mgx_set_launch_threads
     /* MGX_TUNE_MULTI_STATIC    */ 1,
     /* MGX_TUNE_FLEET_EPISODES  */ 1,
+    /* MGX_TUNE_STEP_K_HOT      */ 1,
 };
 struct TuneInit { TuneInit() { for (int j = 0; j < MGX_TUNE_COUNT_; j++) g_tune[j].store(kTuneDefault[j], std::memory_order_relaxed); } } g_tune_init;
 inline int64_t tune(int id) { return g_tune[id].load(std::memory_order_relaxed); }
@@ -390,6 +392,18 @@ static FusedLaunch fused_launch_for(const mgx_handle *h, const KArgs &k, hipStre
     L.stream = s; L.k = &k; L.actions = nullptr; L.tab = nullptr; L.ids = nullptr;
     L.t = t_arg(h); L.K = K; L.normalized = 0; L.out = fo;
     return L;
+}
+
+// Does the K-step launch L of mgx_step_k go to step_k_hot_kernel (mgx_step_hot.hip)?  The hot form of step_k_kernel's loop and
+// nothing else: factorised series, a lock-step handle, no reward shaper, exactly reward (+ SoC where there is a battery; ret_acc
+// may ride along), a layout without a GridModule, and the base rows of all K steps in one LDS image.
+static bool step_k_hot_takes(const FusedLaunch &L)
+{
+    const KArgs &k = *L.k;
+    const bool layout = L.flags == F_GENSET || L.flags == F_BATTERY || L.flags == (F_GENSET | F_BATTERY);
+    const bool outputs = !L.rich && L.out.reward != nullptr && L.out.done == nullptr && (!(L.flags & F_BATTERY) || L.out.soc_trace != nullptr);
+    return tune(MGX_TUNE_STEP_K_HOT) != 0 && layout && outputs && L.fact && k.grid_final == nullptr && k.ep_off == nullptr &&
+           k.shaper == MGX_SHAPER_NONE && L.K <= STEP_HOT_MAX_K;
 }
 
 template <int F, bool NOISE, typename OT>
@@ -1659,6 +1673,7 @@ int mgx_step_k(mgx_handle *h, const void *actions, int32_t K, int normalized, do
     for_each_shard(h, st, [&](const KArgs &k, hipStream_t s) {
         FusedLaunch L = fused_launch_for(h, k, s, fo, K);
         L.actions = actions; L.act_f32 = k.act_f32 != 0; L.normalized = normalized;
+        if (step_k_hot_takes(L) && launch_step_k_hot(L)) return;
         (void)(launch_step_k_p0(L) || launch_step_k_p1(L) || launch_step_k_p2(L) || launch_step_k_p3(L) || launch_step_k_p4(L));
     });
     return finish_step(h, K, st, hipGetLastError(), "step_k_kernel launch");
