@@ -885,7 +885,61 @@ int mgx_step_k_policy_gaussian_episodes(mgx_handle *h, const mgx_policy *policy,
                                         double *value_out, double *final_value_out, double *last_value_out,
                                         const mgx_episode_stats *stats, const mgx_episode_rows *rows, mgx_stream stream);
 
-/* raise_errors=True (BaseMicrogridModule.__init__, base_module.py:40; as_source / as_sink, :213-224,265-270; _raise_error,
+/* WHAT-IF roll-outs of candidate plans ("shooting" model-predictive control): what would grid i earn over the next H steps under
+ * plan c, without taking those steps.  It stands in for the horizon loop of ModelPredictiveControl (algos/mpc/mpc.py: the cost of
+ * running the microgrid over the forecast horizon, on the series a forecaster="oracle" shows) with the simulator in the place of the
+ * cvxpy program: every candidate is H steps of Microgrid.run (microgrid.py:227-325) on a COPY of the grid's state.  The launch
+ * reads the handle of in-place episodes (mgx_reset_episodes) as mgx_rollout_episodes / mgx_step_k_episodes do -- state, parameters,
+ * the rows of the grid's own running episode from the handle's current counter value t0 on, the reward shaper -- and writes
+ * NOTHING back: no state, no counter move, no episode arrays, no statistics, no done flags, no rows.  THE RULE (stated here once;
+ * plain fp64 in step order, multiply and add separate):
+ *     per grid i and candidate c:  w = 1.0;  ret = 0.0
+ *     for k = 0 .. H - 1:
+ *         r   = the reward step k of plan c returns (what mgx_step_discrete / mgx_step return for it, shaper included)
+ *         ret = ret + w * r;   w = w * gamma
+ *         if t0 + k >= ep_final[i] - 1: stop        (the step that ends the episode is counted, nothing after it)
+ * Nothing beyond the end of the RUNNING episode is simulated, with or without mgx_set_auto_reset: where a restart would land is a
+ * draw that belongs to another episode.  The stop depends on the grid alone: steps[i] = min(H, ep_final[i] - t0), at least 1.
+ *     ret[c, i]       the discounted return above
+ *     steps[i]        the steps counted
+ *     end_soc[c, i]   the state of charge after the last counted step (what soc_trace of the roll-out holds there)
+ *     best[i]         the smallest c whose ret[c, i] no other exceeds: c = 0, then every later c replaces it where ret[c, i] is
+ *                     GREATER (ties go to the first maximum)
+ *     best_ret[i]     ret[best[i], i]
+ *     first_action    step 0 of plan best[i], in the form the plans have: the id byte, or the A controls
+ * best / best_ret / first_action / steps come from a second, small launch that is skipped when all four are NULL. */
+typedef struct mgx_lookahead {
+    int32_t struct_size;   /* = sizeof(mgx_lookahead) */
+    int32_t C, H;          /* candidates per grid, horizon; both >= 1 */
+    int32_t per_grid;      /* 0: plans shared by all grids; 1: a plan per grid */
+    double  gamma;         /* in [0, 1] */
+    double  *ret;          /* [C, N], required */
+    int32_t *steps;        /* [N] or NULL */
+    double  *end_soc;      /* [C, N] or NULL: the value soc_trace would hold at the last counted step */
+    int32_t *best;         /* [N] or NULL */
+    double  *best_ret;     /* [N] or NULL */
+    void    *first_action; /* discrete: uint8 [N]; continuous: [N, A] in the action format; or NULL */
+} mgx_lookahead;
+
+/* Discrete plans: priority-list ids as bytes, [C, H] (la->per_grid == 0) or [C, H, N]; `table` / n_actions as in
+ * mgx_rollout_discrete, ids outside the table select list 0.  One launch of lookahead_episodes_kernel (+ the pick).
+ * MGX_ERR_INVALID: a NULL la / ret / handle / plans / table, la->struct_size != sizeof(mgx_lookahead), C or H below 1, gamma outside
+ * [0, 1] or NaN, end_soc on a layout without a battery, a handle that does not step in-place episodes.  MGX_ERR_UNSUPPORTED: what
+ * mgx_rollout_episodes refuses so (several modules of a kind, shards, device-counter mode) and a handle with
+ * mgx_set_forecast_noise set -- the lookahead reads the series rows themselves, which is what the oracle forecaster shows.
+ * MGX_ERR_RANGE: the counter stands outside its range.  mgx_set_final_obs, a forecast horizon in the observation and `done` as bit
+ * sets change nothing (neither rows nor done flags are written).  What needs no handle (la and its fields) is checked first.
+ * Nothing is launched when the call is refused.  An ADDITION to ABI 9 that leaves MGX_ABI_MINOR at 3: found by name (dlsym). */
+int mgx_lookahead_episodes(mgx_handle *h, const uint8_t *plans, const int32_t *table, int32_t n_actions,
+                           const mgx_lookahead *la, mgx_stream stream);
+
+/* Continuous plans: controls [C, H, A] (la->per_grid == 0) or [C, H, N, A] in the handle's action format
+ * (mgx_set_action_format); `normalized` as in mgx_step.  One launch of lookahead_step_k_episodes_kernel (+ the pick).  Refusals as
+ * mgx_lookahead_episodes (there is no table), with mgx_step_k_episodes in the place of mgx_rollout_episodes. */
+int mgx_lookahead_step_k_episodes(mgx_handle *h, const void *plans, int normalized,
+                                  const mgx_lookahead *la, mgx_stream stream);
+
+/* raise_errors=True(BaseMicrogridModule.__init__, base_module.py:40; as_source / as_sink, :213-224,265-270; _raise_error,
  * :79-93): the reference refuses a request a module cannot meet with a ValueError instead of clipping it.  mgx_step always
  * clips; mgx_check_step is its DRY RUN -- the same arithmetic on a register copy of the state, nothing stored, the counter
  * untouched -- and writes per grid the mask of requests the reference would refuse: bit 0 genset request outside

@@ -11,6 +11,7 @@ from .envs import (BatchedMicrogridEnv, DiscreteBatchedMicrogridEnv, DiscreteMic
                    MicrogridEnv)
 from .graph import GraphedRollout  # noqa: F401
 from .hetero import BucketedFleet, PerGridWindowEnv, PerGridWindowFleet  # noqa: F401
+from .mpc import ShootingMPC, lookahead_host, shooting_candidates  # noqa: F401
 from .policy import Exploration, GaussianSampling, MLPPolicy, Sampling, ValueHead, gae  # noqa: F401
 from .priority_list import get_priority_lists  # noqa: F401
 from .rbc import RuleBasedControl  # noqa: F401

@@ -31,9 +31,11 @@ UNITS = (
     ("mgx_policy_critic_episodes.hip", "MGX_EPISODE_PART", 2),          # ... and that one with a critic beside the actor,
     ("mgx_step_policy_gaussian_episodes.hip", "MGX_EPISODE_PART", 2),   # ... the continuous closed loop with a Gaussian head (+ critic),
     ("mgx_gae.hip", None, 1),                                           # the advantages of what such launches return (mgx_gae)
+    ("mgx_lookahead_episodes.hip", "MGX_EPISODE_PART", 2),              # what-if roll-outs of candidate plans, nothing committed
+    ("mgx_lookahead_step_episodes.hip", "MGX_EPISODE_PART", 2),         # ... and their continuous twin
 )
 # everything a built library is stamped with (source_hash): a file missing here would leave a stale libmgx.so looking current
-SOURCES = [os.path.join(_PKG, "csrc", f) for f in [u[0] for u in UNITS] + ["mgx_kernels.hpp", "mgx_core.hpp", "mgx_step_hot.hpp", "mgx_episode_loop.hpp", "mgx_episode_rows.hpp", "mgx_policy.hpp", "mgx_gae.hpp"]] + \
+SOURCES = [os.path.join(_PKG, "csrc", f) for f in [u[0] for u in UNITS] + ["mgx_kernels.hpp", "mgx_core.hpp", "mgx_step_hot.hpp", "mgx_episode_loop.hpp", "mgx_episode_rows.hpp", "mgx_policy.hpp", "mgx_gae.hpp", "mgx_lookahead.hpp"]] + \
           [os.path.join(_ROOT, "include", "mgx.h")]
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-fPIC"]
@@ -183,6 +185,14 @@ class Gaussian(C.Structure):
                 ("scale", C.c_void_p)]
 
 
+class Lookahead(C.Structure):
+    """mgx_lookahead (include/mgx.h): what ``mgx_lookahead_episodes`` / ``mgx_lookahead_step_k_episodes`` simulate and where the
+    results go (device arrays; every output but ``ret`` may be NULL)."""
+    _fields_ = [("struct_size", C.c_int32), ("C", C.c_int32), ("H", C.c_int32), ("per_grid", C.c_int32), ("gamma", C.c_double),
+                ("ret", C.c_void_p), ("steps", C.c_void_p), ("end_soc", C.c_void_p), ("best", C.c_void_p), ("best_ret", C.c_void_p),
+                ("first_action", C.c_void_p)]
+
+
 POLICY_MAX_HIDDEN = 64     # MGX_POLICY_MAX_HIDDEN
 POLICY_LDS_BYTES = 32768   # MGX_POLICY_LDS_BYTES
 
@@ -278,6 +288,8 @@ SYMBOLS = {
                                             + [C.c_void_p] * 10 + [C.POINTER(EpisodeStats), C.POINTER(EpisodeRows), C.c_void_p]),
     "mgx_gae": (C.c_int, [C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double,
                           C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mgx_lookahead_episodes": (C.c_int, [C.c_void_p, C.c_void_p, c_i32_p, C.c_int32, C.POINTER(Lookahead), C.c_void_p]),
+    "mgx_lookahead_step_k_episodes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(Lookahead), C.c_void_p]),
     "mgx_metrics": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "mgx_reset_windows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -8,6 +8,7 @@
 #include "mgx_episode_rows.hpp"
 #include "mgx_policy.hpp"
 #include "mgx_gae.hpp"
+#include "mgx_lookahead.hpp"
 
 #include <cstdarg>
 #include <cstdio>
@@ -84,6 +85,7 @@ struct mgx_handle {
     mgx_columns full_c;                      // the columns as given at create (a factorised batch steps over materialised
                                              // window buffers during a per-grid-window episode: k.c.base_load is NULL then)
     int32_t full_T, full_final, full_initial, full_window_lo, full_window_hi;
+    bool forecast_noise_set;                 // mgx_set_forecast_noise was called (whatever seed): the what-if launches plan on the rows themselves
 };
 
 namespace {
@@ -1073,6 +1075,7 @@ int mgx_set_forecast_noise(mgx_handle *h, uint64_t seed, int increase_uncertaint
     if (!h) return fail(MGX_ERR_INVALID, "mgx_set_forecast_noise: NULL handle");
     h->k.noise_seed = seed;
     h->k.noise_increase = increase_uncertainty ? 1 : 0;
+    h->forecast_noise_set = true;
     return MGX_OK;
 }
 
@@ -2114,6 +2117,138 @@ int mgx_step_k_episodes_rows(mgx_handle *h, const void *actions, int32_t K, int 
     if (!rows || (!rows->obs && !rows->final_obs))
         return mgx_step_k_episodes(h, actions, K, normalized, reward, done, soc_trace, status_trace, stats, stream);
     return step_k_episodes_impl(h, actions, K, normalized, reward, done, soc_trace, status_trace, stats, rows, stream, "mgx_step_k_episodes_rows");
+}
+
+// ---- the what-if launches (mgx_lookahead.hpp): candidate plans simulated from the current state, nothing committed ----
+namespace {
+// The pick over ret [C, N], one lane per grid (a coalesced load per candidate): the first maximum by the rule of include/mgx.h,
+// step 0 of its plan, and the steps every candidate of the grid counted.  `plans`: the launch's own (ids, or controls of `esize`
+// bytes an element, A to a grid).
+struct LookaheadPick {
+    int64_t N;
+    int32_t C, H, t0;
+    bool per_grid;
+    int32_t A, esize;              // elements of a step per grid, bytes of an element (ids: 1, 1)
+    const double *ret;
+    const int32_t *ep_final;
+    const void *plans;
+    int32_t *steps, *best;
+    double *best_ret;
+    void *first_action;
+};
+
+// step 0 of plan b for grid i: row b * H of [C, H, N, A] / [C, H, A], copied element by element in its own width
+__device__ __forceinline__ void lookahead_copy_first(const LookaheadPick &q, int64_t i, int32_t b)
+{
+    const int64_t src = (int64_t)b * q.H * (q.per_grid ? q.N : 1) * q.A + (q.per_grid ? i * q.A : 0), dst = i * q.A;
+    for (int32_t j = 0; j < q.A; j++) {
+        if (q.esize == 1) ((uint8_t *)q.first_action)[dst + j] = ((const uint8_t *)q.plans)[src + j];
+        else if (q.esize == 4) ((uint32_t *)q.first_action)[dst + j] = ((const uint32_t *)q.plans)[src + j];
+        else ((uint64_t *)q.first_action)[dst + j] = ((const uint64_t *)q.plans)[src + j];
+    }
+}
+
+__global__ __launch_bounds__(BLOCK) void lookahead_pick_kernel(const LookaheadPick q)
+{
+    const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= q.N) return;
+    if (q.steps) q.steps[i] = lookahead_steps(q.t0, q.ep_final[i], q.H);
+    if (!q.best && !q.best_ret && !q.first_action) return;
+    int32_t b = 0;
+    double bv = q.ret[i];
+    for (int32_t c = 1; c < q.C; c++) {
+        const double v = q.ret[(int64_t)c * q.N + i];
+        if (v > bv) { bv = v; b = c; }
+    }
+    if (q.best) q.best[i] = b;
+    if (q.best_ret) q.best_ret[i] = bv;
+    if (q.first_action) lookahead_copy_first(q, i, b);
+}
+
+// what both calls check of `la` before they look at the handle
+int lookahead_struct_refusal(const mgx_lookahead *la, const char *fn)
+{
+    if (!la) return fail(MGX_ERR_INVALID, "%s: NULL la", fn);
+    if (la->struct_size != (int32_t)sizeof(mgx_lookahead))
+        return fail(MGX_ERR_INVALID, "%s: la->struct_size is %d, sizeof(mgx_lookahead) is %d", fn, la->struct_size, (int)sizeof(mgx_lookahead));
+    if (!la->ret) return fail(MGX_ERR_INVALID, "%s: NULL la->ret", fn);
+    if (la->C < 1 || la->H < 1) return fail(MGX_ERR_INVALID, "%s: %d candidates over a horizon of %d (both must be positive)", fn, la->C, la->H);
+    if (!(la->gamma >= 0.0 && la->gamma <= 1.0)) return fail(MGX_ERR_INVALID, "%s: gamma = %g is outside [0, 1]", fn, la->gamma);
+    return MGX_OK;
+}
+
+// Every refusal (what needs no handle first), and the launch descriptor but for the plans, which the call owns
+int prepare_lookahead(mgx_handle *h, const void *plans, const mgx_lookahead *la, mgx_stream stream, const char *fn, LookaheadLaunch &L)
+{
+    if (int rc = lookahead_struct_refusal(la, fn)) return rc;
+    if (!h || !plans) return fail(MGX_ERR_INVALID, "%s: NULL argument", fn);
+    if (h->multi) return fail(MGX_ERR_UNSUPPORTED, "%s: needs exactly one module of every kind per grid", fn);
+    if (h->n_shards > 1) return fail(MGX_ERR_UNSUPPORTED, "%s: not offered while the handle steps in shards", fn);
+    if (dev_counter(h)) return fail(MGX_ERR_UNSUPPORTED, "%s: not offered in device-counter mode", fn);
+    if (!h->inplace || !h->k.ep_off || !h->k.ep_final)
+        return fail(MGX_ERR_INVALID, "%s: the handle is not stepping in-place episodes (mgx_reset_episodes); lock-step episodes: "
+                                     "in-place episodes of start 0 and full length", fn);
+    if (h->forecast_noise_set || noisy(h->k.c))
+        return fail(MGX_ERR_UNSUPPORTED, "%s: the handle shows noisy forecasts (mgx_set_forecast_noise); the lookahead plans on the series rows themselves", fn);
+    if (la->end_soc && !(h->flags & F_BATTERY)) return fail(MGX_ERR_INVALID, "%s: end_soc on a layout without a battery", fn);
+    if (h->t < 0 || h->t >= step_limit(h) || (int64_t)h->t + la->H > INT32_MAX)
+        return fail(MGX_ERR_RANGE, "%s: step %d (horizon %d) is outside the counter's range", fn, h->t, la->H);
+    L.flags = h->flags;
+    L.src = factorised(h->k.c) ? EP_SRC_FACT : (h->k.pm_pitch ? EP_SRC_GRID_MAJOR : EP_SRC_GATHER);
+    if (L.src == EP_SRC_FACT && !h->k.pm_pitch)
+        return fail(MGX_ERR_INVALID, "%s: the handle holds no profile-major base tables", fn);
+    L.gpb = fused_grids_per_block(h, h->k.N);
+    L.blocks = (unsigned)((h->k.N + L.gpb - 1) / L.gpb);
+    L.stream = (hipStream_t)stream;
+    L.k = &h->k;
+    L.per_grid = la->per_grid != 0;
+    L.t = h->t; L.C = la->C; L.H = la->H; L.gamma = la->gamma;
+    L.ret = la->ret; L.end_soc = la->end_soc;
+    return MGX_OK;
+}
+
+// behind the launch: its error, then the pick where something asks for it.  The counter stays.
+int finish_lookahead(mgx_handle *h, const LookaheadLaunch &L, bool was_launched, const mgx_lookahead *la, const void *plans, bool discrete,
+                     const char *what, const char *fn)
+{
+    if (!was_launched) return fail(MGX_ERR_UNSUPPORTED, "%s: no kernel for layout flags %d", fn, h->flags);
+    if (int rc = launched(what)) return rc;
+    if (!la->steps && !la->best && !la->best_ret && !la->first_action) return MGX_OK;
+    LookaheadPick q;
+    q.N = h->k.N; q.C = L.C; q.H = L.H; q.t0 = L.t;
+    q.per_grid = L.per_grid;
+    q.A = discrete ? 1 : h->action_dim; q.esize = discrete ? 1 : (h->k.act_f32 ? 4 : 8);
+    q.ret = L.ret; q.ep_final = h->k.ep_final; q.plans = plans;
+    q.steps = la->steps; q.best = la->best; q.best_ret = la->best_ret; q.first_action = la->first_action;
+    lookahead_pick_kernel<<<(unsigned)((q.N + BLOCK - 1) / BLOCK), BLOCK, 0, L.stream>>>(q);
+    return launched("lookahead_pick_kernel launch");
+}
+}  // namespace
+
+int mgx_lookahead_episodes(mgx_handle *h, const uint8_t *plans, const int32_t *table, int32_t n_actions, const mgx_lookahead *la,
+                           mgx_stream stream)
+{
+    g_err[0] = 0;
+    const char *fn = "mgx_lookahead_episodes";
+    LookaheadLaunch L{};
+    if (int rc = prepare_lookahead(h, plans, la, stream, fn, L)) return rc;
+    if (!table) return fail(MGX_ERR_INVALID, "%s: NULL argument", fn);
+    PLWords tab;
+    if (int rc = encode_table(h, table, n_actions, &tab, fn)) return rc;
+    L.tab = &tab; L.ids = plans;
+    const bool was_launched = launch_lookahead_episodes_p0(L) || launch_lookahead_episodes_p1(L);
+    return finish_lookahead(h, L, was_launched, la, plans, true, "lookahead_episodes_kernel launch", fn);
+}
+
+int mgx_lookahead_step_k_episodes(mgx_handle *h, const void *plans, int normalized, const mgx_lookahead *la, mgx_stream stream)
+{
+    g_err[0] = 0;
+    const char *fn = "mgx_lookahead_step_k_episodes";
+    LookaheadLaunch L{};
+    if (int rc = prepare_lookahead(h, plans, la, stream, fn, L)) return rc;
+    L.actions = plans; L.act_f32 = h->k.act_f32 != 0; L.normalized = normalized;
+    const bool was_launched = launch_lookahead_step_k_episodes_p0(L) || launch_lookahead_step_k_episodes_p1(L);
+    return finish_lookahead(h, L, was_launched, la, plans, false, "lookahead_step_k_episodes_kernel launch", fn);
 }
 
 // The closed-loop launches (mgx_policy.hpp).  What they check of the policy before prepare_episode_launch: what needs no handle

@@ -782,6 +782,59 @@ class StepEngine:
         return self._launch_episodes("mgx_step_k_episodes", (_ptr(actions), K, 1 if normalized else 0), K, res, (r, d, s, g), st, out,
                                      obs, final_obs)
 
+    def _lookahead(self, symbol, lead, plans, C_, H, per_grid, first_shape, gamma, end_soc, pick, out):
+        """What the two what-if calls share: the ``mgx_lookahead`` struct over outputs taken from ``out`` or allocated, the call --
+        which moves neither the state nor the counter -- and the result dict."""
+        out = out or {}
+        N, res = self.N, {}
+        la = _lib.Lookahead()
+        la.struct_size = C.sizeof(_lib.Lookahead)
+        la.C, la.H, la.per_grid, la.gamma = int(C_), int(H), int(per_grid), float(gamma)
+        for name, want, shape, dtype in (
+                ("ret", True, (C_, N), torch.float64),
+                ("steps", True, (N,), torch.int32),
+                ("end_soc", end_soc, (C_, N), torch.float64),
+                ("best", pick, (N,), torch.int32),
+                ("best_ret", pick, (N,), torch.float64),
+                ("first_action", pick, first_shape, plans.dtype)):
+            if not want:
+                continue
+            t = out.get(name)
+            if t is None:
+                t = self._empty(*shape, dtype=dtype)
+            elif t.dtype != dtype or t.device != self.device or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
+                raise ValueError(f"out[{name!r}] must be a contiguous {dtype} tensor {list(shape)} on {self.device}")
+            res[name] = t
+            setattr(la, name, _ptr(t))
+        self._call(getattr(self._lib, symbol), _ptr(plans), *lead, C.byref(la))
+        return res
+
+    def lookahead_episodes(self, plans, table, gamma=1.0, end_soc=False, pick=True, out=None):
+        """What every grid would earn over the next H steps under each of C candidate plans of priority-list ids, in ONE launch that
+        commits none of them (``mgx_lookahead_episodes``; a handle in in-place episodes): ``plans`` uint8 ``[C, H]`` (shared by all
+        grids) or ``[C, H, N]`` (a plan per grid).  Returns ``ret`` float64 ``[C, N]`` (the return discounted by ``gamma``, counted
+        up to the end of each grid's running episode and no further), ``steps`` int32 ``[N]`` (the steps counted), with
+        ``end_soc=True`` ``end_soc`` ``[C, N]`` (the SoC after the last counted step) and with ``pick=True`` ``best`` int32 ``[N]`` (the
+        first candidate of maximal return), ``best_ret`` ``[N]`` and ``first_action`` uint8 ``[N]`` (step 0 of that plan).  State,
+        counter, episodes and statistics stay as they are."""
+        if not torch.is_tensor(plans) or plans.dtype != torch.uint8 or plans.device != self.device or not plans.is_contiguous() \
+                or plans.dim() not in (2, 3) or (plans.dim() == 3 and plans.shape[2] != self.N) or plans.numel() == 0:
+            raise ValueError(f"plans must be a contiguous uint8 tensor [C, H] or [C, H, {self.N}] on {self.device}")
+        tptr, n_lists = self._table_ptr(table)
+        return self._lookahead("mgx_lookahead_episodes", (tptr, n_lists), plans, plans.shape[0], plans.shape[1], plans.dim() == 3,
+                               (self.N,), gamma, end_soc, pick, out)
+
+    def lookahead_step_k_episodes(self, plans, normalized=True, gamma=1.0, end_soc=False, pick=True, out=None):
+        """``lookahead_episodes`` for continuous controls (``mgx_lookahead_step_k_episodes``): ``plans`` ``[C, H, A]`` (shared) or
+        ``[C, H, N, A]`` (a plan per grid) in ``action_dtype``, stepped as ``step(plans[c, k], normalized)`` would; ``first_action``
+        is ``[N, A]`` in ``action_dtype``.  Everything else as ``lookahead_episodes``."""
+        A = self.action_dim
+        if not torch.is_tensor(plans) or plans.dtype != self.action_dtype or plans.device != self.device or not plans.is_contiguous() \
+                or plans.dim() not in (3, 4) or plans.shape[-1] != A or (plans.dim() == 4 and plans.shape[2] != self.N) or plans.numel() == 0:
+            raise ValueError(f"plans must be a contiguous {self.action_dtype} tensor [C, H, {A}] or [C, H, {self.N}, {A}] on {self.device}")
+        return self._lookahead("mgx_lookahead_step_k_episodes", (1 if normalized else 0,), plans, plans.shape[0], plans.shape[1],
+                               plans.dim() == 4, (self.N, A), gamma, end_soc, pick, out)
+
     def _launch_policy_episodes(self, symbol, policy, exploration, lead, K, res, bufs, taken, st, out, obs, final_obs, sampling=None,
                                 probs=None, critic=None, values=(None, None, None)):
         """The tail of the closed-loop episode launches: ``symbol`` -- with an ``exploration`` its exploring form, which takes the

@@ -788,6 +788,48 @@ class PerGridWindowEnv:
         return self._launch_fused(lambda **kw: e.step_k_episodes(actions, normalized=normalized, **kw), observations, final_observations,
                                   reward=reward, done=done, soc_trace=soc_trace, status_trace=status_trace, out=out)
 
+    def _lookahead_refusal(self):
+        """Why ``lookahead`` is not offered on this env (None: it is): what ``_fused_refusal`` says of the env's episodes -- the
+        launch reads in-place episodes as ``rollout`` / ``step_k`` do -- without what concerns the outputs of a step (it takes none)."""
+        if not self.auto_reset:
+            return "auto_reset=False: equal-length windows step in lock-step (auto_reset=True runs the in-place episodes it reads)"
+        if self.generator is not None:
+            return "a torch generator: its draws are made on the host between steps"
+        if self.full.layout.multi:
+            return "several modules of a kind per grid: single steps (the fused kernel holds one module of every kind)"
+        if not (self.native and self._device_draws):
+            return "native=False: the lookahead reads in-place episodes"
+        if self.full.forecast_noise is not None or any(self.full.cols.get(k) is not None
+                                                       for k in ("load_noise_std", "pv_noise_std", "grid_noise_std")):
+            return "noisy forecasts: the lookahead plans on the series rows themselves (the oracle forecaster's)"
+        return None
+
+    def lookahead(self, plans, gamma=1.0, normalized=True, end_soc=False, pick=True, out=None):
+        """What every grid would earn over the next H steps under each of C candidate plans, in ONE launch that takes none of those
+        steps (``mgx_lookahead_episodes`` for ``discrete=True``, ``mgx_lookahead_step_k_episodes`` otherwise; ``auto_reset=True`` with
+        device draws and one module of every kind) -- the primitive of planning by simulation (``pymgrid_amd.ShootingMPC``; random
+        shooting, CEM and tree-search roll-outs are loops over it).  ``plans``: priority-list ids ``[C, H]`` (shared by all grids) or
+        ``[C, H, N]`` (a plan per grid); or controls ``[C, H, A]`` / ``[C, H, N, A]`` in the env's ``action_dtype``, stepped as
+        ``step(plans[c, k], normalized)``.  Every candidate starts from the grid's current state and row and is counted to the end
+        of the grid's running episode at the most -- the step that ends it included, nothing of the episode a restart would draw.
+        Returns ``ret`` ``[C, N]`` (the return discounted by ``gamma``, ``pymgrid_amd.lookahead_host``'s rule bit for bit),
+        ``steps`` ``[N]`` (the steps counted), with ``pick=True`` ``best`` ``[N]`` (the first candidate of maximal return),
+        ``best_ret`` ``[N]`` and ``first_action`` (step 0 of that plan: ids uint8 ``[N]``, or controls ``[N, A]``; ``step`` takes either),
+        with ``end_soc=True`` ``end_soc`` ``[C, N]`` (the SoC after the last counted step, a terminal value's input).  Nothing moves:
+        state, episodes, counters and ``episode_stats`` stay, the next ``step`` is the one it would have been.  ``out=``: your own
+        tensors by those names."""
+        why = self._lookahead_refusal()
+        if why is not None:
+            raise ValueError(f"PerGridWindowEnv.lookahead is not offered with {why}")
+        if self.starts is None:
+            raise RuntimeError("lookahead() before reset()")
+        env = self.env
+        e = env.engine
+        if isinstance(env, DiscreteBatchedMicrogridEnv):
+            plans = _as_ids(plans, self.full.device, dtype=torch.uint8)
+            return e.lookahead_episodes(plans, env._table, gamma=gamma, end_soc=end_soc, pick=pick, out=out)
+        return e.lookahead_step_k_episodes(plans, normalized=normalized, gamma=gamma, end_soc=end_soc, pick=pick, out=out)
+
     def _check_policy(self, kind, policy, head, n_out, what):
         """What ``rollout_policy`` / ``step_k_policy`` refuse on top of ``rollout`` / ``step_k`` with rows: a policy of the wrong head
         or the wrong size."""

@@ -1,0 +1,499 @@
+"""What-if roll-outs of candidate plans (mgx_lookahead_episodes / mgx_lookahead_step_k_episodes, StepEngine.lookahead_episodes /
+lookahead_step_k_episodes, PerGridWindowEnv.lookahead, ShootingMPC): C plans per grid simulated H steps ahead in one launch that
+commits none of them == C twin envs rolled out with ``rollout`` / ``step_k`` and reduced by ``lookahead_host`` -- returns, steps, pick,
+first action and end SoC bit for bit (torch.equal on fp64: same operations, same order) -- and afterwards nothing has moved."""
+import os
+
+import numpy as np
+import pytest
+import torch
+
+SOAK = int(os.environ.get("MGX_FUZZ_SEED", "0"))
+N, T, C_ = 333, 150, 5            # two workgroups, the last wave partly empty; candidate 3 is a copy of candidate 1 (ties on every grid)
+F64 = torch.float64
+GBG, GB, BG = "genset+battery+grid", "genset+battery", "battery+grid"      # the three architectures of test_rollout_episodes.CASES
+
+# (arch, series, trajectory_length, H, shaper, per_grid, gamma, prefix, forecast horizon of the observation)
+# H = 3 is below both ring depths (4 / 8), H = 9 above the deeper one and a multiple of neither; length 6: every episode ends inside
+# H = 9 (after the prefix of 5 every grid stands on its last step), None: random lengths, lanes of a wave stop at different steps
+CASES = [
+    (GBG, "factorised", 6, 9, False, False, 1.0, 0, 0),
+    (GBG, "materialised", None, 9, True, True, 0.9, 5, 6),
+    (GBG, "gather", None, 3, False, True, 1.0, 5, 0),
+    (GBG, "factorised", None, 9, True, True, 0.9, 0, 0),
+    (GB, "factorised", None, 9, True, False, 0.9, 5, 0),
+    (GB, "materialised", 6, 3, False, True, 1.0, 0, 6),
+    (GB, "gather", 6, 9, True, False, 0.9, 5, 0),
+    (BG, "factorised", None, 1, False, True, 0.9, 0, 0),
+    (BG, "materialised", None, 9, False, False, 1.0, 5, 0),
+    (BG, "gather", 6, 1, True, False, 1.0, 5, 0),
+]
+# the continuous launch: the same cases, each with an action format and a reading of the controls
+FORMATS = [(torch.float64, True), (torch.float32, False), (torch.float64, False), (torch.float32, True)]
+CONT_CASES = [c + FORMATS[j % 4] for j, c in enumerate(CASES)]
+
+
+def _batch(device, arch, series, H, n=N, t=T, seed=17):
+    from pymgrid_amd.generator import generate
+    return generate(n, n_steps=t, seed=seed + 1000 * SOAK, arch=arch, device=device, horizon=H, mixed_timers=True,
+                    series="factorised" if series == "factorised" else "materialised")
+
+
+def _shaper(on):
+    from pymgrid_amd import BatteryDischargeShaper
+    return BatteryDischargeShaper() if on else None
+
+
+def _snapshot(pe):
+    cols = pe.env.batch.cols
+    snap = {name: cols[name].clone() for name in ("charge", "soc", "gen_status") if name in cols}
+    snap["t"] = pe.env.engine._lib.mgx_current_step(pe.env.engine._h)
+    snap["starts"] = pe.starts.clone()
+    snap["lengths"] = None if pe.lengths is None else pe.lengths.clone()
+    snap["current_steps"] = pe.env.current_steps.clone()
+    for name, v in (pe.episode_stats or {}).items():
+        snap["stat_" + name] = v.clone()
+    return snap
+
+
+def _untouched(pe, snap):
+    now = _snapshot(pe)
+    assert now.keys() == snap.keys()
+    for name, v in snap.items():
+        assert torch.equal(now[name], v) if torch.is_tensor(v) else now[name] == v, name
+
+
+class _Gather:
+    """The ``grid_major_copy`` tunable off for series == "gather" (the rows read where they lie), restored afterwards."""
+
+    def __init__(self, series):
+        self.series = series
+
+    def __enter__(self):
+        from pymgrid_amd import _lib
+        self.old = _lib.get_tunable("grid_major_copy")[0]
+        if self.series == "gather":
+            _lib.set_tunable("grid_major_copy", 0)
+
+    def __exit__(self, *exc):
+        from pymgrid_amd import _lib
+        _lib.set_tunable("grid_major_copy", self.old)
+
+
+def _envs(device, arch, series, length, shaper, obs_h, discrete, count, **kw):
+    from pymgrid_amd.hetero import PerGridWindowEnv
+    envs = [PerGridWindowEnv(_batch(device, arch, series, obs_h), trajectory_length=length, discrete=discrete, auto_reset=True,
+                             seed=23 + SOAK, reward_shaping_func=_shaper(shaper), **kw) for _ in range(count)]
+    for e in envs:
+        torch.manual_seed(41 + SOAK)                   # the same first draw
+        e.reset()
+    return envs
+
+
+def _plan_of(plans, c, per_grid, discrete):
+    """Candidate c's plan as the twin's launch takes it: ids [H, N] / controls [H, N, A]."""
+    p = plans[c]
+    if per_grid:
+        return p.contiguous()
+    return (p[:, None].expand(p.shape[0], N) if discrete else p[:, None, :].expand(p.shape[0], N, p.shape[1])).contiguous()
+
+
+def _step_of(plans, best, k, per_grid):
+    """Step k of plan best[i] for every grid i."""
+    b = best.long()
+    return plans[b, k, torch.arange(N, device=plans.device)] if per_grid else plans[b, k]
+
+
+def _lookahead_equals_twin_rollouts(device, arch, series, length, H, shaper, per_grid, gamma, prefix, obs_h, discrete,
+                                    dtype=torch.float64, normalized=True):
+    from pymgrid_amd import lookahead_host
+    with _Gather(series):
+        kw = {} if discrete else dict(action_dtype=dtype)
+        # the env under test, a twin per candidate and one twin nobody looks ahead on
+        envs = _envs(device, arch, series, length, shaper, obs_h, discrete, C_ + 2, **kw)
+        la, twins, plain = envs[0], envs[1:C_ + 1], envs[C_ + 1]
+        g = torch.Generator(device=device); g.manual_seed(3 + SOAK)
+        e = la.env.engine
+        A = e.action_dim
+        scale = 1.0 if normalized else 30.0
+        n_act = la.env.action_space.n if discrete else None
+
+        def draw(*lead):                                   # ids [*lead, N] / controls [*lead, N, A]
+            if discrete:
+                return torch.randint(0, n_act, (*lead, N), device=device, generator=g).to(torch.uint8)
+            return (torch.rand((*lead, N, A), device=device, generator=g, dtype=F64) * scale).to(dtype)
+        if prefix:                                         # the same steps on all of them, in one launch (so the statistics exist)
+            acts = draw(prefix)
+            for pe in envs:
+                pe.rollout(acts) if discrete else pe.step_k(acts, normalized=normalized)
+        if per_grid:
+            plans = draw(C_, H)
+        elif discrete:
+            plans = torch.randint(0, n_act, (C_, H), device=device, generator=g).to(torch.uint8)
+        else:
+            plans = (torch.rand((C_, H, A), device=device, generator=g, dtype=F64) * scale).to(dtype)
+        plans[3] = plans[1]
+        plans = plans.contiguous()
+
+        snap = _snapshot(la)
+        out = la.lookahead(plans, gamma=gamma, normalized=normalized, end_soc=True)
+        _untouched(la, snap)
+
+        rewards, socs, dones = [], [], []
+        for c, tw in enumerate(twins):
+            p = _plan_of(plans, c, per_grid, discrete)
+            r = tw.rollout(p, reward=True, done=True, soc_trace=True) if discrete else \
+                tw.step_k(p, normalized=normalized, reward=True, done=True, soc_trace=True)
+            rewards.append(r["reward"]); socs.append(r["soc_trace"]); dones.append(r["done"])
+        for d in dones[1:]:
+            assert torch.equal(d, dones[0])                # the end of an episode depends on the grid alone
+        ref = lookahead_host(torch.stack(rewards), dones[0], gamma)
+        ar = torch.arange(N, device=device)
+        assert set(out) == {"ret", "steps", "best", "best_ret", "first_action", "end_soc"}
+        assert out["ret"].shape == (C_, N) and torch.equal(out["ret"], ref["ret"])
+        assert out["steps"].dtype == torch.int32 and torch.equal(out["steps"], ref["steps"])
+        assert out["best"].dtype == torch.int32 and torch.equal(out["best"], ref["best"])
+        assert torch.equal(out["best_ret"], ref["best_ret"])
+        assert torch.equal(out["end_soc"], torch.stack([s[ref["last"], ar] for s in socs]))
+        first = _step_of(plans, ref["best"], 0, per_grid)
+        assert out["first_action"].dtype == plans.dtype and torch.equal(out["first_action"], first)
+        # the test's own input: ties on every grid and the first of them wins; the steps differ where the case says so
+        assert torch.equal(out["ret"][1], out["ret"][3]) and not bool((out["best"] == 3).any())
+        steps = out["steps"]
+        assert int(steps.min()) >= 1 and int(steps.max()) <= H
+        if length == 6:
+            assert bool((steps == min(H, 1 if prefix else 6)).all())
+        elif H == 9:
+            assert len(steps.unique()) > 2 and int(steps.max()) == H
+        # pick=False: the return launch alone, the same returns
+        lean = la.lookahead(plans, gamma=gamma, normalized=normalized, pick=False)
+        assert set(lean) == {"ret", "steps"} and torch.equal(lean["ret"], out["ret"]) and torch.equal(lean["steps"], steps)
+        _untouched(la, snap)
+
+        # nothing moved: the next step is the one of a twin nobody looked ahead on -- and it is step 0 of the best plan; going on
+        # with the rest of that plan for `steps` steps collects best_ret
+        acc, w = torch.zeros(N, dtype=F64, device=device), 1.0
+        for k in range(int(steps.max())):
+            a = _step_of(plans, out["best"], k, per_grid)
+            if k == 0:
+                a = out["first_action"]
+            a = a.to(torch.int32) if discrete else a.contiguous()
+            step = (lambda pe: pe.step(a)) if discrete else (lambda pe: pe.step(a, normalized=normalized))
+            o1, r1, d1, _ = step(la)
+            if k == 0:
+                o2, r2, d2, _ = step(plain)
+                assert torch.equal(o1, o2) and torch.equal(r1, r2) and torch.equal(d1, d2)
+            acc = torch.where(k < steps, acc + w * r1, acc)
+            w = w * gamma
+        assert torch.equal(acc, out["best_ret"])
+        for pe in envs:
+            pe.env.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("arch,series,length,H,shaper,per_grid,gamma,prefix,obs_h", CASES)
+def test_discrete_lookahead_equals_twin_rollouts(arch, series, length, H, shaper, per_grid, gamma, prefix, obs_h, device):
+    _lookahead_equals_twin_rollouts(device, arch, series, length, H, shaper, per_grid, gamma, prefix, obs_h, True)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("arch,series,length,H,shaper,per_grid,gamma,prefix,obs_h,dtype,normalized", CONT_CASES)
+def test_continuous_lookahead_equals_twin_step_k(arch, series, length, H, shaper, per_grid, gamma, prefix, obs_h, dtype, normalized, device):
+    _lookahead_equals_twin_rollouts(device, arch, series, length, H, shaper, per_grid, gamma, prefix, obs_h, False, dtype, normalized)
+
+
+def test_cases_cover_every_value_of_every_axis():
+    """The pruned product keeps every value of every axis for both kernels (the continuous cases are the discrete ones + a format)."""
+    for j, values in enumerate(([GBG, GB, BG], ["factorised", "materialised", "gather"], [6, None], [1, 3, 9], [False, True],
+                                [False, True], [1.0, 0.9], [0, 5], [0, 6])):
+        assert {c[j] for c in CASES} == set(values), j
+    assert {c[9:] for c in CONT_CASES} == set(FORMATS)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("discrete", [True, False])
+def test_grids_on_their_last_step_without_auto_reset(discrete, device):
+    """In-place episodes without set_auto_reset, every grid on (or behind) its last step: one step is counted, ``ret`` is that step's
+    reward -- for every horizon, and ids outside the table are list 0."""
+    from pymgrid_amd import BatchedMicrogridEnv, DiscreteBatchedMicrogridEnv
+    n, H = 333, 4
+    cls = DiscreteBatchedMicrogridEnv if discrete else BatchedMicrogridEnv
+    envs = [cls(_batch(device, GBG, "factorised", 0, n=n, t=60)) for _ in range(2)]
+    g = torch.Generator(device=device); g.manual_seed(5 + SOAK)
+    starts = torch.randint(0, 40, (n,), device=device, generator=g).to(torch.int32)
+    lengths = torch.randint(1, 4, (n,), device=device, generator=g).to(torch.int32)
+    for env in envs:
+        env.reset_windows(starts, lengths, max_length=8, rolling="inplace")
+    la, twin = envs
+    e = la.engine
+    if discrete:
+        move = torch.zeros(2, n, dtype=torch.uint8, device=device)
+        for env in envs:                                       # two steps on: lengths 1 and 2 are behind their end, 3 stands on it
+            env.engine.rollout_episodes(move, env._table, 2)
+        plans = torch.randint(0, la.action_space.n, (3, H), device=device, generator=g).to(torch.uint8)
+        plans[2] = plans[0]
+        plans[2, 0] = 0
+        plans[0, 0] = 250                                      # (outside the table: list 0, what candidate 2 names)
+        out = e.lookahead_episodes(plans, la._table, gamma=0.9)
+        ref = twin.engine.rollout_episodes(plans[1, :1, None].expand(1, n).contiguous(), twin._table, 1, reward=True)["reward"][0]
+        assert torch.equal(out["ret"][0], out["ret"][2])
+    else:
+        move = torch.rand(2, n, e.action_dim, device=device, generator=g, dtype=F64)
+        for env in envs:
+            env.engine.step_k_episodes(move)
+        plans = torch.rand(3, H, e.action_dim, device=device, generator=g, dtype=F64)
+        out = e.lookahead_step_k_episodes(plans, gamma=0.9)
+        ref = twin.engine.step_k_episodes(plans[1, :1, None, :].expand(1, n, e.action_dim).contiguous(), reward=True)["reward"][0]
+    assert bool((out["steps"] == 1).all())
+    assert torch.equal(out["ret"][1], ref)
+    assert e.current_step == 2
+    for env in envs:
+        env.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("discrete", [True, False])
+def test_every_layout(discrete, device):
+    """The kernels of all ten layouts (tests/layouts.py), engine to engine: lookahead == the twins' launches over the same plans."""
+    from layouts import LAYOUTS, carve
+    from pymgrid_amd import BatchedMicrogridEnv, DiscreteBatchedMicrogridEnv, lookahead_host
+    n, H = 333, 9
+    full = _batch(device, GBG, "factorised", 0, n=n, t=60)
+    g = torch.Generator(device=device); g.manual_seed(7 + SOAK)
+    starts = torch.randint(0, 30, (n,), device=device, generator=g).to(torch.int32)
+    lengths = torch.randint(1, 14, (n,), device=device, generator=g).to(torch.int32)
+    ar = torch.arange(n, device=device)
+    cls = DiscreteBatchedMicrogridEnv if discrete else BatchedMicrogridEnv
+    for flags in LAYOUTS:
+        if not discrete and not flags & 7:
+            continue                                           # no controllable module: no control to plan (discrete: the one empty list)
+        envs = [cls(carve(full, flags)) for _ in range(3)]
+        for env in envs:
+            env.reset_windows(starts, lengths, max_length=13, rolling="inplace")
+        la, twins = envs[0], envs[1:]
+        e = la.engine
+        soc = bool(flags & 2)
+        if discrete:
+            plans = torch.randint(0, la.action_space.n, (2, H, n), device=device, generator=g).to(torch.uint8)
+            out = e.lookahead_episodes(plans, la._table, gamma=0.9, end_soc=soc)
+            refs = [tw.engine.rollout_episodes(plans[c], tw._table, H, reward=True, done=True, soc_trace=True) for c, tw in enumerate(twins)]
+        else:
+            plans = torch.rand((2, H, n, e.action_dim), device=device, generator=g, dtype=F64)
+            out = e.lookahead_step_k_episodes(plans, gamma=0.9, end_soc=soc)
+            refs = [tw.engine.step_k_episodes(plans[c], reward=True, done=True, soc_trace=True) for c, tw in enumerate(twins)]
+        ref = lookahead_host(torch.stack([r["reward"] for r in refs]), refs[0]["done"], 0.9)
+        for name in ("ret", "steps", "best", "best_ret"):
+            assert torch.equal(out[name], ref[name]), (flags, name)
+        assert torch.equal(out["first_action"], plans[ref["best"].long(), 0, ar]), flags
+        if soc:
+            assert torch.equal(out["end_soc"], torch.stack([r["soc_trace"][ref["last"], ar] for r in refs])), flags
+        assert len(out["steps"].unique()) > 2 and e.current_step == 0
+        for env in envs:
+            env.close()
+
+
+@pytest.mark.gpu
+def test_refusals_of_the_c_abi(device):
+    """Both entry points refuse -- nothing launched, the state and the caller's buffers untouched, the text naming the call -- a
+    lock-step handle (MGX_ERR_INVALID), shards, forecast noise, several modules of a kind (MGX_ERR_UNSUPPORTED), end_soc without a
+    battery, C or H below 1 and a gamma outside [0, 1] (MGX_ERR_INVALID)."""
+    import ctypes as C
+    from pymgrid_amd import BatchedMicrogridEnv, DiscreteBatchedMicrogridEnv, MgxError, _lib
+    from pymgrid_amd.generator import generate, widen
+    from layouts import carve
+    n, H = 300, 4
+    nan = float("nan")
+
+    def snapshot(env):
+        cols = env.batch.cols
+        snap = {name: cols[name].clone() for name in ("charge", "soc", "gen_status") if name in cols}
+        snap["t"] = env.engine._lib.mgx_current_step(env.engine._h)
+        return snap
+
+    def refused(env, code, **kw):
+        e = env.engine
+        disc = isinstance(env, DiscreteBatchedMicrogridEnv)
+        plans = torch.zeros((2, H), dtype=torch.uint8, device=device) if disc else torch.zeros((2, H, e.action_dim), dtype=F64, device=device)
+        ret = torch.full((2, n), nan, dtype=F64, device=device)
+        snap = snapshot(env)
+        with pytest.raises(MgxError) as ei:
+            if disc:
+                e.lookahead_episodes(plans, env._table if env._table is not None else np.zeros((1, 3, 2), dtype=np.int32), out={"ret": ret}, **kw)
+            else:
+                e.lookahead_step_k_episodes(plans, out={"ret": ret}, **kw)
+        assert ei.value.code == code, ei.value
+        assert ("mgx_lookahead_episodes" if disc else "mgx_lookahead_step_k_episodes") in str(ei.value)
+        assert bool(ret.isnan().all())
+        now = snapshot(env)
+        for name, v in snap.items():
+            assert torch.equal(now[name], v) if torch.is_tensor(v) else now[name] == v, name
+
+    starts = torch.zeros(n, dtype=torch.int32, device=device)
+    for cls in (DiscreteBatchedMicrogridEnv, BatchedMicrogridEnv):
+        env = cls(_batch(device, GBG, "factorised", 0, n=n, t=60))
+        env.reset()
+        refused(env, _lib.MGX_ERR_INVALID)                                   # a lock-step episode
+        env.engine.set_shards(2)
+        refused(env, _lib.MGX_ERR_UNSUPPORTED)                               # shards
+        env.engine.set_shards(1)
+        env.reset_windows(starts, None, max_length=9)
+        refused(env, _lib.MGX_ERR_INVALID)                                   # gathered windows
+        env.reset_windows(starts, None, max_length=9, rolling="inplace")
+        refused(env, _lib.MGX_ERR_INVALID, gamma=1.5)
+        refused(env, _lib.MGX_ERR_INVALID, gamma=-0.1)
+        refused(env, _lib.MGX_ERR_INVALID, gamma=nan)
+        env.engine.set_forecast_noise(seed=5)
+        refused(env, _lib.MGX_ERR_UNSUPPORTED)                               # noisy forecasts
+        env.close()
+        env = cls(carve(_batch(device, GBG, "factorised", 0, n=n, t=60), 1 | 4))   # genset + grid: no battery
+        env.reset_windows(starts, None, max_length=9, rolling="inplace")
+        refused(env, _lib.MGX_ERR_INVALID, end_soc=True)
+        assert "end_soc" not in (env.engine.lookahead_episodes(torch.zeros((2, H), dtype=torch.uint8, device=device), env._table)
+                                 if cls is DiscreteBatchedMicrogridEnv else
+                                 env.engine.lookahead_step_k_episodes(torch.zeros((2, H, env.engine.action_dim), dtype=F64, device=device)))
+        env.close()
+        wide = widen(generate(n, n_steps=60, seed=4, arch=GB, device=device), n_battery=2)      # several modules of a kind
+        env = cls(wide)
+        env.reset_windows(starts, None, max_length=9, rolling="inplace")
+        refused(env, _lib.MGX_ERR_UNSUPPORTED)
+        env.close()
+    # C and H below 1 (the engine's own shape check stands before them: through ctypes)
+    env = DiscreteBatchedMicrogridEnv(_batch(device, GB, "factorised", 0, n=n, t=60))
+    env.reset_windows(starts, None, max_length=9, rolling="inplace")
+    e = env.engine
+    ret = torch.full((2, n), nan, dtype=F64, device=device)
+    plans = torch.zeros((2, H), dtype=torch.uint8, device=device)
+    tptr, n_lists = e._table_ptr(env._table)
+    for c, h in ((0, H), (2, 0), (-1, H)):
+        la = _lib.Lookahead()
+        la.struct_size, la.C, la.H, la.gamma, la.ret = C.sizeof(_lib.Lookahead), c, h, 1.0, ret.data_ptr()
+        assert e._lib.mgx_lookahead_episodes(e._h, plans.data_ptr(), tptr, n_lists, C.byref(la), None) == _lib.MGX_ERR_INVALID
+        assert b"mgx_lookahead_episodes" in e._lib.mgx_last_error()
+    torch.cuda.synchronize()
+    assert bool(ret.isnan().all())
+    env.close()
+
+
+@pytest.mark.gpu
+def test_refusals_of_the_python_surface(device):
+    """PerGridWindowEnv.lookahead / ShootingMPC: a ValueError that says which option stands in the way; a step's outputs (log,
+    final observations, dry runs) stand in no way -- the lookahead takes no step."""
+    from pymgrid_amd import ShootingMPC
+    from pymgrid_amd.generator import generate, widen
+    from pymgrid_amd.hetero import PerGridWindowEnv
+    n = 300
+    plans = torch.zeros(2, 3, dtype=torch.uint8, device=device)
+    gen = torch.Generator(device=device); gen.manual_seed(1)
+    wide = widen(generate(n, n_steps=60, seed=4, arch=GB, device=device), n_battery=2)
+    for word, kw, b in (("generator", dict(generator=gen, auto_reset=True), None), ("auto_reset=False", dict(auto_reset=False), None),
+                        ("native=False", dict(auto_reset=True, native=False), None), ("several modules", dict(auto_reset=True), wide)):
+        pe = PerGridWindowEnv(b if b is not None else _batch(device, GB, "factorised", 0, n=n, t=60), trajectory_length=9, discrete=True,
+                              seed=2, **kw)
+        pe.reset()
+        with pytest.raises(ValueError, match=word):
+            pe.lookahead(plans)
+        with pytest.raises(ValueError, match=word):
+            ShootingMPC(pe, 3)
+        pe.env.close()
+    for kw in (dict(log=True), dict(final_observation=True), dict(check_asserts=True)):
+        pe = PerGridWindowEnv(_batch(device, GB, "factorised", 0, n=n, t=60), trajectory_length=9, discrete=True, auto_reset=True, seed=2, **kw)
+        pe.reset()
+        assert pe.lookahead(plans)["ret"].shape == (2, n)
+        pe.env.close()
+    pe = PerGridWindowEnv(_batch(device, GB, "factorised", 0, n=n, t=60), trajectory_length=9, discrete=True, auto_reset=True, seed=2)
+    with pytest.raises(RuntimeError, match="reset"):
+        pe.lookahead(plans)
+    pe.reset()
+    with pytest.raises(ValueError, match="plans"):
+        pe.lookahead(torch.zeros(2, 3, 7, dtype=torch.uint8, device=device))      # neither [C, H] nor [C, H, N]
+    with pytest.raises(TypeError):
+        ShootingMPC(pe.env, 3)
+    pe.env.close()
+    pc = PerGridWindowEnv(_batch(device, GB, "factorised", 0, n=n, t=60), trajectory_length=9, discrete=False, auto_reset=True, seed=2)
+    pc.reset()
+    with pytest.raises(ValueError, match="n_random"):
+        ShootingMPC(pc, 3)
+    with pytest.raises(ValueError, match="plans"):
+        pc.lookahead(torch.zeros(2, 3, 3, dtype=torch.float32, device=device))    # the env's action_dtype is float64
+    pc.env.close()
+
+
+def _mpc_env(device, discrete=True):
+    from pymgrid_amd.hetero import PerGridWindowEnv
+    pe = PerGridWindowEnv(_batch(device, GBG, "factorised", 0), trajectory_length=5, discrete=discrete, auto_reset=True, seed=23 + SOAK)
+    torch.manual_seed(41 + SOAK)
+    pe.reset()
+    return pe
+
+
+@pytest.mark.gpu
+def test_shooting_mpc_run_is_the_loop_of_lookahead_and_step(device):
+    """ShootingMPC.run(12) == a hand-written loop of lookahead + step, bit for bit; cut into 5 + 7 steps it equals the uncut run (the
+    random plans are a function of (seed, counter) alone); the statistics follow mgx_episode_stats' rule."""
+    from pymgrid_amd import ShootingMPC, shooting_candidates
+    H, R, seed = 6, 4, 11
+    whole, cut, hand = (_mpc_env(device) for _ in range(3))
+    res = ShootingMPC(whole, H, n_random=R, seed=seed, gamma=0.9).run(12, reward=True, done=True)
+    assert res["reward"].shape == (12, N) and res["done"].dtype == torch.bool
+    m = ShootingMPC(cut, H, n_random=R, seed=seed, gamma=0.9)
+    parts = [m.run(5, reward=True, done=True), m.run(7, reward=True, done=True)]
+    assert torch.equal(torch.cat([p["reward"] for p in parts]), res["reward"])
+    assert torch.equal(torch.cat([p["done"] for p in parts]), res["done"])
+    n_lists = hand.env.action_space.n
+    rows, dones = [], []
+    for _ in range(12):
+        plans = shooting_candidates(n_lists, H, R, seed, hand.env.current_step, device)
+        assert plans.shape == (n_lists + R, H)
+        out = hand.lookahead(plans, gamma=0.9)
+        _, r, d, _ = hand.step(out["first_action"].to(torch.int32))
+        rows.append(r.clone()); dones.append(d.clone())
+    r, d = torch.stack(rows), torch.stack(dones)
+    assert torch.equal(r, res["reward"]) and torch.equal(d, res["done"])
+    assert bool(d.any())
+    # the statistics by the rule of include/mgx.h
+    run, tot, eps = torch.zeros(N, dtype=F64, device=device), torch.zeros(N, dtype=F64, device=device), torch.zeros(N, dtype=torch.int32, device=device)
+    for k in range(12):
+        run = run + r[k]
+        tot = torch.where(d[k], tot + run, tot)
+        eps = eps + d[k].to(torch.int32)
+        run = torch.where(d[k], torch.zeros_like(run), run)
+    for st in (res, parts[1]):
+        assert torch.equal(st["episode_return_sum"], tot) and torch.equal(st["episodes"], eps) and torch.equal(st["return_running"], run)
+    for pe in (whole, cut, hand):
+        pe.env.close()
+
+
+@pytest.mark.gpu
+def test_shooting_mpc_with_a_horizon_of_one_earns_what_it_foresaw(device):
+    """H = 1, gamma = 1, the constant candidates only: every executed step's reward is that step's best_ret."""
+    from pymgrid_amd import ShootingMPC
+    pe = _mpc_env(device)
+    m = ShootingMPC(pe, 1)
+    for _ in range(8):
+        a = m.act()
+        foreseen = m.last["best_ret"].clone()
+        assert m.last["ret"].shape == (pe.env.action_space.n, N) and bool((m.last["steps"] == 1).all())
+        _, r, _, _ = pe.step(a)
+        assert torch.equal(r, foreseen)
+    pe.env.close()
+
+
+@pytest.mark.gpu
+def test_shooting_mpc_continuous_and_callable_candidates(device):
+    """The continuous default set (n_random uniform plans, redrawn per counter) and ``candidates=`` as a callable: run == the loop."""
+    from pymgrid_amd import ShootingMPC
+    a, b = _mpc_env(device, discrete=False), _mpc_env(device, discrete=False)
+    m = ShootingMPC(a, 5, n_random=6, seed=3)
+    res = m.run(6)
+    A = b.env.engine.action_dim
+    assert m.default_candidates(0).shape == (6, 5, A) and torch.equal(m.default_candidates(4), m.default_candidates(4))
+    assert not torch.equal(m.default_candidates(4), m.default_candidates(5))
+    calls = []
+
+    def candidates(env):
+        calls.append(env.env.current_step)
+        return m.default_candidates(env.env.current_step)
+    res2 = ShootingMPC(b, 5, candidates=candidates).run(6)
+    assert torch.equal(res["reward"], res2["reward"]) and calls == list(range(6))
+    for pe in (a, b):
+        pe.env.close()
