@@ -939,6 +939,72 @@ int mgx_lookahead_episodes(mgx_handle *h, const uint8_t *plans, const int32_t *t
 int mgx_lookahead_step_k_episodes(mgx_handle *h, const void *plans, int normalized,
                                   const mgx_lookahead *la, mgx_stream stream);
 
+/* CROSS-ENTROPY METHOD (CEM) planning: the candidates of a what-if launch DRAWN INSIDE IT round a per-grid mean, and the refit of
+ * that mean and deviation on the best few on the device.  The plan tensor [C, H, N, A] never exists: a candidate control is a
+ * function of (key, grid, candidate, plan step, column) formed in registers, and the refit regenerates the elites' controls from
+ * the same draws.  mean, sigma: double [H, N, A] (device), NORMALISED controls.  THE RULE (stated here once):
+ *
+ * Normal pair p of grid i, candidate c, plan step k (k: the index into the plan, not the step counter): Philox4x32-10 with the
+ * counter words (lo32(i), (uint32)c, (uint32)k, 0xCE300000 + p) and the key (lo32(key), hi32(key)); its four words r[0 .. 3] give
+ * (z[2p], z[2p + 1]) exactly as the normal pair of mgx_gaussian forms its pair out of r[0 .. 3].  Pair 0 serves columns 0 and 1,
+ * pair 1 columns 2 and 3.
+ *
+ * Candidate value x[c, k, i, o]:
+ *     c == 0:  v = mean[k, i, o]                                    (candidate 0 is the mean plan itself: no draw)
+ *     c >= 1:  s = sigma[k, i, o];  v = s > 0 ? mean[k, i, o] + s * z[o] : mean[k, i, o]      (a separate multiply and add)
+ *     x = !(v > 0) ? 0.0 : (v > 1 ? 1.0 : v)                        (the clip of mgx_policy)
+ *     action format F32 (mgx_set_action_format; mgx_cem_refit.round_f32):  x = (double)(float)x -- what a float32 plan would hold
+ * A pair is drawn only where one of its columns is live (s > 0: false for a negative or NaN sigma, which are not scanned for). */
+typedef struct mgx_cem {
+    int32_t struct_size;      /* = sizeof(mgx_cem) */
+    int32_t reserved;
+    uint64_t key;             /* Philox key */
+    const double *mean;       /* device [H, N, A] */
+    const double *sigma;      /* device [H, N, A] */
+} mgx_cem;
+
+/* mgx_lookahead_step_k_episodes with plans[c, k, i, :] replaced by x[c, k, i, :] above (normalised controls: there is no
+ * `normalized`): one launch of lookahead_gaussian_episodes_kernel (+ the pick, which regenerates step 0 of candidate best[i] as
+ * first_action, in the action format).  The return rule, the stop at the episode's end and every output are those of mgx_lookahead,
+ * word for word; la->per_grid must be 1.  Refusals: those of mgx_lookahead_step_k_episodes; on top MGX_ERR_INVALID for a NULL cem,
+ * cem->struct_size != sizeof(mgx_cem), a NULL mean or sigma, la->per_grid != 1 and a layout without a control.  (The draw holds 32 bits of i; a handle
+ * holds fewer grids than that, mgx_cem_refit refuses more.)  Nothing is launched when the call is refused.  An ADDITION to ABI 9 that
+ * leaves MGX_ABI_MINOR at 3: found by name (dlsym). */
+int mgx_lookahead_gaussian_episodes(mgx_handle *h, const mgx_cem *cem, const mgx_lookahead *la, mgx_stream stream);
+
+/* The refit of (mean, sigma) on the n_elite best of the C candidates of such a launch.  THE RULE (stated here once; plain fp64,
+ * every multiply and add separate, sums in the order e = 0 .. n_elite - 1, S the square root of mgx_gaussian):
+ *     elite[e, i]: for e = 0 .. n_elite - 1 the first maximum of ret[:, i] among the candidates not yet taken -- start at the lowest
+ *         such c, a later c replaces it where its return is GREATER (so elite[0] is best of mgx_lookahead and ties go to the lower c)
+ *     n = steps ? steps[i] : H.   Rows k < n, per column o, x_e = x[elite[e, i], k, i, o]:
+ *         m = (x_0 + x_1 + ...) / n_elite;   d = S(((x_0 - m)^2 + (x_1 - m)^2 + ...) / n_elite)
+ *         mean_out = alpha * m + (1.0 - alpha) * mean;   sg = alpha * d + (1.0 - alpha) * sigma
+ *         sigma_out = sg > sigma_min ? sg : sigma_min
+ *     Rows k >= n (nothing of them was simulated): mean_out = mean, sigma_out = sigma.
+ *     best_plan[k, i, :] = x[elite[0, i], k, i, :] for every k, float32 where round_f32 (which also rounds every x above).
+ * Two launches: cem_elite_kernel (a lane per grid), cem_refit_kernel (a lane per (grid, k)).  mean_out / sigma_out may be
+ * cem->mean / cem->sigma: a lane reads only the entries it writes. */
+struct mgx_cem_refit {
+    int32_t struct_size;      /* = sizeof(mgx_cem_refit) */
+    int32_t C, H;             /* candidates, horizon of the launch whose returns these are; both >= 1 */
+    int32_t n_elite;          /* in [1, min(C, 32)] */
+    int32_t round_f32;        /* the action format of that launch: 0 F64, 1 F32 */
+    double  alpha;            /* in [0, 1]: the weight of the new estimate */
+    double  sigma_min;        /* >= 0: the floor of sigma_out on the refitted rows */
+    const double  *ret;       /* [C, N] */
+    const int32_t *steps;     /* [N] or NULL (= H for every grid) */
+    int32_t *elite;           /* [n_elite, N], required */
+    double  *mean_out;        /* [H, N, A] */
+    double  *sigma_out;       /* [H, N, A] */
+    void    *best_plan;       /* [H, N, A] float64, or float32 where round_f32; or NULL */
+};                            /* (a struct tag without a typedef: the call below bears the same name) */
+
+/* Handle-free on the current device (as mgx_gae); N grids of A action columns.  MGX_ERR_INVALID: a NULL cem / refit / mean / sigma /
+ * ret / elite / mean_out / sigma_out, a wrong struct_size, N, C or H below 1, n_elite outside [1, min(C, 32)], A outside 1 .. 4,
+ * alpha outside [0, 1] or NaN, sigma_min negative or NaN.  MGX_ERR_UNSUPPORTED: N > 2^32.  An ADDITION to ABI 9 that leaves
+ * MGX_ABI_MINOR at 3. */
+int mgx_cem_refit(int64_t N, int32_t A, const mgx_cem *cem, const struct mgx_cem_refit *refit, mgx_stream stream);
+
 /* raise_errors=True(BaseMicrogridModule.__init__, base_module.py:40; as_source / as_sink, :213-224,265-270; _raise_error,
  * :79-93): the reference refuses a request a module cannot meet with a ValueError instead of clipping it.  mgx_step always
  * clips; mgx_check_step is its DRY RUN -- the same arithmetic on a register copy of the state, nothing stored, the counter

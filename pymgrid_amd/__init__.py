@@ -11,8 +11,9 @@ from .envs import (BatchedMicrogridEnv, DiscreteBatchedMicrogridEnv, DiscreteMic
                    MicrogridEnv)
 from .graph import GraphedRollout  # noqa: F401
 from .hetero import BucketedFleet, PerGridWindowEnv, PerGridWindowFleet  # noqa: F401
-from .mpc import ShootingMPC, lookahead_host, shooting_candidates  # noqa: F401
-from .policy import Exploration, GaussianSampling, MLPPolicy, Sampling, ValueHead, gae  # noqa: F401
+from .mpc import CEMPlanner, ShootingMPC, cem_key, lookahead_host, shooting_candidates  # noqa: F401
+from .policy import (Exploration, GaussianSampling, MLPPolicy, Sampling, ValueHead, cem_candidates_host,  # noqa: F401
+                     cem_refit_host, gae)
 from .priority_list import get_priority_lists  # noqa: F401
 from .rbc import RuleBasedControl  # noqa: F401
 from .trajectory import (BatteryDischargeShaper, DeterministicTrajectory,  # noqa: F401

@@ -33,9 +33,11 @@ UNITS = (
     ("mgx_gae.hip", None, 1),                                           # the advantages of what such launches return (mgx_gae)
     ("mgx_lookahead_episodes.hip", "MGX_EPISODE_PART", 2),              # what-if roll-outs of candidate plans, nothing committed
     ("mgx_lookahead_step_episodes.hip", "MGX_EPISODE_PART", 2),         # ... and their continuous twin
+    ("mgx_lookahead_gaussian_episodes.hip", "MGX_EPISODE_PART", 2),     # ... with the candidates drawn inside the launch (CEM)
+    ("mgx_cem.hip", None, 1),                                           # ... its pick, the elites and the refit (mgx_cem_refit)
 )
 # everything a built library is stamped with (source_hash): a file missing here would leave a stale libmgx.so looking current
-SOURCES = [os.path.join(_PKG, "csrc", f) for f in [u[0] for u in UNITS] + ["mgx_kernels.hpp", "mgx_core.hpp", "mgx_step_hot.hpp", "mgx_episode_loop.hpp", "mgx_episode_rows.hpp", "mgx_policy.hpp", "mgx_gae.hpp", "mgx_lookahead.hpp"]] + \
+SOURCES = [os.path.join(_PKG, "csrc", f) for f in [u[0] for u in UNITS] + ["mgx_kernels.hpp", "mgx_core.hpp", "mgx_step_hot.hpp", "mgx_episode_loop.hpp", "mgx_episode_rows.hpp", "mgx_policy.hpp", "mgx_gae.hpp", "mgx_lookahead.hpp", "mgx_cem.hpp"]] + \
           [os.path.join(_ROOT, "include", "mgx.h")]
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-fPIC"]
@@ -193,6 +195,20 @@ class Lookahead(C.Structure):
                 ("first_action", C.c_void_p)]
 
 
+class Cem(C.Structure):
+    """mgx_cem (include/mgx.h): the key and the per-grid distribution ``mgx_lookahead_gaussian_episodes`` draws its candidates from
+    and ``mgx_cem_refit`` regenerates them from (``mean`` / ``sigma``: float64 device ``[H, N, A]``)."""
+    _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32), ("key", C.c_uint64), ("mean", C.c_void_p), ("sigma", C.c_void_p)]
+
+
+class CemRefit(C.Structure):
+    """mgx_cem_refit (include/mgx.h): the returns ``mgx_cem_refit`` ranks and where the elites, the new distribution and the best
+    plan go (device arrays; ``steps`` and ``best_plan`` may be NULL)."""
+    _fields_ = [(n, C.c_int32) for n in ("struct_size", "C", "H", "n_elite", "round_f32")] + \
+               [("alpha", C.c_double), ("sigma_min", C.c_double)] + \
+               [(n, C.c_void_p) for n in ("ret", "steps", "elite", "mean_out", "sigma_out", "best_plan")]
+
+
 POLICY_MAX_HIDDEN = 64     # MGX_POLICY_MAX_HIDDEN
 POLICY_LDS_BYTES = 32768   # MGX_POLICY_LDS_BYTES
 
@@ -290,6 +306,8 @@ SYMBOLS = {
                           C.c_void_p, C.c_void_p, C.c_void_p]),
     "mgx_lookahead_episodes": (C.c_int, [C.c_void_p, C.c_void_p, c_i32_p, C.c_int32, C.POINTER(Lookahead), C.c_void_p]),
     "mgx_lookahead_step_k_episodes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(Lookahead), C.c_void_p]),
+    "mgx_lookahead_gaussian_episodes": (C.c_int, [C.c_void_p, C.POINTER(Cem), C.POINTER(Lookahead), C.c_void_p]),
+    "mgx_cem_refit": (C.c_int, [C.c_int64, C.c_int32, C.POINTER(Cem), C.POINTER(CemRefit), C.c_void_p]),
     "mgx_metrics": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "mgx_reset_windows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -9,6 +9,7 @@
 #include "mgx_policy.hpp"
 #include "mgx_gae.hpp"
 #include "mgx_lookahead.hpp"
+#include "mgx_cem.hpp"
 
 #include <cstdarg>
 #include <cstdio>
@@ -2249,6 +2250,75 @@ int mgx_lookahead_step_k_episodes(mgx_handle *h, const void *plans, int normaliz
     L.actions = plans; L.act_f32 = h->k.act_f32 != 0; L.normalized = normalized;
     const bool was_launched = launch_lookahead_step_k_episodes_p0(L) || launch_lookahead_step_k_episodes_p1(L);
     return finish_lookahead(h, L, was_launched, la, plans, false, "lookahead_step_k_episodes_kernel launch", fn);
+}
+
+// ---- CEM planning (mgx_cem.hpp): the candidates drawn inside the what-if launch, the refit on the device ----
+// what both calls check of `cem`
+static int cem_struct_refusal(const mgx_cem *cem, const char *fn)
+{
+    if (!cem) return fail(MGX_ERR_INVALID, "%s: NULL cem", fn);
+    if (cem->struct_size != (int32_t)sizeof(mgx_cem))
+        return fail(MGX_ERR_INVALID, "%s: cem->struct_size is %d, sizeof(mgx_cem) is %d", fn, cem->struct_size, (int)sizeof(mgx_cem));
+    if (!cem->mean || !cem->sigma) return fail(MGX_ERR_INVALID, "%s: NULL cem->mean or cem->sigma", fn);
+    return MGX_OK;
+}
+
+int mgx_lookahead_gaussian_episodes(mgx_handle *h, const mgx_cem *cem, const mgx_lookahead *la, mgx_stream stream)
+{
+    g_err[0] = 0;
+    const char *fn = "mgx_lookahead_gaussian_episodes";
+    if (int rc = lookahead_struct_refusal(la, fn)) return rc;
+    if (int rc = cem_struct_refusal(cem, fn)) return rc;
+    if (la->per_grid != 1) return fail(MGX_ERR_INVALID, "%s: la->per_grid is %d: every grid has its own distribution (1)", fn, la->per_grid);
+    LookaheadLaunch L{};
+    if (int rc = prepare_lookahead(h, cem->mean, la, stream, fn, L)) return rc;
+    if (h->action_dim < 1 || h->action_dim > 4) return fail(MGX_ERR_INVALID, "%s: the layout has %d controls (1 .. 4 can be planned)", fn, h->action_dim);
+    L.act_f32 = h->k.act_f32 != 0; L.normalized = 1;
+    L.cem_key = cem->key; L.cem_mean = cem->mean; L.cem_sigma = cem->sigma;
+    const bool was_launched = launch_lookahead_gaussian_episodes_p0(L) || launch_lookahead_gaussian_episodes_p1(L);
+    if (!was_launched) return fail(MGX_ERR_UNSUPPORTED, "%s: no kernel for layout flags %d", fn, h->flags);
+    if (int rc = launched("lookahead_gaussian_episodes_kernel launch")) return rc;
+    if (!la->steps && !la->best && !la->best_ret && !la->first_action) return MGX_OK;
+    CemPick q{};
+    q.N = h->k.N; q.C = L.C; q.H = L.H; q.t0 = L.t; q.A = h->action_dim;
+    q.f32 = L.act_f32; q.key = cem->key; q.mean = cem->mean; q.sigma = cem->sigma;
+    q.ret = L.ret; q.ep_final = h->k.ep_final;
+    q.steps = la->steps; q.best = la->best; q.best_ret = la->best_ret; q.first_action = la->first_action;
+    launch_cem_pick(q, L.stream);
+    return launched("cem_pick_kernel launch");
+}
+
+int mgx_cem_refit(int64_t N, int32_t A, const mgx_cem *cem, const struct mgx_cem_refit *refit, mgx_stream stream)
+{
+    g_err[0] = 0;
+    const char *fn = "mgx_cem_refit";
+    if (int rc = cem_struct_refusal(cem, fn)) return rc;
+    if (!refit) return fail(MGX_ERR_INVALID, "%s: NULL refit", fn);
+    if (refit->struct_size != (int32_t)sizeof(struct mgx_cem_refit))
+        return fail(MGX_ERR_INVALID, "%s: refit->struct_size is %d, sizeof(struct mgx_cem_refit) is %d", fn, refit->struct_size, (int)sizeof(struct mgx_cem_refit));
+    if (!refit->ret || !refit->elite || !refit->mean_out || !refit->sigma_out)
+        return fail(MGX_ERR_INVALID, "%s: NULL refit->ret, elite, mean_out or sigma_out", fn);
+    if (N < 1 || refit->C < 1 || refit->H < 1)
+        return fail(MGX_ERR_INVALID, "%s: N = %lld, %d candidates over a horizon of %d (all must be positive)", fn, (long long)N, refit->C, refit->H);
+    if (refit->n_elite < 1 || refit->n_elite > refit->C || refit->n_elite > 32)
+        return fail(MGX_ERR_INVALID, "%s: n_elite = %d is outside [1, min(C, 32)], C = %d", fn, refit->n_elite, refit->C);
+    if (A < 1 || A > 4) return fail(MGX_ERR_INVALID, "%s: A = %d action columns (1 .. 4)", fn, A);
+    if (!(refit->alpha >= 0.0 && refit->alpha <= 1.0)) return fail(MGX_ERR_INVALID, "%s: alpha = %g is outside [0, 1]", fn, refit->alpha);
+    if (!(refit->sigma_min >= 0.0)) return fail(MGX_ERR_INVALID, "%s: sigma_min = %g is negative or NaN", fn, refit->sigma_min);
+    if (N > (int64_t)1 << 32) return fail(MGX_ERR_UNSUPPORTED, "%s: more than 2^32 grids (the draw holds 32 bits of the grid)", fn);
+    int ndev = 0;
+    hipError_t e = hipGetDeviceCount(&ndev);
+    if (e != hipSuccess || ndev <= 0) return fail(MGX_ERR_DEVICE, "%s: no HIP device available -- this engine has no CPU path", fn);
+    CemRefitArgs g{};
+    g.N = N; g.A = A; g.C = refit->C; g.H = refit->H; g.E = refit->n_elite;
+    g.f32 = refit->round_f32 != 0; g.key = cem->key;
+    g.alpha = refit->alpha; g.beta = 1.0 - refit->alpha; g.sigma_min = refit->sigma_min;
+    g.mean = cem->mean; g.sigma = cem->sigma; g.ret = refit->ret; g.steps = refit->steps; g.elite = refit->elite;
+    g.mean_out = refit->mean_out; g.sigma_out = refit->sigma_out; g.best_plan = refit->best_plan;
+    launch_cem_elite(g, (hipStream_t)stream);
+    if (int rc = launched("cem_elite_kernel launch")) return rc;
+    launch_cem_refit(g, (hipStream_t)stream);
+    return launched("cem_refit_kernel launch");
 }
 
 // The closed-loop launches (mgx_policy.hpp).  What they check of the policy before prepare_episode_launch: what needs no handle

@@ -42,6 +42,8 @@ struct LookaheadLaunch {
     const uint8_t *ids;              // discrete: plans [C, H] or [C, H, N]
     const void *actions;             // continuous: plans [C, H, A] or [C, H, N, A] in the handle's action format
     bool act_f32;
+    uint64_t cem_key;                // drawn candidates (mgx_cem): the key and the [H, N, A] rows the controls are formed from
+    const double *cem_mean, *cem_sigma;
     int normalized;
     int32_t t, C, H;
     double gamma;
@@ -52,5 +54,8 @@ constexpr int LOOKAHEAD_MAX_Y = 65535;       // candidates per launch (gridDim.y
 
 bool launch_lookahead_episodes_p0(const LookaheadLaunch &L); bool launch_lookahead_episodes_p1(const LookaheadLaunch &L);
 bool launch_lookahead_step_k_episodes_p0(const LookaheadLaunch &L); bool launch_lookahead_step_k_episodes_p1(const LookaheadLaunch &L);
+// ... and their sibling with drawn candidates (mgx_lookahead_gaussian_episodes: lookahead_gaussian_episodes_kernel,
+// mgx_lookahead_gaussian_episodes.hip, on top of mgx_cem.hpp)
+bool launch_lookahead_gaussian_episodes_p0(const LookaheadLaunch &L); bool launch_lookahead_gaussian_episodes_p1(const LookaheadLaunch &L);
 
 }  // namespace mgx

@@ -483,11 +483,10 @@ __device__ __forceinline__ double policy_sqrt(double v)
     return pos ? S : 0.0;
 }
 
-// normal pair p of grid i at step counter t: z0 = z[2p] = R cos, z1 = z[2p + 1] = R sin (Box-Muller on draw number 8 + p)
-__device__ __forceinline__ void gaussian_pair(uint64_t seed, int64_t i, int32_t t, uint32_t p, double &z0, double &z1)
+// four words of a draw -> a normal pair: z0 = R cos, z1 = R sin (Box-Muller).  Shared by the Gaussian head's draw below and the CEM
+// candidates' (mgx_cem.hpp), which differ in the counter words alone.
+__device__ __forceinline__ void gaussian_pair_of_words(const uint32_t (&r)[4], double &z0, double &z1)
 {
-    uint32_t r[4];
-    explore_draw(seed, i, t, 8u + p, r);
     const double u1 = 1.0 - uniform53(r[0], r[1]);                                        // (exact; in (0, 1])
     const double R = policy_sqrt(-2.0 * policy_log(u1));
     const uint64_t a64 = (uint64_t)r[2] << 32 | r[3];
@@ -499,6 +498,14 @@ __device__ __forceinline__ void gaussian_pair(uint64_t seed, int64_t i, int32_t 
     const double cs = q == 0u ? c : (q == 1u ? -s : (q == 2u ? -c : s));
     z0 = R * cs;
     z1 = R * sn;
+}
+
+// normal pair p of grid i at step counter t: z0 = z[2p], z1 = z[2p + 1], out of draw number 8 + p
+__device__ __forceinline__ void gaussian_pair(uint64_t seed, int64_t i, int32_t t, uint32_t p, double &z0, double &z1)
+{
+    uint32_t r[4];
+    explore_draw(seed, i, t, 8u + p, r);
+    gaussian_pair_of_words(r, z0, z1);
 }
 
 // C_i of the lane, formed once in the prologue: the sum over the live columns (s > 0) of L(s) + log(2 pi) / 2, in column order

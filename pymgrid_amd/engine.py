@@ -782,9 +782,9 @@ class StepEngine:
         return self._launch_episodes("mgx_step_k_episodes", (_ptr(actions), K, 1 if normalized else 0), K, res, (r, d, s, g), st, out,
                                      obs, final_obs)
 
-    def _lookahead(self, symbol, lead, plans, C_, H, per_grid, first_shape, gamma, end_soc, pick, out):
-        """What the two what-if calls share: the ``mgx_lookahead`` struct over outputs taken from ``out`` or allocated, the call --
-        which moves neither the state nor the counter -- and the result dict."""
+    def _lookahead(self, symbol, lead, first_dtype, C_, H, per_grid, first_shape, gamma, end_soc, pick, out):
+        """What the three what-if calls share: the ``mgx_lookahead`` struct over outputs taken from ``out`` or allocated, the call
+        ``symbol(handle, *lead, &la, stream)`` -- which moves neither the state nor the counter -- and the result dict."""
         out = out or {}
         N, res = self.N, {}
         la = _lib.Lookahead()
@@ -796,7 +796,7 @@ class StepEngine:
                 ("end_soc", end_soc, (C_, N), torch.float64),
                 ("best", pick, (N,), torch.int32),
                 ("best_ret", pick, (N,), torch.float64),
-                ("first_action", pick, first_shape, plans.dtype)):
+                ("first_action", pick, first_shape, first_dtype)):
             if not want:
                 continue
             t = out.get(name)
@@ -806,7 +806,7 @@ class StepEngine:
                 raise ValueError(f"out[{name!r}] must be a contiguous {dtype} tensor {list(shape)} on {self.device}")
             res[name] = t
             setattr(la, name, _ptr(t))
-        self._call(getattr(self._lib, symbol), _ptr(plans), *lead, C.byref(la))
+        self._call(getattr(self._lib, symbol), *lead, C.byref(la))
         return res
 
     def lookahead_episodes(self, plans, table, gamma=1.0, end_soc=False, pick=True, out=None):
@@ -821,8 +821,8 @@ class StepEngine:
                 or plans.dim() not in (2, 3) or (plans.dim() == 3 and plans.shape[2] != self.N) or plans.numel() == 0:
             raise ValueError(f"plans must be a contiguous uint8 tensor [C, H] or [C, H, {self.N}] on {self.device}")
         tptr, n_lists = self._table_ptr(table)
-        return self._lookahead("mgx_lookahead_episodes", (tptr, n_lists), plans, plans.shape[0], plans.shape[1], plans.dim() == 3,
-                               (self.N,), gamma, end_soc, pick, out)
+        return self._lookahead("mgx_lookahead_episodes", (_ptr(plans), tptr, n_lists), plans.dtype, plans.shape[0], plans.shape[1],
+                               plans.dim() == 3, (self.N,), gamma, end_soc, pick, out)
 
     def lookahead_step_k_episodes(self, plans, normalized=True, gamma=1.0, end_soc=False, pick=True, out=None):
         """``lookahead_episodes`` for continuous controls (``mgx_lookahead_step_k_episodes``): ``plans`` ``[C, H, A]`` (shared) or
@@ -832,8 +832,73 @@ class StepEngine:
         if not torch.is_tensor(plans) or plans.dtype != self.action_dtype or plans.device != self.device or not plans.is_contiguous() \
                 or plans.dim() not in (3, 4) or plans.shape[-1] != A or (plans.dim() == 4 and plans.shape[2] != self.N) or plans.numel() == 0:
             raise ValueError(f"plans must be a contiguous {self.action_dtype} tensor [C, H, {A}] or [C, H, {self.N}, {A}] on {self.device}")
-        return self._lookahead("mgx_lookahead_step_k_episodes", (1 if normalized else 0,), plans, plans.shape[0], plans.shape[1],
-                               plans.dim() == 4, (self.N, A), gamma, end_soc, pick, out)
+        return self._lookahead("mgx_lookahead_step_k_episodes", (_ptr(plans), 1 if normalized else 0), plans.dtype, plans.shape[0],
+                               plans.shape[1], plans.dim() == 4, (self.N, A), gamma, end_soc, pick, out)
+
+    def _cem_struct(self, mean, sigma, key):
+        """``mgx_cem`` over ``mean`` / ``sigma`` (contiguous float64 ``[H, N, A]`` on the engine's device) and the 64-bit ``key``."""
+        A = self.action_dim
+        for name, t in (("mean", mean), ("sigma", sigma)):
+            if not torch.is_tensor(t) or t.dtype != torch.float64 or t.device != self.device or not t.is_contiguous() \
+                    or t.dim() != 3 or tuple(t.shape[1:]) != (self.N, A) or t.shape[0] < 1:
+                raise ValueError(f"{name} must be a contiguous float64 tensor [H, {self.N}, {A}] on {self.device}")
+        if mean.shape != sigma.shape:
+            raise ValueError(f"mean {list(mean.shape)} and sigma {list(sigma.shape)} must agree")
+        key = int(key)
+        if not 0 <= key < 2 ** 64:
+            raise ValueError(f"key = {key}: a 64-bit unsigned key")
+        cem = _lib.Cem()
+        cem.struct_size, cem.key, cem.mean, cem.sigma = C.sizeof(_lib.Cem), key, _ptr(mean), _ptr(sigma)
+        return cem
+
+    def lookahead_gaussian_episodes(self, mean, sigma, n_candidates, key, gamma=1.0, end_soc=False, pick=True, out=None):
+        """``lookahead_step_k_episodes`` over ``n_candidates`` plans per grid that are DRAWN inside the launch round ``mean`` with
+        deviation ``sigma`` (float64 ``[H, N, A]``, normalised controls; ``mgx_lookahead_gaussian_episodes``) -- the values of
+        ``pymgrid_amd.policy.cem_candidates_host(mean, sigma, n_candidates, key, action_dtype)`` without that tensor: candidate 0 is
+        the clipped mean.  ``first_action`` is ``[N, A]`` in ``action_dtype``.  Everything else as ``lookahead_episodes``."""
+        cem = self._cem_struct(mean, sigma, key)
+        if int(n_candidates) < 1:
+            raise ValueError("n_candidates must be positive")
+        return self._lookahead("mgx_lookahead_gaussian_episodes", (C.byref(cem),), self.action_dtype, int(n_candidates), mean.shape[0],
+                               True, (self.N, self.action_dim), gamma, end_soc, pick, out)
+
+    def cem_refit(self, ret, steps, mean, sigma, key, n_elite, alpha=1.0, sigma_min=0.0, best_plan=True, out=None):
+        """The refit of ``(mean, sigma)`` on the ``n_elite`` best of the candidates whose returns ``ret`` (float64 ``[C, N]``) a
+        ``lookahead_gaussian_episodes`` over ``(mean, sigma, key)`` left, on the device (``mgx_cem_refit``;
+        ``pymgrid_amd.policy.cem_refit_host``'s values bit for bit): ``elite`` int32 ``[n_elite, N]``, ``mean`` / ``sigma`` float64
+        ``[H, N, A]`` (rows ``k >= steps`` pass through; ``steps`` int32 ``[N]`` or None: every row is refitted) and, with
+        ``best_plan=True``, ``best_plan`` ``[H, N, A]`` in ``action_dtype`` (the controls of candidate ``elite[0]``).  ``out=``: your
+        own tensors by those names; ``out["mean"]`` / ``out["sigma"]`` may be the inputs (in place)."""
+        cem = self._cem_struct(mean, sigma, key)
+        H, N, A = mean.shape
+        if not torch.is_tensor(ret) or ret.dtype != torch.float64 or ret.device != self.device or not ret.is_contiguous() \
+                or ret.dim() != 2 or ret.shape[1] != N or ret.shape[0] < 1:
+            raise ValueError(f"ret must be a contiguous float64 tensor [C, {N}] on {self.device}")
+        if steps is not None and (not torch.is_tensor(steps) or steps.dtype != torch.int32 or steps.device != self.device
+                                  or not steps.is_contiguous() or tuple(steps.shape) != (N,)):
+            raise ValueError(f"steps must be a contiguous int32 tensor [{N}] on {self.device} or None")
+        out = out or {}
+        E = int(n_elite)
+        res = {}
+        for name, want, shape, dtype in (("elite", True, (E, N), torch.int32), ("mean", True, (H, N, A), torch.float64),
+                                         ("sigma", True, (H, N, A), torch.float64), ("best_plan", best_plan, (H, N, A), self.action_dtype)):
+            if not want:
+                continue
+            t = out.get(name)
+            if t is None:
+                t = self._empty(*[max(d, 0) for d in shape], dtype=dtype)
+            elif t.dtype != dtype or t.device != self.device or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
+                raise ValueError(f"out[{name!r}] must be a contiguous {dtype} tensor {list(shape)} on {self.device}")
+            res[name] = t
+        rf = _lib.CemRefit()
+        rf.struct_size, rf.C, rf.H, rf.n_elite = C.sizeof(_lib.CemRefit), int(ret.shape[0]), int(H), E
+        rf.round_f32 = 1 if self.action_dtype == torch.float32 else 0
+        rf.alpha, rf.sigma_min = float(alpha), float(sigma_min)
+        rf.ret, rf.steps, rf.elite = _ptr(ret), _ptr(steps), _ptr(res["elite"])
+        rf.mean_out, rf.sigma_out, rf.best_plan = _ptr(res["mean"]), _ptr(res["sigma"]), _ptr(res.get("best_plan"))
+        with torch.cuda.device(self.device):
+            check(self._lib.mgx_cem_refit(N, A, C.byref(cem), C.byref(rf), torch.cuda.current_stream(self.device).cuda_stream))
+        return res
 
     def _launch_policy_episodes(self, symbol, policy, exploration, lead, K, res, bufs, taken, st, out, obs, final_obs, sampling=None,
                                 probs=None, critic=None, values=(None, None, None)):

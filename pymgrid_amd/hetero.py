@@ -830,6 +830,38 @@ class PerGridWindowEnv:
             return e.lookahead_episodes(plans, env._table, gamma=gamma, end_soc=end_soc, pick=pick, out=out)
         return e.lookahead_step_k_episodes(plans, normalized=normalized, gamma=gamma, end_soc=end_soc, pick=pick, out=out)
 
+    def _cem_engine(self, what):
+        """The engine of a continuous env that offers ``lookahead`` and has been reset, or the error that says why not."""
+        why = self._lookahead_refusal()
+        if why is None and isinstance(self.env, DiscreteBatchedMicrogridEnv):
+            why = "discrete=True: the candidates are drawn round a mean of continuous controls"
+        if why is not None:
+            raise ValueError(f"PerGridWindowEnv.{what} is not offered with {why}")
+        if self.starts is None:
+            raise RuntimeError(f"{what}() before reset()")
+        return self.env.engine
+
+    def lookahead_gaussian(self, mean, sigma, n_candidates, key, gamma=1.0, end_soc=False, pick=True, out=None):
+        """``lookahead`` over ``n_candidates`` plans per grid DRAWN INSIDE THE LAUNCH round a per-grid ``mean`` with deviation
+        ``sigma`` (float64 ``[H, N, A]``, normalised controls; ``mgx_lookahead_gaussian_episodes``) -- the primitive of the
+        cross-entropy method (``pymgrid_amd.CEMPlanner``).  The results are those of
+        ``lookahead(cem_candidates_host(mean, sigma, n_candidates, key, action_dtype))`` bit for bit, without the ``[C, H, N, A]``
+        tensor: candidate 0 is the clipped mean itself, candidate ``c >= 1`` ``clip(mean + sigma * z)`` with ``z`` a function of
+        ``(key, grid, c, plan step, column)``; columns with ``sigma <= 0`` stay on the mean.  Continuous envs only; everything else
+        (results, ``out=``, nothing moves) as ``lookahead``."""
+        e = self._cem_engine("lookahead_gaussian")
+        return e.lookahead_gaussian_episodes(mean, sigma, n_candidates, key, gamma=gamma, end_soc=end_soc, pick=pick, out=out)
+
+    def cem_refit(self, ret, steps, mean, sigma, key, n_elite, alpha=1.0, sigma_min=0.0, best_plan=True, out=None):
+        """``(mean, sigma)`` refitted on the ``n_elite`` best candidates of ``lookahead_gaussian(mean, sigma, C, key)`` -- ``ret`` and
+        ``steps`` are its results -- in two small launches that regenerate the elites' controls from the draw
+        (``mgx_cem_refit``; ``pymgrid_amd.policy.cem_refit_host`` bit for bit).  Returns ``elite`` ``[n_elite, N]``, ``mean``,
+        ``sigma`` ``[H, N, A]`` (``alpha``: the weight of the new estimate, ``sigma_min``: the floor of the new sigma; rows the launch
+        did not simulate pass through) and ``best_plan`` ``[H, N, A]`` in ``action_dtype``.  ``out={"mean": mean, "sigma": sigma}``
+        refits in place."""
+        e = self._cem_engine("cem_refit")
+        return e.cem_refit(ret, steps, mean, sigma, key, n_elite, alpha=alpha, sigma_min=sigma_min, best_plan=best_plan, out=out)
+
     def _check_policy(self, kind, policy, head, n_out, what):
         """What ``rollout_policy`` / ``step_k_policy`` refuse on top of ``rollout`` / ``step_k`` with rows: a policy of the wrong head
         or the wrong size."""

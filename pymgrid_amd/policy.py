@@ -229,26 +229,155 @@ def policy_sqrt(v):
     return torch.where(pos, r + (0.5 * y) * (a - r * r), torch.zeros_like(v))
 
 
-def gaussian_uniforms(seed, grid, counter, pair, device=None):
-    """``(u1, q, f)`` of normal pair ``pair`` (``mgx_gaussian``): the radius' uniform in (0, 1], the quadrant (int64, 0 .. 3) and the
-    fraction of a quarter turn, out of draw number ``GAUSS_DRAW + pair``."""
-    r = philox_words(seed, grid, counter, EXPLORE_TAG + GAUSS_DRAW + int(pair), device)
+def uniforms_of_words(r):
+    """``(u1, q, f)`` out of the four words ``r`` of one draw (``mgx_gaussian``): the radius' uniform in (0, 1], the quadrant (int64,
+    0 .. 3) and the fraction of a quarter turn."""
     u1 = 1.0 - uniform53(r[0], r[1])
     q = r[2] >> 30                                                  # (bits 63, 62 of a64 = r[2] << 32 | r[3])
     f = ((((r[2] & 0x3FFFFFFF) << 22) | (r[3] >> 10)).to(torch.float64)) * (1.0 / 4503599627370496.0)
     return u1, q, f
 
 
-def gaussian_pair(seed, grid, counter, pair, device=None):
-    """``(z[2 * pair], z[2 * pair + 1])`` of ``mgx_gaussian`` (include/mgx.h): two independent standard normal draws of grid
-    ``grid`` at step counter ``counter`` by Box-Muller on the rule's own logarithm, sine and cosine -- the device's
-    ``gaussian_pair`` bit for bit."""
-    u1, q, f = gaussian_uniforms(seed, grid, counter, pair, device)
+def pair_of_words(r):
+    """Four words of one draw -> a normal pair by Box-Muller on the rule's own logarithm, square root, sine and cosine
+    (``mgx_gaussian``): the device's ``gaussian_pair_of_words`` bit for bit.  What ``gaussian_pair`` and ``cem_pair`` share."""
+    u1, q, f = uniforms_of_words(r)
     R = policy_sqrt(-2.0 * policy_log(u1))
     s, c = policy_quarter_turn(f)
     sin = torch.where(q == 0, s, torch.where(q == 1, c, torch.where(q == 2, -s, -c)))
     cos = torch.where(q == 0, c, torch.where(q == 1, -s, torch.where(q == 2, -c, s)))
     return R * cos, R * sin
+
+
+def gaussian_uniforms(seed, grid, counter, pair, device=None):
+    """``(u1, q, f)`` of normal pair ``pair`` (``mgx_gaussian``), out of draw number ``GAUSS_DRAW + pair``."""
+    return uniforms_of_words(philox_words(seed, grid, counter, EXPLORE_TAG + GAUSS_DRAW + int(pair), device))
+
+
+def gaussian_pair(seed, grid, counter, pair, device=None):
+    """``(z[2 * pair], z[2 * pair + 1])`` of ``mgx_gaussian`` (include/mgx.h): two independent standard normal draws of grid
+    ``grid`` at step counter ``counter`` by Box-Muller on the rule's own logarithm, sine and cosine -- the device's
+    ``gaussian_pair`` bit for bit."""
+    return pair_of_words(philox_words(seed, grid, counter, EXPLORE_TAG + GAUSS_DRAW + int(pair), device))
+
+
+CEM_TAG = 0xCE300000        # fourth Philox counter word of normal pair 0 of a CEM candidate (include/mgx.h, mgx_cem)
+
+
+def policy_clip(v):
+    """The clip of ``mgx_policy``: ``0.0`` where ``not v > 0`` (a NaN too), ``1.0`` where ``v > 1``, else ``v``."""
+    return torch.where(~(v > 0), torch.zeros_like(v), torch.where(v > 1, torch.ones_like(v), v))
+
+
+def cem_pair(key, grid, cand, step, pair, device=None):
+    """``(z[2 * pair], z[2 * pair + 1])`` of grid ``grid`` (below 2**32), candidate ``cand``, plan step ``step`` (``mgx_cem``,
+    include/mgx.h): the counter words ``(lo32(grid), cand, step, CEM_TAG + pair)`` under ``key``, turned into a pair as
+    ``gaussian_pair`` turns its words -- the device's ``cem_pair`` bit for bit."""
+    grid = torch.as_tensor(grid, device=device).to(torch.int64)
+    cand = torch.as_tensor(cand, device=grid.device).to(torch.int64)
+    return pair_of_words(philox_words(key, grid + (cand << 32), step, CEM_TAG + int(pair), grid.device))
+
+
+def _cem_check(mean, sigma):
+    for name, t in (("mean", mean), ("sigma", sigma)):
+        if not torch.is_tensor(t) or t.dtype != torch.float64 or t.dim() != 3:
+            raise ValueError(f"{name} must be a float64 tensor [H, N, A], not {getattr(t, 'dtype', type(t))} {list(getattr(t, 'shape', ()))}")
+    if mean.shape != sigma.shape or mean.device != sigma.device:
+        raise ValueError(f"mean {list(mean.shape)} on {mean.device} and sigma {list(sigma.shape)} on {sigma.device} must agree")
+    H, N, A = mean.shape
+    if H < 1 or N < 1 or not 1 <= A <= MAX_CONTROLS:
+        raise ValueError(f"mean must be [H, N, A] with H, N >= 1 and 1 <= A <= {MAX_CONTROLS}, not {list(mean.shape)}")
+    return int(H), int(N), int(A)
+
+
+def _cem_values(mean, sigma, key, cand, grid, dtype):
+    """``x[cand, k, grid, o]`` of ``mgx_cem`` for ``mean`` / ``sigma`` ``[H, N, A]``, ``cand`` int64 broadcastable against
+    ``[..., H, N]`` and ``grid`` int64 ``[N]`` (the grids' numbers): float64 ``[..., H, N, A]``, rounded once where ``dtype`` is
+    float32."""
+    if dtype not in (torch.float64, torch.float32):
+        raise ValueError("dtype must be torch.float64 or torch.float32")
+    H, N, A = mean.shape
+    step = torch.arange(H, dtype=torch.int64, device=mean.device).view(H, 1)
+    drawn = cand >= 1
+    cols = []
+    for p in range((A + 1) // 2):
+        for o, z in zip((2 * p, 2 * p + 1), cem_pair(key, grid, cand, step, p)):
+            if o < A:
+                m, s = mean[..., o], sigma[..., o]
+                cols.append(torch.where((s > 0) & drawn, m + s * z, m))
+    x = policy_clip(torch.stack(torch.broadcast_tensors(*cols), dim=-1))
+    return x.to(torch.float32).to(torch.float64) if dtype == torch.float32 else x
+
+
+def cem_candidates_host(mean, sigma, C, key, dtype=torch.float64, grid=None, first=0):
+    """The candidates ``mgx_lookahead_gaussian_episodes`` draws inside its launch, as the plan tensor it never builds (``mgx_cem``,
+    include/mgx.h, operation by operation in torch, on any device): ``[C, H, N, A]`` in ``dtype`` from ``mean`` / ``sigma`` float64
+    ``[H, N, A]`` -- candidate 0 the clipped mean, candidate ``c >= 1`` ``clip(mean + sigma * z)`` on the columns with
+    ``sigma > 0``, ``z`` a function of ``(key, grid, c, plan step, column)`` alone.  float32: the float64 values rounded once.
+    ``grid`` (int64 ``[N]``, default ``0 .. N - 1``): the numbers of the grids the rows belong to; ``first``: the number of the
+    first candidate (a subset evaluated on its own gives the same values)."""
+    H, N, A = _cem_check(mean, sigma)
+    C = int(C)
+    if C < 1 or int(first) < 0:
+        raise ValueError("C must be positive and first non-negative")
+    dev = mean.device
+    grid = torch.arange(N, dtype=torch.int64, device=dev) if grid is None else torch.as_tensor(grid, device=dev).to(torch.int64)
+    if grid.shape != (N,):
+        raise ValueError(f"grid must name the {N} grids of mean")
+    cand = torch.arange(int(first), int(first) + C, dtype=torch.int64, device=dev).view(C, 1, 1)
+    return _cem_values(mean, sigma, int(key), cand, grid, dtype).to(dtype).contiguous()
+
+
+def cem_refit_host(ret, steps, mean, sigma, key, n_elite, alpha=1.0, sigma_min=0.0, dtype=torch.float64):
+    """The rule of ``mgx_cem_refit`` (include/mgx.h) in torch, on any device, operation by operation: from the returns ``ret``
+    float64 ``[C, N]`` of a launch over the candidates of ``(mean, sigma, key)`` and the steps it counted (``steps`` int32 ``[N]``
+    or None: H) to ``elite`` int32 ``[n_elite, N]`` (the explicit loop: the first maximum among the candidates not yet taken, a
+    later one replaces it where GREATER), the refitted ``mean`` / ``sigma`` ``[H, N, A]`` (rows ``k >= steps`` pass through) and
+    ``best_plan`` ``[H, N, A]`` in ``dtype`` (candidate ``elite[0]``)."""
+    H, N, A = _cem_check(mean, sigma)
+    if not torch.is_tensor(ret) or ret.dtype != torch.float64 or ret.dim() != 2 or ret.shape[1] != N or ret.shape[0] < 1:
+        raise ValueError(f"ret must be a float64 tensor [C, {N}], not {getattr(ret, 'dtype', type(ret))} {list(getattr(ret, 'shape', ()))}")
+    Cn, E = int(ret.shape[0]), int(n_elite)
+    if not 1 <= E <= min(Cn, 32):
+        raise ValueError(f"n_elite = {n_elite} is outside [1, min(C, 32)], C = {Cn}")
+    alpha, sigma_min = float(alpha), float(sigma_min)
+    if not 0.0 <= alpha <= 1.0:
+        raise ValueError(f"alpha = {alpha} is outside [0, 1]")
+    if not sigma_min >= 0.0:
+        raise ValueError(f"sigma_min = {sigma_min} is negative or NaN")
+    if steps is not None and (not torch.is_tensor(steps) or steps.dtype != torch.int32 or tuple(steps.shape) != (N,)):
+        raise ValueError(f"steps must be an int32 tensor [{N}] or None")
+    dev = mean.device
+    grid = torch.arange(N, dtype=torch.int64, device=dev)
+    taken = torch.zeros((Cn, N), dtype=torch.bool, device=dev)
+    elite = torch.empty((E, N), dtype=torch.int32, device=dev)
+    for e in range(E):
+        b = torch.full((N,), -1, dtype=torch.int32, device=dev)
+        bv = torch.zeros(N, dtype=torch.float64, device=dev)
+        for c in range(Cn):
+            take = ~taken[c] & ((b < 0) | (ret[c] > bv))
+            b = torch.where(take, torch.full_like(b, c), b)
+            bv = torch.where(take, ret[c], bv)
+        elite[e] = b
+        taken[b.long(), grid] = True
+    xs = [_cem_values(mean, sigma, int(key), elite[e].long().view(1, N), grid, dtype) for e in range(E)]     # each [H, N, A]
+    tot = torch.zeros_like(mean)
+    for x in xs:
+        tot = tot + x
+    En = torch.full_like(mean, float(E))          # (a tensor: torch divides by a NUMBER on the GPU as a multiply by its reciprocal)
+    m = tot / En
+    q = torch.zeros_like(mean)
+    for x in xs:
+        d = x - m
+        q = q + d * d
+    d = policy_sqrt(q / En)
+    sg = alpha * d + (1.0 - alpha) * sigma
+    n = torch.full((N,), H, dtype=torch.int32, device=dev) if steps is None else steps
+    fit = (torch.arange(H, dtype=torch.int32, device=dev).view(H, 1) < n.view(1, N)).unsqueeze(-1)
+    return {"elite": elite,
+            "mean": torch.where(fit, alpha * m + (1.0 - alpha) * mean, mean),
+            "sigma": torch.where(fit, torch.where(sg > sigma_min, sg, torch.full_like(sg, sigma_min)), sigma),
+            "best_plan": xs[0].to(dtype).contiguous()}
 
 
 class GaussianSampling:
