@@ -683,7 +683,7 @@ typedef struct mgx_exploration {
 } mgx_exploration;
 
 /* mgx_rollout_policy_episodes with the discrete head exploring by the rule of mgx_exploration: one launch of
- * rollout_policy_explore_episodes_kernel.  action_id_out receives the ids taken, explored ones included.  explore == NULL: the call
+ * rollout_policy_head_episodes_kernel (exploring head).  action_id_out receives the ids taken, explored ones included.  explore == NULL: the call
  * IS mgx_rollout_policy_episodes (forwarded).  Every other argument, result and refusal as there; on top MGX_ERR_INVALID for
  * explore->struct_size != sizeof(mgx_exploration), an epsilon outside [0, 1] or NaN, a negative or NaN sigma[o] for
  * o < mgx_action_dim (both calls check the whole struct, whichever head they run).
@@ -693,7 +693,7 @@ int mgx_rollout_policy_explore_episodes(mgx_handle *h, const mgx_policy *policy,
                                         uint32_t *status_trace, uint8_t *action_id_out, const mgx_episode_stats *stats,
                                         const mgx_episode_rows *rows, mgx_stream stream);
 
-/* The continuous twin (step_k_policy_explore_episodes_kernel): mgx_step_k_policy_episodes with the noise of mgx_exploration on
+/* The continuous twin (step_k_policy_head_episodes_kernel, exploring head): mgx_step_k_policy_episodes with the noise of mgx_exploration on
  * every control before its clip.  actions_out receives the controls taken.  explore == NULL: the call IS
  * mgx_step_k_policy_episodes.  On top of its refusals MGX_ERR_INVALID as mgx_rollout_policy_explore_episodes refuses a mgx_exploration.
  * An ADDITION to ABI 9 that leaves MGX_ABI_MINOR at 3: consumers find it by name (dlsym). */
@@ -740,7 +740,7 @@ typedef struct mgx_sampling {
 } mgx_sampling;
 
 /* mgx_rollout_policy_episodes with the discrete head sampling by the rule of mgx_sampling: one launch of
- * rollout_policy_sample_episodes_kernel.  action_id_out receives the ids taken; prob_out: double [K, N], the probability of the id
+ * rollout_policy_head_episodes_kernel (sampling head).  action_id_out receives the ids taken; prob_out: double [K, N], the probability of the id
  * taken at every step, or NULL.  Every other argument, result and refusal as mgx_rollout_policy_episodes; on top MGX_ERR_INVALID for
  * a NULL sampling, sampling->struct_size != sizeof(mgx_sampling), a negative, infinite or NaN temperature.
  * An ADDITION to ABI 9 that leaves MGX_ABI_MINOR at 3: consumers find it by name (dlsym). */
@@ -763,7 +763,7 @@ typedef struct mgx_critic {
     const double *b;          /* device [P] */
 } mgx_critic;
 
-/* mgx_rollout_policy_sample_episodes with a critic: one launch of rollout_policy_critic_episodes_kernel.  Each of the three
+/* mgx_rollout_policy_sample_episodes with a critic: one launch of rollout_policy_head_episodes_kernel (sampling head with a critic).  Each of the three
  * outputs may be NULL:
  *   value_out        double [K, N]: V of the row the id of step k was chosen on (the row the policy reads at step k; after a
  *                    restart inside the launch the first row of the new episode)
@@ -868,7 +868,7 @@ typedef struct mgx_gaussian {
 } mgx_gaussian;
 
 /* mgx_step_k_policy_episodes with the Gaussian head of mgx_gaussian, and with `critic` the value head of mgx_critic: one launch of
- * step_k_policy_gaussian_episodes_kernel.  actions_out: double [K, N, A], the clipped controls taken; raw_actions_out: double
+ * step_k_policy_head_episodes_kernel (Gaussian head).  actions_out: double [K, N, A], the clipped controls taken; raw_actions_out: double
  * [K, N, A], the pre-clip actions raw; logp_out: double [K, N], their log-probability; each may be NULL.  critic == NULL: no values
  * -- value_out, final_value_out and last_value_out must then be NULL.  With a critic the three follow
  * mgx_rollout_policy_critic_episodes word for word (each may be NULL; untouched entries of final_value_out keep the caller's

@@ -25,17 +25,20 @@ UNITS = (
     ("mgx_step_episode_rows.hip", "MGX_EPISODE_PART", 2),               # ... and its continuous twin,
     ("mgx_policy_episodes.hip", "MGX_EPISODE_PART", 2),                 # ... the closed-loop roll-out (a policy inside the launch)
     ("mgx_step_policy_episodes.hip", "MGX_EPISODE_PART", 2),            # ... and its continuous twin,
-    ("mgx_policy_explore_episodes.hip", "MGX_EPISODE_PART", 2),         # ... the closed-loop roll-out with an exploring head
-    ("mgx_step_policy_explore_episodes.hip", "MGX_EPISODE_PART", 2),    # ... and its continuous twin,
-    ("mgx_policy_sample_episodes.hip", "MGX_EPISODE_PART", 2),          # ... the closed-loop roll-out with a softmax-sampling head
-    ("mgx_policy_critic_episodes.hip", "MGX_EPISODE_PART", 2),          # ... and that one with a critic beside the actor,
-    ("mgx_step_policy_gaussian_episodes.hip", "MGX_EPISODE_PART", 2),   # ... the continuous closed loop with a Gaussian head (+ critic),
+    ("mgx_policy_head_episodes.hip", "MGX_EPISODE_PART", 2),            # ... the closed-loop roll-out with a head (UNIT_HEADS)
+    ("mgx_step_policy_head_episodes.hip", "MGX_EPISODE_PART", 2),       # ... and its continuous twin,
     ("mgx_gae.hip", None, 1),                                           # the advantages of what such launches return (mgx_gae)
     ("mgx_lookahead_episodes.hip", "MGX_EPISODE_PART", 2),              # what-if roll-outs of candidate plans, nothing committed
     ("mgx_lookahead_step_episodes.hip", "MGX_EPISODE_PART", 2),         # ... and their continuous twin
     ("mgx_lookahead_gaussian_episodes.hip", "MGX_EPISODE_PART", 2),     # ... with the candidates drawn inside the launch (CEM)
     ("mgx_cem.hip", None, 1),                                           # ... its pick, the elites and the refit (mgx_cem_refit)
 )
+# ... of which these hold ONE kernel text for several heads (PolicyHead, csrc/mgx_policy.hpp): (the -D macro that selects a head, the
+# heads) -- sliced by head as well, one object per (head, slice): <file>_h<h>_<p>.o, each as long as the head's own unit used to be
+UNIT_HEADS = {
+    "mgx_policy_head_episodes.hip": ("MGX_POLICY_HEAD", (1, 2, 3)),         # exploring, sampling, sampling with a critic
+    "mgx_step_policy_head_episodes.hip": ("MGX_POLICY_HEAD", (1, 4, 5)),    # exploring, Gaussian, Gaussian with a critic
+}
 # everything a built library is stamped with (source_hash): a file missing here would leave a stale libmgx.so looking current
 SOURCES = [os.path.join(_PKG, "csrc", f) for f in [u[0] for u in UNITS] + ["mgx_kernels.hpp", "mgx_core.hpp", "mgx_step_hot.hpp", "mgx_episode_loop.hpp", "mgx_episode_rows.hpp", "mgx_policy.hpp", "mgx_gae.hpp", "mgx_lookahead.hpp", "mgx_cem.hpp"]] + \
           [os.path.join(_ROOT, "include", "mgx.h")]
@@ -381,9 +384,17 @@ def build(force=False, verbose=False, defs=(), lib_path=None, abi_only=False):
 
 
 def _units(objdir):
-    """[(source, its -D flag if any, object file in ``objdir``)] of every translation unit of UNITS, mgx_abi.hip first."""
-    return [(os.path.join(_PKG, "csrc", f), [f"-D{macro}={p}"] if macro else [], os.path.join(objdir, f[:-4] + (f"_{p}.o" if macro else ".o")))
-            for f, macro, parts in UNITS for p in range(parts)]
+    """[(source, its -D flags if any, object file in ``objdir``)] of every translation unit of UNITS, mgx_abi.hip first: one per
+    slice, of the files of UNIT_HEADS one per (head, slice)."""
+    out = []
+    for f, macro, parts in UNITS:
+        head_macro, heads = UNIT_HEADS.get(f, (None, (None,)))
+        for h in heads:
+            for p in range(parts):
+                defs = ([f"-D{head_macro}={h}"] if head_macro else []) + ([f"-D{macro}={p}"] if macro else [])
+                tag = (f"_h{h}" if head_macro else "") + (f"_{p}" if macro else "")
+                out.append((os.path.join(_PKG, "csrc", f), defs, os.path.join(objdir, f[:-4] + tag + ".o")))
+    return out
 
 
 def _build(LIB_PATH, extra_defs, verbose, objtag, force=True, abi_only=False):

@@ -2407,9 +2407,9 @@ static int critic_refusal(const CriticCall &cc, const char *fn, EpisodePolicyLau
     return MGX_OK;
 }
 
-// The closed-loop roll-out, greedy (no explore, no sampling: rollout_policy_episodes_kernel), exploring
-// (rollout_policy_explore_episodes_kernel), sampling (`sample`: rollout_policy_sample_episodes_kernel, which needs a
-// mgx_sampling) or sampling with a critic (`cc`, with `sample`: rollout_policy_critic_episodes_kernel): every check, then one launch.
+// The closed-loop roll-out, greedy (no explore, no sampling: rollout_policy_episodes_kernel) or with a head
+// (rollout_policy_head_episodes_kernel): exploring, sampling (`sample`, which needs a mgx_sampling) or sampling with a critic (`cc`,
+// with `sample`): every check, then one launch.
 static int rollout_policy_episodes_impl(mgx_handle *h, const mgx_policy *policy, const mgx_exploration *explore, bool sample,
                                         const mgx_sampling *sampling, const int32_t *table, int32_t n_actions, int32_t K, double *reward,
                                         uint8_t *done, double *soc_trace, uint32_t *status_trace, uint8_t *action_id_out,
@@ -2430,14 +2430,11 @@ static int rollout_policy_episodes_impl(mgx_handle *h, const mgx_policy *policy,
                                         "mgx_rollout_discrete", "mgx_step_lists", table, n_actions, &tab, P.r)) return rc;
     if (int rc = policy_dims_refusal(h, policy, tab.n_actions, 4, "n_actions", fn, P, cc != nullptr)) return rc;
     P.r.e.tab = &tab; P.actions_out = action_id_out; P.prob_out = prob_out;
-    const bool launched = cc        ? launch_rollout_policy_critic_episodes_p0(P) || launch_rollout_policy_critic_episodes_p1(P)
-                          : sample  ? launch_rollout_policy_sample_episodes_p0(P) || launch_rollout_policy_sample_episodes_p1(P)
-                          : explore ? launch_rollout_policy_explore_episodes_p0(P) || launch_rollout_policy_explore_episodes_p1(P)
-                                    : launch_rollout_policy_episodes_p0(P) || launch_rollout_policy_episodes_p1(P);
-    return finish_episode_launch(h, P.r.e, launched,
-                                 cc        ? "rollout_policy_critic_episodes_kernel launch"
-                                 : sample  ? "rollout_policy_sample_episodes_kernel launch"
-                                 : explore ? "rollout_policy_explore_episodes_kernel launch" : "rollout_policy_episodes_kernel launch", fn);
+    P.head = cc ? HEAD_SAMPLE_CRITIC : sample ? HEAD_SAMPLE : explore ? HEAD_EXPLORE : HEAD_GREEDY;
+    const bool launched = P.head == HEAD_GREEDY ? launch_rollout_policy_episodes_p0(P) || launch_rollout_policy_episodes_p1(P)
+                                                : launch_rollout_policy_head_episodes_p<0>(P) || launch_rollout_policy_head_episodes_p<1>(P);
+    return finish_episode_launch(h, P.r.e, launched, P.head == HEAD_GREEDY ? "rollout_policy_episodes_kernel launch"
+                                                                           : "rollout_policy_head_episodes_kernel launch", fn);
 }
 
 int mgx_rollout_policy_episodes(mgx_handle *h, const mgx_policy *policy, const int32_t *table, int32_t n_actions, int32_t K,
@@ -2511,13 +2508,12 @@ static int gaussian_refusal(const GaussianCall &gc, const char *fn, EpisodePolic
             return fail(MGX_ERR_INVALID, "%s: a value output without a critic", fn);
         return MGX_OK;
     }
-    P.critic = true;
     return critic_refusal(cc, fn, P);
 }
 
-// The closed-loop continuous K-step, greedy (explore == NULL: step_k_policy_episodes_kernel), exploring
-// (step_k_policy_explore_episodes_kernel) or Gaussian (`gc`: step_k_policy_gaussian_episodes_kernel, which needs a mgx_gaussian and
-// takes a critic): every check, then one launch.
+// The closed-loop continuous K-step, greedy (explore == NULL: step_k_policy_episodes_kernel) or with a head
+// (step_k_policy_head_episodes_kernel): exploring or Gaussian (`gc`, which needs a mgx_gaussian and takes a critic): every check,
+// then one launch.
 static int step_k_policy_episodes_impl(mgx_handle *h, const mgx_policy *policy, const mgx_exploration *explore, int32_t K, double *reward,
                                        uint8_t *done, double *soc_trace, uint32_t *status_trace, double *actions_out,
                                        const mgx_episode_stats *stats, const mgx_episode_rows *rows, mgx_stream stream, const char *fn,
@@ -2527,6 +2523,7 @@ static int step_k_policy_episodes_impl(mgx_handle *h, const mgx_policy *policy, 
     if (int rc = policy_struct_refusal(policy, fn)) return rc;
     const mgx_episode_rows none{(int32_t)sizeof(mgx_episode_rows), 0, nullptr, nullptr};
     EpisodePolicyLaunch P{};
+    P.head = gc ? (gc->cc->critic ? HEAD_GAUSSIAN_CRITIC : HEAD_GAUSSIAN) : explore ? HEAD_EXPLORE : HEAD_GREEDY;
     if (gc) {                                                    // (what needs no handle first)
         if (int rc = gaussian_refusal(*gc, fn, P)) return rc;
         if (!h) return fail(MGX_ERR_INVALID, "%s: NULL argument", fn);
@@ -2536,14 +2533,12 @@ static int step_k_policy_episodes_impl(mgx_handle *h, const mgx_policy *policy, 
                                         "mgx_step", nullptr, 0, nullptr, P.r)) return rc;
     if (h->k.act_f32)
         return fail(MGX_ERR_UNSUPPORTED, "%s: the handle's action format is float32 (mgx_set_action_format); the policy's controls are doubles", fn);
-    if (int rc = policy_dims_refusal(h, policy, h->action_dim, 1, "mgx_action_dim", fn, P, P.critic)) return rc;
+    if (int rc = policy_dims_refusal(h, policy, h->action_dim, 1, "mgx_action_dim", fn, P, head_has_critic(P.head))) return rc;
     P.actions_out = actions_out;
-    const bool launched = gc        ? launch_step_k_policy_gaussian_episodes_p0(P) || launch_step_k_policy_gaussian_episodes_p1(P)
-                          : explore ? launch_step_k_policy_explore_episodes_p0(P) || launch_step_k_policy_explore_episodes_p1(P)
-                                    : launch_step_k_policy_episodes_p0(P) || launch_step_k_policy_episodes_p1(P);
-    return finish_episode_launch(h, P.r.e, launched,
-                                 gc        ? "step_k_policy_gaussian_episodes_kernel launch"
-                                 : explore ? "step_k_policy_explore_episodes_kernel launch" : "step_k_policy_episodes_kernel launch", fn);
+    const bool launched = P.head == HEAD_GREEDY ? launch_step_k_policy_episodes_p0(P) || launch_step_k_policy_episodes_p1(P)
+                                                : launch_step_k_policy_head_episodes_p<0>(P) || launch_step_k_policy_head_episodes_p<1>(P);
+    return finish_episode_launch(h, P.r.e, launched, P.head == HEAD_GREEDY ? "step_k_policy_episodes_kernel launch"
+                                                                           : "step_k_policy_head_episodes_kernel launch", fn);
 }
 
 int mgx_step_k_policy_episodes(mgx_handle *h, const mgx_policy *policy, int32_t K, double *reward, uint8_t *done,

@@ -2,14 +2,13 @@
 // mgx_step_k_policy_episodes: mgx_step_policy_episodes.hip): the policy of include/mgx.h (a small fp64 network of plain IEEE
 // operations) staged in LDS once per workgroup and evaluated per lane between "row of the coming step" and "step", and the
 // lane's row strip -- the H = 0 row is built ONCE per step into the wave's tile, read back as the policy's input and, where
-// the launch returns observations, streamed out of the same tile as the row the step before returned.  Their exploring twins
-// (mgx_rollout_policy_explore_episodes: mgx_policy_explore_episodes.hip, mgx_step_k_policy_explore_episodes:
-// mgx_step_policy_explore_episodes.hip) add the draw, the epsilon choice and the noise of mgx_exploration, each stated once below;
-// the sampling twin of the discrete launch (mgx_rollout_policy_sample_episodes: mgx_policy_sample_episodes.hip) the exp and the
-// softmax-sampling head of mgx_sampling; the critic twin of that one (mgx_rollout_policy_critic_episodes:
-// mgx_policy_critic_episodes.hip) the value head of mgx_critic, in functions of its own; the Gaussian twin of the continuous launch
-// (mgx_step_k_policy_gaussian_episodes: mgx_step_policy_gaussian_episodes.hip) the log, the quarter turn, the normal pair and the
-// head of mgx_gaussian.
+// the launch returns observations, streamed out of the same tile as the row the step before returned.  Their twins with
+// a head on the policy's outputs (one kernel text per family, the head a template argument: mgx_policy_head_episodes.hip,
+// mgx_step_policy_head_episodes.hip) add, each stated once below: the exploring heads (mgx_rollout_policy_explore_episodes,
+// mgx_step_k_policy_explore_episodes) the draw, the epsilon choice and the noise of mgx_exploration; the sampling head of the
+// discrete launch (mgx_rollout_policy_sample_episodes) the exp and the softmax-sampling head of mgx_sampling; that head with a
+// critic (mgx_rollout_policy_critic_episodes) the value head of mgx_critic, in functions of its own; the Gaussian heads of the
+// continuous launch (mgx_step_k_policy_gaussian_episodes) the log, the quarter turn, the normal pair and the head of mgx_gaussian.
 // On top of mgx_episode_rows.hpp (the rows) and, through it, mgx_episode_loop.hpp (what all six episode loops share).
 #pragma once
 #include "mgx_episode_rows.hpp"
@@ -148,8 +147,8 @@ __device__ __forceinline__ int32_t policy_argmax(const double (&y)[NO], int32_t 
 // the continuous head: a normalised control
 __device__ __forceinline__ double policy_clip(double y) { return !(y > 0.0) ? 0.0 : (y > 1.0 ? 1.0 : y); }
 
-// ---- exploration: the rule of mgx_exploration (include/mgx.h), for the two exploring kernels (mgx_policy_explore_episodes.hip,
-// mgx_step_policy_explore_episodes.hip).  Every piece is a function of (seed, grid, step counter, number) and of values the step
+// ---- exploration: the rule of mgx_exploration (include/mgx.h), for the exploring heads (mgx_policy_head_episodes.hip,
+// mgx_step_policy_head_episodes.hip).  Every piece is a function of (seed, grid, step counter, number) and of values the step
 // has at hand: a draw is formed where it is used and holds no register across the step. ----
 // mgx_exploration as the kernels see it, by value in their argument struct
 struct ExploreArgs {
@@ -195,7 +194,7 @@ __device__ __forceinline__ double policy_noisy_clip(double y, double s, uint64_t
     return policy_clip(y + s * z);
 }
 
-// ---- sampling: the rule of mgx_sampling (include/mgx.h), for rollout_policy_sample_episodes_kernel (mgx_policy_sample_episodes.hip) ----
+// ---- sampling: the rule of mgx_sampling (include/mgx.h), for the sampling heads of rollout_policy_head_episodes_kernel (mgx_policy_head_episodes.hip) ----
 // mgx_sampling as the kernel sees it, by value in its argument struct
 struct SampleArgs {
     uint64_t seed;
@@ -277,7 +276,7 @@ __device__ __forceinline__ int32_t policy_sample(double (&y)[NO], int32_t no, do
     return id;
 }
 
-// ---- the critic: the rule of mgx_critic (include/mgx.h), for rollout_policy_critic_episodes_kernel (mgx_policy_critic_episodes.hip).
+// ---- the critic: the rule of mgx_critic (include/mgx.h), for the heads with a critic (HEAD_SAMPLE_CRITIC, HEAD_GAUSSIAN_CRITIC).
 // New functions beside the ones above, which the greedy, exploring and sampling kernels keep to themselves. ----
 // mgx_critic as the kernel sees it, by value in its argument struct
 struct CriticArgs {
@@ -403,8 +402,8 @@ __device__ __forceinline__ double policy_value(const double *w, int32_t nh, int3
     return val;
 }
 
-// ---- the Gaussian head: the rule of mgx_gaussian (include/mgx.h), for step_k_policy_gaussian_episodes_kernel
-// (mgx_step_policy_gaussian_episodes.hip).  New functions beside the ones above; log, sine and cosine are fixed sequences of IEEE
+// ---- the Gaussian head: the rule of mgx_gaussian (include/mgx.h), for the Gaussian heads of step_k_policy_head_episodes_kernel
+// (mgx_step_policy_head_episodes.hip).  New functions beside the ones above; log, sine and cosine are fixed sequences of IEEE
 // operations (the build has -ffp-contract=off), and so is the square root (policy_sqrt); the division is the correctly rounded one. ----
 // mgx_gaussian as the kernel sees it, by value in its argument struct
 struct GaussianArgs {
@@ -667,7 +666,36 @@ struct StepPolicyGaussianArgs {
     double *last_value_out;                // [N] or NULL
 };
 
-// ---- host side: what mgx_abi.hip hands the slices of the six translation units ----
+// The head of a closed-loop launch: what the two head kernels (mgx_policy_head_episodes.hip: exploring, sampling, sampling with a
+// critic; mgx_step_policy_head_episodes.hip: exploring, Gaussian, Gaussian with a critic) take as their last template argument and
+// their objects as -DMGX_POLICY_HEAD.  The greedy kernels (mgx_policy_episodes.hip, mgx_step_policy_episodes.hip) take none.
+enum PolicyHead : int { HEAD_GREEDY = 0, HEAD_EXPLORE = 1, HEAD_SAMPLE = 2, HEAD_SAMPLE_CRITIC = 3, HEAD_GAUSSIAN = 4, HEAD_GAUSSIAN_CRITIC = 5 };
+constexpr bool head_has_critic(int head) { return head == HEAD_SAMPLE_CRITIC || head == HEAD_GAUSSIAN_CRITIC; }
+
+// ... and the struct each head's kernel takes: every head keeps the layout of its kernarg segment
+template <int HEAD>
+using RolloutPolicyHeadArgs = std::conditional_t<HEAD == HEAD_EXPLORE, RolloutPolicyExploreArgs,
+                              std::conditional_t<HEAD == HEAD_SAMPLE, RolloutPolicySampleArgs, RolloutPolicyCriticArgs>>;
+template <int HEAD>
+using StepPolicyHeadArgs = std::conditional_t<HEAD == HEAD_EXPLORE, StepPolicyExploreArgs, StepPolicyGaussianArgs>;
+
+// The path from a head's struct to a part the heads share, stated once per struct: `greedy_part` the greedy kernel's struct at its
+// front, `sampling_part` the sampling kernel's (of the heads that sample).  Each for the parameter and for late_kernargs' view of
+// the kernarg segment (its address space), so the kernels' text spells no path of one head.
+#define MGX_KERNARG __attribute__((address_space(4)))
+#define MGX_ARGS_PART(FN, ARGS, PART, PATH)                                                                      \
+    __host__ __device__ __forceinline__ const PART &FN(const ARGS &x) { return PATH; }                          \
+    __device__ __forceinline__ const MGX_KERNARG PART &FN(const MGX_KERNARG ARGS &x) { return PATH; }
+MGX_ARGS_PART(greedy_part, RolloutPolicyExploreArgs, RolloutPolicyArgs, x.g)
+MGX_ARGS_PART(greedy_part, RolloutPolicySampleArgs, RolloutPolicyArgs, x.g)
+MGX_ARGS_PART(greedy_part, RolloutPolicyCriticArgs, RolloutPolicyArgs, x.s.g)
+MGX_ARGS_PART(greedy_part, StepPolicyExploreArgs, StepPolicyArgs, x.g)
+MGX_ARGS_PART(greedy_part, StepPolicyGaussianArgs, StepPolicyArgs, x.g)
+MGX_ARGS_PART(sampling_part, RolloutPolicySampleArgs, RolloutPolicySampleArgs, x)
+MGX_ARGS_PART(sampling_part, RolloutPolicyCriticArgs, RolloutPolicySampleArgs, x.s)
+#undef MGX_ARGS_PART
+
+// ---- host side: what mgx_abi.hip hands the slices of the translation units ----
 struct EpisodePolicyLaunch {
     EpisodeRowsLaunch r;             // as for the kernels with rows (obs / final_obs may both be NULL here)
     PolicyArgs pol;
@@ -678,16 +706,35 @@ struct EpisodePolicyLaunch {
     double *prob_out;
     CriticArgs cr;                   // ... the critic kernel alone the rest (lds_bytes / pol.stride then hold policy_critic_set_doubles)
     double *value_out, *final_value_out, *last_value_out;
-    GaussianArgs gs;                 // ... the Gaussian kernel these, `cr` and the three outputs above with `critic`
+    GaussianArgs gs;                 // ... the Gaussian kernel these, `cr` and the three outputs above with its critic
     double *raw_out, *logp_out;
-    bool critic;
+    int head;                        // PolicyHead: which kernel of the family
 };
 bool launch_rollout_policy_episodes_p0(const EpisodePolicyLaunch &L); bool launch_rollout_policy_episodes_p1(const EpisodePolicyLaunch &L);
 bool launch_step_k_policy_episodes_p0(const EpisodePolicyLaunch &L); bool launch_step_k_policy_episodes_p1(const EpisodePolicyLaunch &L);
-bool launch_rollout_policy_explore_episodes_p0(const EpisodePolicyLaunch &L); bool launch_rollout_policy_explore_episodes_p1(const EpisodePolicyLaunch &L);
-bool launch_step_k_policy_explore_episodes_p0(const EpisodePolicyLaunch &L); bool launch_step_k_policy_explore_episodes_p1(const EpisodePolicyLaunch &L);
-bool launch_rollout_policy_sample_episodes_p0(const EpisodePolicyLaunch &L); bool launch_rollout_policy_sample_episodes_p1(const EpisodePolicyLaunch &L);
-bool launch_rollout_policy_critic_episodes_p0(const EpisodePolicyLaunch &L); bool launch_rollout_policy_critic_episodes_p1(const EpisodePolicyLaunch &L);
-bool launch_step_k_policy_gaussian_episodes_p0(const EpisodePolicyLaunch &L); bool launch_step_k_policy_gaussian_episodes_p1(const EpisodePolicyLaunch &L);
+// ... and of the two head files, whose objects hold one head of one slice each (-DMGX_POLICY_HEAD=h -DMGX_EPISODE_PART=p) and define
+// their instance of these; the launch of slice PART of a family picks the instance of the launch's head
+template <int HEAD, int PART> bool launch_rollout_policy_head_episodes(const EpisodePolicyLaunch &L);
+template <int HEAD, int PART> bool launch_step_k_policy_head_episodes(const EpisodePolicyLaunch &L);
+template <int PART>
+inline bool launch_rollout_policy_head_episodes_p(const EpisodePolicyLaunch &L)
+{
+    switch (L.head) {
+        case HEAD_EXPLORE: return launch_rollout_policy_head_episodes<HEAD_EXPLORE, PART>(L);
+        case HEAD_SAMPLE: return launch_rollout_policy_head_episodes<HEAD_SAMPLE, PART>(L);
+        case HEAD_SAMPLE_CRITIC: return launch_rollout_policy_head_episodes<HEAD_SAMPLE_CRITIC, PART>(L);
+        default: return false;
+    }
+}
+template <int PART>
+inline bool launch_step_k_policy_head_episodes_p(const EpisodePolicyLaunch &L)
+{
+    switch (L.head) {
+        case HEAD_EXPLORE: return launch_step_k_policy_head_episodes<HEAD_EXPLORE, PART>(L);
+        case HEAD_GAUSSIAN: return launch_step_k_policy_head_episodes<HEAD_GAUSSIAN, PART>(L);
+        case HEAD_GAUSSIAN_CRITIC: return launch_step_k_policy_head_episodes<HEAD_GAUSSIAN_CRITIC, PART>(L);
+        default: return false;
+    }
+}
 
 }  // namespace mgx

@@ -2,6 +2,7 @@
 // rollout_episodes_rows_kernel (mgx_episode_rows.hip) with the priority-list id of every step chosen inside the launch, by the
 // policy of include/mgx.h applied to the row the grid stands on.  One of the six translation units of mgx_episode_loop.hpp, which
 // states what their loops share and how a unit is compiled; what the rows add is in mgx_episode_rows.hpp, the policy in mgx_policy.hpp.
+// This loop with a head on the policy's outputs (exploring, sampling, sampling with a critic): mgx_policy_head_episodes.hip.
 #include "mgx_policy.hpp"
 
 namespace mgx {

@@ -3,6 +3,7 @@
 // chosen inside the launch, by the policy of include/mgx.h applied to the row the grid stands on.  The continuous twin of
 // rollout_policy_episodes_kernel (mgx_policy_episodes.hip).  One of the six translation units of mgx_episode_loop.hpp, which states
 // what their loops share and how a unit is compiled; what the rows add is in mgx_episode_rows.hpp, the policy in mgx_policy.hpp.
+// This loop with a head on the policy's outputs (exploring, Gaussian, Gaussian with a critic): mgx_step_policy_head_episodes.hip.
 #include "mgx_policy.hpp"
 
 namespace mgx {

@@ -35,7 +35,8 @@ def test_c_abi_exports_every_declared_symbol():
 
 def test_every_source_is_hashed_and_every_hip_file_is_compiled_once():
     """A file under csrc/ that ``_lib.SOURCES`` forgets is left out of ``source_hash()``: a stale libmgx.so would pass for current.
-    Every ``.hip`` is the file of exactly one entry of ``_lib.UNITS``, and ``_units`` compiles every entry."""
+    Every ``.hip`` is the file of exactly one entry of ``_lib.UNITS``, and ``_units`` compiles every entry: once per slice, a file
+    of ``_lib.UNIT_HEADS`` once per (head, slice)."""
     from pymgrid_amd import _lib
     csrc = os.path.join(ROOT, "pymgrid_amd", "csrc")
     on_disk = {os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith((".hip", ".hpp"))}      # (not _build*: directories)
@@ -51,10 +52,14 @@ def test_every_source_is_hashed_and_every_hip_file_is_compiled_once():
     for src, defs, obj in units:
         compiled.setdefault(os.path.basename(src), []).append((tuple(defs), obj))
     assert sorted(compiled) == hip
+    assert set(_lib.UNIT_HEADS) <= {u[0] for u in _lib.UNITS}
     for f, macro, parts in _lib.UNITS:
         assert parts >= 1 and (macro is not None or parts == 1)
-        assert len(compiled[f]) == parts
-        assert [d for d, _ in compiled[f]] == [((f"-D{macro}={p}",) if macro else ()) for p in range(parts)]
+        head_macro, heads = _lib.UNIT_HEADS.get(f, (None, (None,)))
+        assert len(heads) == len(set(heads)) >= 1 and (head_macro is None) == (f not in _lib.UNIT_HEADS)
+        assert len(compiled[f]) == len(heads) * parts
+        assert [d for d, _ in compiled[f]] == [((f"-D{head_macro}={h}",) if head_macro else ()) + ((f"-D{macro}={p}",) if macro else ())
+                                               for h in heads for p in range(parts)]
     assert len({obj for _, _, obj in units}) == len(units)
     assert os.path.basename(units[0][0]) == "mgx_abi.hip"          # (abi_only variants compile the first unit alone)
 

@@ -14,7 +14,7 @@ import torch
 
 from test_episode_rows import HostStats, _same_bits, _snapshot, _state_equal, _untouched
 from test_policy_explore import DOCUMENTED as EXPLORE_DOCUMENTED
-from test_policy_explore import _compare, _envs_equal
+from test_policy_explore import _compare, _envs_equal, _forms_of
 from test_policy_rollout import DOCUMENTED as GREEDY_DOCUMENTED
 from test_policy_rollout import WANT, _batch, _c_policy, _n_out, _policy
 from test_policy_sample import CASES, LAUNCHES, N
@@ -240,8 +240,9 @@ def test_symbols_struct_and_header():
         header = fh.read()
     for name in ("mgx_rollout_policy_critic_episodes", "mgx_gae"):
         assert name in _lib.SYMBOLS and getattr(L, name) is not None and f"int {name}(" in header
-    assert "mgx_policy_critic_episodes.hip" in [u[0] for u in _lib.UNITS] and "mgx_gae.hip" in [u[0] for u in _lib.UNITS]
-    assert all(any(src.endswith(f) for src in _lib.SOURCES) for f in ("mgx_policy_critic_episodes.hip", "mgx_gae.hip"))
+    assert "mgx_policy_head_episodes.hip" in [u[0] for u in _lib.UNITS] and "mgx_gae.hip" in [u[0] for u in _lib.UNITS]
+    assert SAMPLE_CRITIC in _lib.UNIT_HEADS["mgx_policy_head_episodes.hip"][1]
+    assert all(any(src.endswith(f) for src in _lib.SOURCES) for f in ("mgx_policy_head_episodes.hip", "mgx_gae.hip"))
     assert _lib.lib().mgx_abi_minor() == 3 == _lib.ABI_MINOR and _lib.lib().mgx_abi_version() == 9
     # the three structs before it keep their sizes
     assert C.sizeof(_lib.Policy) == 24 + 5 * C.sizeof(C.c_void_p) and C.sizeof(_lib.Exploration) == 64 and C.sizeof(_lib.Sampling) == 32
@@ -260,13 +261,14 @@ def test_symbols_struct_and_header():
     assert b"mgx_gae" in lib.mgx_last_error()
 
 
-DOCUMENTED = {   # kernel: (forms, most AGPRs, most spilled SGPRs, least occupancy in waves per SIMD) -- the figures of DESIGN.md
-    "rollout_policy_critic_episodes_kernel": (30, 59, 65, 1),
+SAMPLE_CRITIC = 3    # PolicyHead (csrc/mgx_policy.hpp)
+DOCUMENTED = {   # (kernel, head): (forms, most AGPRs, most spilled SGPRs, least occupancy in waves per SIMD) -- the figures of DESIGN.md
+    ("rollout_policy_head_episodes_kernel", SAMPLE_CRITIC): (30, 59, 65, 1),
 }
 
 
 def test_the_critic_kernel_uses_what_design_md_says():
-    """The 30 new forms (ten layouts x three row sources): no scratch memory, no vector register spilled, vgpr + agpr <= 512, LDS
+    """The 30 forms of the sampling head with a critic (ten layouts x three row sources): no scratch memory, no vector register spilled, vgpr + agpr <= 512, LDS
     within the siblings' bound; AGPRs, spilled SGPRs and occupancy no worse than DESIGN.md's kernel table records them.  The greedy,
     exploring and sampling kernels keep exactly the figures their own tests record."""
     from pymgrid_amd import _lib
@@ -278,9 +280,9 @@ def test_the_critic_kernel_uses_what_design_md_says():
         design = fh.read()
 
     def forms_of(kernel):
-        return {name: u for name, u in usage.items() if name.split("<")[0].split("::")[-1] == kernel}
+        return _forms_of(usage, kernel)
     for kernel, (n_forms, agpr, sgpr_spill, occupancy) in DOCUMENTED.items():
-        assert f"`{kernel}<7,4,0>`" in design
+        assert f"`{kernel[0]}<7,4,0,{kernel[1]}>`" in design
         forms = forms_of(kernel)
         assert len(forms) == n_forms, (kernel, sorted(forms))
         for name, u in forms.items():

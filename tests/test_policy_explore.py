@@ -149,14 +149,23 @@ def test_symbols_struct_and_header():
     assert b"mgx_step_k_policy_explore_episodes" in lib.mgx_last_error()
 
 
-DOCUMENTED = {   # kernel: (forms, most AGPRs, most spilled SGPRs, least occupancy in waves per SIMD) -- the figures of DESIGN.md
-    "rollout_policy_explore_episodes_kernel": (30, 52, 10, 1),
-    "step_k_policy_explore_episodes_kernel": (30, 0, 23, 2),
+EXPLORE = 1     # PolicyHead (csrc/mgx_policy.hpp): the last template argument of the two head kernels
+DOCUMENTED = {   # (kernel, head): (forms, most AGPRs, most spilled SGPRs, least occupancy in waves per SIMD) -- the figures of DESIGN.md
+    ("rollout_policy_head_episodes_kernel", EXPLORE): (30, 52, 10, 1),
+    ("step_k_policy_head_episodes_kernel", EXPLORE): (30, 0, 23, 2),
 }
 
 
+def _forms_of(usage, kernel):
+    """The forms of ``kernel`` in a table of ``_lib.resource_usage()``: a kernel's name, or (name of a head kernel, head) for the
+    forms of that head alone."""
+    kernel, head = kernel if isinstance(kernel, tuple) else (kernel, None)
+    return {name: u for name, u in usage.items()
+            if name.split("<")[0].split("::")[-1] == kernel and (head is None or name.endswith(f", {head}>"))}
+
+
 def test_the_exploring_kernels_use_what_design_md_says():
-    """The 60 new forms (two kernels x ten layouts x three row sources): no scratch memory, no vector register spilled; AGPRs,
+    """The 60 forms of the exploring head (two kernels x ten layouts x three row sources): no scratch memory, no vector register spilled; AGPRs,
     spilled SGPRs and occupancy no worse than DESIGN.md's kernel table records them."""
     from pymgrid_amd import _lib
     _lib.build()
@@ -166,8 +175,8 @@ def test_the_exploring_kernels_use_what_design_md_says():
     with open(os.path.join(ROOT, "DESIGN.md")) as fh:
         design = fh.read()
     for kernel, (n_forms, agpr, sgpr_spill, occupancy) in DOCUMENTED.items():
-        assert f"`{kernel}<7,4,0>`" in design
-        forms = {name: u for name, u in usage.items() if name.split("<")[0].split("::")[-1] == kernel}
+        assert f"`{kernel[0]}<7,4,0,{kernel[1]}>`" in design
+        forms = _forms_of(usage, kernel)
         assert len(forms) == n_forms, (kernel, sorted(forms))
         for name, u in forms.items():
             assert u["scratch"] == 0 and u["vgpr_spill"] == 0, (name, u)

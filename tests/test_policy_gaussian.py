@@ -12,7 +12,7 @@ import pytest
 import torch
 
 from test_episode_rows import HostStats, _same_bits, _snapshot, _state_equal, _untouched
-from test_policy_explore import _compare, _envs_equal
+from test_policy_explore import _compare, _envs_equal, _forms_of
 from test_policy_rollout import WANT, _c_policy, _envs, _policy
 
 F64, F32 = torch.float64, torch.float32
@@ -341,12 +341,13 @@ def test_refusals_of_the_c_abi_and_of_the_python_surface(device):
 
 
 # ---- what the compiler made of the new forms -----------------------------------------------------------------------------------------
-# kernel: (forms, most AGPRs, most spilled SGPRs, least occupancy in waves per SIMD) without / with the critic -- DESIGN.md's table
-DOCUMENTED = {False: (30, 0, 48, 2), True: (30, 0, 51, 2)}
+# head (PolicyHead, csrc/mgx_policy.hpp: Gaussian, Gaussian with a critic): (forms, most AGPRs, most spilled SGPRs, least occupancy
+# in waves per SIMD) -- DESIGN.md's table
+DOCUMENTED = {4: (30, 0, 48, 2), 5: (30, 0, 51, 2)}
 
 
 def test_the_gaussian_kernel_uses_what_design_md_says():
-    """The 60 new forms (ten layouts x three row sources, without and with the critic): no scratch memory, no vector register spilled,
+    """The 60 forms of the Gaussian heads (ten layouts x three row sources, without and with the critic): no scratch memory, no vector register spilled,
     vgpr + agpr <= 512, LDS within the siblings' bound; AGPRs, spilled SGPRs and occupancy no worse than DESIGN.md records them."""
     from pymgrid_amd import _lib
     _lib.build()
@@ -355,12 +356,11 @@ def test_the_gaussian_kernel_uses_what_design_md_says():
         pytest.skip("libmgx.so was not built on this machine (no resource_usage.json beside the objects)")
     with open(os.path.join(ROOT, "DESIGN.md")) as fh:
         design = fh.read()
-    kernel = "step_k_policy_gaussian_episodes_kernel"
-    assert f"`{kernel}<7,4,0,false>`" in design and f"`{kernel}<7,4,0,true>`" in design
-    mine = {name: u for name, u in usage.items() if name.split("<")[0].split("::")[-1] == kernel}
-    for critic, (n_forms, agpr, sgpr_spill, occupancy) in DOCUMENTED.items():
-        forms = {name: u for name, u in mine.items() if name.endswith(", true>" if critic else ", false>")}
-        assert len(forms) == n_forms, (critic, sorted(forms))
+    kernel = "step_k_policy_head_episodes_kernel"
+    assert f"`{kernel}<7,4,0,4>`" in design and f"`{kernel}<7,4,0,5>`" in design
+    for head, (n_forms, agpr, sgpr_spill, occupancy) in DOCUMENTED.items():
+        forms = _forms_of(usage, (kernel, head))
+        assert len(forms) == n_forms, (head, sorted(forms))
         for name, u in forms.items():
             assert u["scratch"] == 0 and u["vgpr_spill"] == 0, (name, u)
             assert u["vgpr"] <= 256 and u["agpr"] <= agpr and u["vgpr"] + u["agpr"] <= 512, (name, u)

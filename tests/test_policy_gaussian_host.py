@@ -310,8 +310,9 @@ def test_symbols_struct_and_header():
     assert "typedef struct mgx_gaussian" in header and header.count("L(a), for a positive NORMAL double a") == 1
     assert header.count("S(v), for a finite double v") == 1 and "0x5FE6EB50C7B537A9" in header
     assert _lib.lib().mgx_abi_minor() == 3 == _lib.ABI_MINOR
-    assert "mgx_step_policy_gaussian_episodes.hip" in [u[0] for u in _lib.UNITS]
-    assert any(src.endswith("mgx_step_policy_gaussian_episodes.hip") for src in _lib.SOURCES)
+    assert "mgx_step_policy_head_episodes.hip" in [u[0] for u in _lib.UNITS]
+    assert {4, 5} <= set(_lib.UNIT_HEADS["mgx_step_policy_head_episodes.hip"][1])      # (PolicyHead: Gaussian, Gaussian with a critic)
+    assert any(src.endswith("mgx_step_policy_head_episodes.hip") for src in _lib.SOURCES)
     fields = re.search(r"typedef struct mgx_gaussian \{(.*?)\} mgx_gaussian;", header, re.S).group(1)
     fields = re.sub(r"/\*.*?\*/", "", fields, flags=re.S)
     assert re.findall(r"([a-z_]+)(?:\[4\])?;", fields) == [n for n, _ in _lib.Gaussian._fields_]

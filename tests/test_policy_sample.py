@@ -14,7 +14,7 @@ import torch
 
 from test_episode_rows import HostStats, _same_bits, _snapshot, _state_equal, _untouched
 from test_policy_explore import DOCUMENTED as EXPLORE_DOCUMENTED
-from test_policy_explore import _compare, _envs_equal
+from test_policy_explore import _compare, _envs_equal, _forms_of
 from test_policy_rollout import DOCUMENTED as GREEDY_DOCUMENTED
 from test_policy_rollout import WANT, _batch, _c_policy, _n_out, _policy
 
@@ -283,13 +283,14 @@ def test_symbol_struct_and_header():
     assert b"mgx_rollout_policy_sample_episodes" in lib.mgx_last_error()
 
 
-DOCUMENTED = {   # kernel: (forms, most AGPRs, most spilled SGPRs, least occupancy in waves per SIMD) -- the figures of DESIGN.md
-    "rollout_policy_sample_episodes_kernel": (30, 52, 41, 1),
+SAMPLE = 2      # PolicyHead (csrc/mgx_policy.hpp)
+DOCUMENTED = {   # (kernel, head): (forms, most AGPRs, most spilled SGPRs, least occupancy in waves per SIMD) -- the figures of DESIGN.md
+    ("rollout_policy_head_episodes_kernel", SAMPLE): (30, 52, 41, 1),
 }
 
 
 def test_the_sampling_kernel_uses_what_design_md_says():
-    """The 30 new forms (ten layouts x three row sources): no scratch memory, no vector register spilled, LDS within the siblings'
+    """The 30 forms of the sampling head (ten layouts x three row sources): no scratch memory, no vector register spilled, LDS within the siblings'
     bound; AGPRs, spilled SGPRs and occupancy no worse than DESIGN.md's kernel table records them.  The greedy and exploring
     kernels keep the figures their own tests record."""
     from pymgrid_amd import _lib
@@ -301,9 +302,9 @@ def test_the_sampling_kernel_uses_what_design_md_says():
         design = fh.read()
 
     def forms_of(kernel):
-        return {name: u for name, u in usage.items() if name.split("<")[0].split("::")[-1] == kernel}
+        return _forms_of(usage, kernel)
     for kernel, (n_forms, agpr, sgpr_spill, occupancy) in DOCUMENTED.items():
-        assert f"`{kernel}<7,4,0>`" in design
+        assert f"`{kernel[0]}<7,4,0,{kernel[1]}>`" in design
         forms = forms_of(kernel)
         assert len(forms) == n_forms, (kernel, sorted(forms))
         for name, u in forms.items():

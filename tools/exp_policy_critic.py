@@ -183,8 +183,8 @@ def main():
                   f"    (g) mgx_gae, [{K}, {N}] with final_value and returns: {fmt(us['g'])} us per call = {g_us / K:.3f} us per env-step; "
                   f"{moved / 1e6:.1f} MB moved, {moved / g_us / 1e6:.3f} TB/s = {moved / g_us / 1e6 / 8.0:.3f} of the 8 TB/s peak; "
                   f"the torch loop (a3) takes {med['a3'] * K:.1f} us per call: {med['a3'] * K / g_us:.1f}x"]
-        for kernel in ("rollout_policy_sample", "rollout_policy_critic"):
-            name = f"mgx::{kernel}_episodes_kernel<{flags}, {4 if flags & 4 else 8}, 0>"
+        for head in (2, 3):                                       # (HEAD_SAMPLE, HEAD_SAMPLE_CRITIC)
+            name = f"mgx::rollout_policy_head_episodes_kernel<{flags}, {4 if flags & 4 else 8}, 0, {head}>"
             if name in usage:
                 lines.append(f"#   {name}: {json.dumps(usage[name], sort_keys=True)}")
         if flags == 7:

@@ -102,7 +102,7 @@ def main():
                       f"    (z)/(g) = {med['z'] / med['g']:.3f}   (x)/(g) = {med['x'] / med['g']:.3f}   (z) - (g) = {med['z'] - med['g']:.3f} us per step "
                       f"= {per_draw:.1f} ps per draw (chip-wide)"]
             for name in (f"mgx::{kernel}_episodes_kernel<{flags}, {4 if flags & 4 else 8}, 0>",
-                         f"mgx::{kernel}_explore_episodes_kernel<{flags}, {4 if flags & 4 else 8}, 0>"):
+                         f"mgx::{kernel}_head_episodes_kernel<{flags}, {4 if flags & 4 else 8}, 0, 1>"):      # (1: HEAD_EXPLORE)
                 if name in usage:
                     lines.append(f"#   {name}: {json.dumps(usage[name], sort_keys=True)}")
             results.append(dict(layout=flags, head=head, n_out=int(n_out), draws=draws, **{k: round(v, 4) for k, v in med.items()}))

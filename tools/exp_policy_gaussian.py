@@ -155,9 +155,9 @@ def main():
               f"    (n) - (x) = {med['n'] - med['x']:.3f} us per step   (n)/(x) = {med['n'] / med['x']:.3f}   (v) - (n) = {med['v'] - med['n']:.3f}   "
               f"(t)/(n) = {med['t'] / med['n']:.1f}   (t)/(v) = {med['t'] / med['v']:.1f}"]
     ring = 4 if flags & 4 else 8
-    for name in (f"mgx::step_k_policy_episodes_kernel<{flags}, {ring}, 0>", f"mgx::step_k_policy_explore_episodes_kernel<{flags}, {ring}, 0>",
-                 f"mgx::step_k_policy_gaussian_episodes_kernel<{flags}, {ring}, 0, false>",
-                 f"mgx::step_k_policy_gaussian_episodes_kernel<{flags}, {ring}, 0, true>"):
+    for name in (f"mgx::step_k_policy_episodes_kernel<{flags}, {ring}, 0>", f"mgx::step_k_policy_head_episodes_kernel<{flags}, {ring}, 0, 1>",
+                 f"mgx::step_k_policy_head_episodes_kernel<{flags}, {ring}, 0, 4>",      # (1, 4, 5: HEAD_EXPLORE, HEAD_GAUSSIAN,
+                 f"mgx::step_k_policy_head_episodes_kernel<{flags}, {ring}, 0, 5>"):     # HEAD_GAUSSIAN_CRITIC)
         if name in usage:
             lines.append(f"#   {name}: {json.dumps(usage[name], sort_keys=True)}")
     lines.append("# " + json.dumps(dict(layout=flags, n_out=int(A), **{k: round(v, 4) for k, v in med.items()})))

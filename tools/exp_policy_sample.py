@@ -131,8 +131,8 @@ def main():
                   f"    (t) stepped multinomial + step     {fmt(us['t'])}",
                   f"    (s)/(g) = {med['s'] / med['g']:.3f}   (s)/(x) = {med['s'] / med['x']:.3f}   (s) - (g) = {med['s'] - med['g']:.3f} us per step   "
                   f"(t)/(s) = {med['t'] / med['s']:.1f}"]
-        for kernel in ("rollout_policy", "rollout_policy_explore", "rollout_policy_sample"):
-            name = f"mgx::{kernel}_episodes_kernel<{flags}, {4 if flags & 4 else 8}, 0>"
+        for kernel, head in (("rollout_policy", ""), ("rollout_policy_head", ", 1"), ("rollout_policy_head", ", 2")):   # (greedy, HEAD_EXPLORE, HEAD_SAMPLE)
+            name = f"mgx::{kernel}_episodes_kernel<{flags}, {4 if flags & 4 else 8}, 0{head}>"
             if name in usage:
                 lines.append(f"#   {name}: {json.dumps(usage[name], sort_keys=True)}")
         results.append(dict(layout=flags, n_out=int(n_out), **{k: round(v, 4) for k, v in med.items()}))
