@@ -803,6 +803,73 @@ int mgx_rollout_policy_critic_episodes(mgx_handle *h, const mgx_policy *policy, 
 int mgx_gae(int64_t N, int32_t K, const double *reward, const uint8_t *done, const double *value, const double *final_value,
             const double *last_value, double gamma, double lambda, double *advantage, double *returns, mgx_stream stream);
 
+/* THE GRADIENT of the PPO-clip / A2C loss with respect to the parameters of a discrete mgx_policy and the mgx_critic on its trunk,
+ * from what the sampling launch returned (rows, ids, probabilities) and mgx_gae made of it (advantages, returns); handle-free on the
+ * current device (as mgx_gae).  The forward pass is the launch's own sequence of operations, so on an un-updated policy the
+ * probability ratio is exactly 1.0.  K * N samples s = (k, i); x = x[k, i, :] (float64, or float32 widened to double as mgx_policy
+ * widens a float32 row).  mask: uint8 [K, N] or NULL; a sample with mask 0 contributes nothing (a minibatch, an excluded sample);
+ * M is the number of live samples, counted on the device as an integer.  THE RULE (stated here once; every multiply and add
+ * separate, sums in index order):
+ *     forward:    y[0 .. n_out), V by mgx_policy and mgx_critic; h[u] the hidden vector after its ReLU (n_hidden = 0: h = x)
+ *                 best, g, tau = scale ? temperature * scale[i] : temperature, beta, e[o], S exactly as mgx_sampling states them;
+ *                 d[o] = (y[o] - best) * beta, d[g] = 0.0 (as e[g] is 1.0 by definition)
+ *                 pi[o] = e[o] / S;  a = action_id[s];  rho = pi[a] / old_prob[s]
+ *                 where !(tau > 0) (the greedy head): rho = 1.0 / old_prob[s], and the policy and entropy terms of the sample --
+ *                 c, dy, its policy loss, entropy and clipped flag -- are zero; the value term stays
+ *     surrogate:  A = advantage[s];  active = !((A > 0 && rho > hi) || (A < 0 && rho < lo)),  hi = 1.0 + clip_eps, lo = 1.0 - clip_eps
+ *                 (formed once on the host; clip_eps = +inf never gates: A2C, the unclipped surrogate)
+ *                 c = active ? -(A * rho) : 0.0;   the sample's policy loss: active ? c : -(A * (A > 0 ? hi : lo))
+ *     entropy:    lnS = L(S), the L of mgx_gaussian;  logpi[o] = d[o] - lnS
+ *                 Hs = 0.0; for o in order, where e[o] > 0:  Hs = Hs + pi[o] * logpi[o];   H = -Hs
+ *     logits:     dy[o] = beta * (c * ((o == a ? 1.0 : 0.0) - pi[o]) + ent_coef * t[o]),  t[o] = e[o] > 0 ? pi[o] * (logpi[o] + H) : 0.0
+ *     value:      diff = V - returns[s];  dv = vf_coef * diff;  the sample's value loss: 0.5 * (diff * diff)    (no critic: dv = 0)
+ *     trunk:      per hidden unit u:  q = 0.0; for o in order: q = q + w2[o, u] * dy[o];  with a critic: q = q + cw[u] * dv;
+ *                 dh[u] = h[u] > 0 ? q : 0.0
+ *     per-sample terms:  dy[o] * h[u] -> g_w2[o, u];  dy[o] -> g_b2[o];  dv * h[u] -> g_cw[u];  dv -> g_cb;
+ *                        dh[u] * x[j] -> g_w1[u, j];  dh[u] -> g_b1[u]         (n_hidden = 0: x in the place of h, no g_w1 / g_b1)
+ *     result:     every output = (1.0 / M) * (the sum of its term over the live samples);  M = 0 gives zeros
+ *     stats[0 .. 3] = the means over the live samples of policy loss, value loss, entropy H and the clipped flag (!active)
+ *     ratio_out[s] = rho on the live samples; masked samples keep the caller's bytes
+ * The loss these are the gradient of: mean(policy loss) + vf_coef * mean(value loss) - ent_coef * mean(H).
+ * THE SUMS over the samples go through the matrix cores (v_mfma_f64_16x16x4_f64, four samples per instruction) and then over waves
+ * and workgroups in a fixed order: the result is the same from run to run, but the ORDER of the sum is the kernel's, and how the
+ * fp64 MFMA rounds its inner sum of four products is not documented -- so a sum over many samples is within the any-order bound
+ * (M + 2) * 2^-53 * sum_s |term_s| / M of the exact one, not bit for bit a host loop's.  One live sample is exact: a product added
+ * to zeros.  How the MFMA treats subnormal products is not known either: keep the terms normal numbers.  No atomics are used. */
+struct mgx_policy_grad {
+    int32_t struct_size;      /* = sizeof(struct mgx_policy_grad) */
+    int32_t x_f32;            /* 0: x is float64; 1: float32 */
+    const void    *x;         /* [K, N, n_in]: the row decision (k, i) was taken on */
+    const uint8_t *action_id; /* [K, N] */
+    const double  *old_prob;  /* [K, N] */
+    const double  *advantage; /* [K, N] */
+    const double  *returns;   /* [K, N]; NULL without a critic */
+    const uint8_t *mask;      /* [K, N] or NULL */
+    double clip_eps;          /* >= 0; +inf: no clipping */
+    double vf_coef, ent_coef;
+    double *g_w1, *g_b1;      /* [n_hidden, n_in], [n_hidden]; each output may be NULL */
+    double *g_w2, *g_b2;      /* [n_out, n_mid], [n_out] */
+    double *g_cw, *g_cb;      /* [n_mid], [1]; NULL without a critic */
+    double *stats;            /* [4] */
+    double *ratio_out;        /* [K, N] */
+    void   *workspace;        /* the per-workgroup partials: mgx_policy_grad_workspace bytes, at least; 8-byte aligned */
+    int64_t workspace_bytes;
+};                            /* (a struct tag without a typedef: the call below bears the same name) */
+
+/* The bytes of workspace a call with these shapes needs.  Refusals as mgx_policy_grad refuses N, K and the policy; NULL bytes. */
+int mgx_policy_grad_workspace(int64_t N, int32_t K, const mgx_policy *policy, int64_t *bytes);
+
+/* Two launches: policy_grad_kernel (a lane per sample, a wave 64 grids and a chunk of k) and policy_grad_finish_kernel (the
+ * partials in a fixed order, times 1 / M, into the caller's arrays).  Of `sampling` only temperature and scale are read: no draw is
+ * made.  critic may be NULL: no value term, and returns, g_cw and g_cb must then be NULL.  Nothing is launched when the call is refused:
+ * MGX_ERR_INVALID: a NULL pg / policy / sampling / x / action_id / old_prob / advantage, a wrong struct_size (pg, policy, sampling,
+ * critic), N or K below 1, n_in or n_out outside 1 .. 12, NULL weights, a negative, infinite or NaN temperature, a negative or NaN
+ * clip_eps, a NaN coefficient, x_f32 other than 0 or 1, returns, g_cw or g_cb without a critic, NULL returns with one, a NULL or too
+ * small workspace.  MGX_ERR_UNSUPPORTED: n_policies > 1 or a policy_index (the gradient of a population is not offered),
+ * n_hidden > MGX_POLICY_MAX_HIDDEN.  An ADDITION to ABI 9 that leaves MGX_ABI_MINOR at 3: found by name (dlsym). */
+int mgx_policy_grad(int64_t N, int32_t K, const mgx_policy *policy, const mgx_critic *critic, const mgx_sampling *sampling,
+                    const struct mgx_policy_grad *pg, mgx_stream stream);
+
 /* A GAUSSIAN policy head inside the closed-loop continuous launch: every control is drawn from N(y[o], s[o]^2) -- a true normal
  * draw, not the lattice of mgx_exploration -- and the launch returns the pre-clip action and its exact log-density, what the
  * on-policy methods need on the continuous head.  As exp in mgx_sampling, log, sine and cosine are PART OF THE RULE: fixed sequences

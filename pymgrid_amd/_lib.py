@@ -28,6 +28,7 @@ UNITS = (
     ("mgx_policy_head_episodes.hip", "MGX_EPISODE_PART", 2),            # ... the closed-loop roll-out with a head (UNIT_HEADS)
     ("mgx_step_policy_head_episodes.hip", "MGX_EPISODE_PART", 2),       # ... and its continuous twin,
     ("mgx_gae.hip", None, 1),                                           # the advantages of what such launches return (mgx_gae)
+    ("mgx_policy_grad.hip", "MGX_POLICY_GRAD_PART", 4),                 # ... and the PPO / A2C gradient of them (mgx_policy_grad), sliced by row width
     ("mgx_lookahead_episodes.hip", "MGX_EPISODE_PART", 2),              # what-if roll-outs of candidate plans, nothing committed
     ("mgx_lookahead_step_episodes.hip", "MGX_EPISODE_PART", 2),         # ... and their continuous twin
     ("mgx_lookahead_gaussian_episodes.hip", "MGX_EPISODE_PART", 2),     # ... with the candidates drawn inside the launch (CEM)
@@ -40,7 +41,7 @@ UNIT_HEADS = {
     "mgx_step_policy_head_episodes.hip": ("MGX_POLICY_HEAD", (1, 4, 5)),    # exploring, Gaussian, Gaussian with a critic
 }
 # everything a built library is stamped with (source_hash): a file missing here would leave a stale libmgx.so looking current
-SOURCES = [os.path.join(_PKG, "csrc", f) for f in [u[0] for u in UNITS] + ["mgx_kernels.hpp", "mgx_core.hpp", "mgx_step_hot.hpp", "mgx_episode_loop.hpp", "mgx_episode_rows.hpp", "mgx_policy.hpp", "mgx_gae.hpp", "mgx_lookahead.hpp", "mgx_cem.hpp"]] + \
+SOURCES = [os.path.join(_PKG, "csrc", f) for f in [u[0] for u in UNITS] + ["mgx_kernels.hpp", "mgx_core.hpp", "mgx_step_hot.hpp", "mgx_episode_loop.hpp", "mgx_episode_rows.hpp", "mgx_policy.hpp", "mgx_gae.hpp", "mgx_policy_grad.hpp", "mgx_lookahead.hpp", "mgx_cem.hpp"]] + \
           [os.path.join(_ROOT, "include", "mgx.h")]
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-fPIC"]
@@ -212,6 +213,16 @@ class CemRefit(C.Structure):
                [(n, C.c_void_p) for n in ("ret", "steps", "elite", "mean_out", "sigma_out", "best_plan")]
 
 
+class PolicyGrad(C.Structure):
+    """mgx_policy_grad (include/mgx.h): what ``mgx_policy_grad`` reads of a collection, where the gradients go and its workspace (device
+    arrays; ``returns``, ``mask`` and every output may be NULL)."""
+    _fields_ = [("struct_size", C.c_int32), ("x_f32", C.c_int32)] + \
+               [(n, C.c_void_p) for n in ("x", "action_id", "old_prob", "advantage", "returns", "mask")] + \
+               [(n, C.c_double) for n in ("clip_eps", "vf_coef", "ent_coef")] + \
+               [(n, C.c_void_p) for n in ("g_w1", "g_b1", "g_w2", "g_b2", "g_cw", "g_cb", "stats", "ratio_out", "workspace")] + \
+               [("workspace_bytes", C.c_int64)]
+
+
 POLICY_MAX_HIDDEN = 64     # MGX_POLICY_MAX_HIDDEN
 POLICY_LDS_BYTES = 32768   # MGX_POLICY_LDS_BYTES
 
@@ -307,6 +318,9 @@ SYMBOLS = {
                                             + [C.c_void_p] * 10 + [C.POINTER(EpisodeStats), C.POINTER(EpisodeRows), C.c_void_p]),
     "mgx_gae": (C.c_int, [C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double,
                           C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mgx_policy_grad_workspace": (C.c_int, [C.c_int64, C.c_int32, C.POINTER(Policy), C.POINTER(C.c_int64)]),
+    "mgx_policy_grad": (C.c_int, [C.c_int64, C.c_int32, C.POINTER(Policy), C.POINTER(Critic), C.POINTER(Sampling), C.POINTER(PolicyGrad),
+                                  C.c_void_p]),
     "mgx_lookahead_episodes": (C.c_int, [C.c_void_p, C.c_void_p, c_i32_p, C.c_int32, C.POINTER(Lookahead), C.c_void_p]),
     "mgx_lookahead_step_k_episodes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(Lookahead), C.c_void_p]),
     "mgx_lookahead_gaussian_episodes": (C.c_int, [C.c_void_p, C.POINTER(Cem), C.POINTER(Lookahead), C.c_void_p]),

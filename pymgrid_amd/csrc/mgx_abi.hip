@@ -8,6 +8,7 @@
 #include "mgx_episode_rows.hpp"
 #include "mgx_policy.hpp"
 #include "mgx_gae.hpp"
+#include "mgx_policy_grad.hpp"
 #include "mgx_lookahead.hpp"
 #include "mgx_cem.hpp"
 
@@ -2954,6 +2955,93 @@ int mgx_gae(int64_t N, int32_t K, const double *reward, const uint8_t *done, con
     if (e != hipSuccess || ndev <= 0) return fail(MGX_ERR_DEVICE, "mgx_gae: no HIP device available -- this engine has no CPU path");
     launch_gae(GaeArgs{N, K, reward, done, value, final_value, last_value, gamma, gamma * lambda, advantage, returns}, (hipStream_t)stream);
     return launched("gae_kernel launch");
+}
+
+// The gradient of the PPO-clip / A2C loss (policy_grad_kernel + policy_grad_finish_kernel: mgx_policy_grad.hip); handle-free, on the
+// current device.  What both calls check of the shapes and the policy:
+static int policy_grad_dims_refusal(int64_t N, int32_t K, const mgx_policy *policy, const char *fn)
+{
+    if (!policy) return fail(MGX_ERR_INVALID, "%s: NULL policy", fn);
+    if (int rc = policy_struct_refusal(policy, fn)) return rc;
+    if (N <= 0 || K <= 0) return fail(MGX_ERR_INVALID, "%s: N = %lld, K = %d: both must be positive", fn, (long long)N, K);
+    if (policy->n_in <= 0 || policy->n_in > 12 || policy->n_out <= 0 || policy->n_out > 12)
+        return fail(MGX_ERR_INVALID, "%s: policy->n_in is %d, policy->n_out is %d: both lie in 1 .. 12", fn, policy->n_in, policy->n_out);
+    if (policy->n_policies > 1 || policy->policy_index)
+        return fail(MGX_ERR_UNSUPPORTED, "%s: the gradient of a population (n_policies = %d%s) is not offered", fn, policy->n_policies,
+                    policy->policy_index ? ", a policy_index" : "");
+    if (policy->n_hidden > MGX_POLICY_MAX_HIDDEN)
+        return fail(MGX_ERR_UNSUPPORTED, "%s: policy->n_hidden is %d, at most MGX_POLICY_MAX_HIDDEN = %d", fn, policy->n_hidden, MGX_POLICY_MAX_HIDDEN);
+    return MGX_OK;
+}
+
+static int64_t policy_grad_workspace_bytes(int64_t N, int32_t K, int32_t n_hidden)
+{
+    const PolicyGradShape s = policy_grad_shape(N, K);
+    return (int64_t)s.bx * s.by * policy_grad_block_doubles(n_hidden) * (int64_t)sizeof(double);
+}
+
+int mgx_policy_grad_workspace(int64_t N, int32_t K, const mgx_policy *policy, int64_t *bytes)
+{
+    g_err[0] = 0;
+    const char *fn = "mgx_policy_grad_workspace";
+    if (!bytes) return fail(MGX_ERR_INVALID, "%s: NULL bytes", fn);
+    if (int rc = policy_grad_dims_refusal(N, K, policy, fn)) return rc;
+    *bytes = policy_grad_workspace_bytes(N, K, policy->n_hidden);
+    return MGX_OK;
+}
+
+int mgx_policy_grad(int64_t N, int32_t K, const mgx_policy *policy, const mgx_critic *critic, const mgx_sampling *sampling,
+                    const struct mgx_policy_grad *pg, mgx_stream stream)
+{
+    g_err[0] = 0;
+    const char *fn = "mgx_policy_grad";
+    if (!pg) return fail(MGX_ERR_INVALID, "%s: NULL pg", fn);
+    if (pg->struct_size != (int32_t)sizeof(struct mgx_policy_grad))
+        return fail(MGX_ERR_INVALID, "%s: pg->struct_size is %d, sizeof(struct mgx_policy_grad) is %d", fn, pg->struct_size,
+                    (int)sizeof(struct mgx_policy_grad));
+    if (int rc = policy_grad_dims_refusal(N, K, policy, fn)) return rc;
+    if (!sampling) return fail(MGX_ERR_INVALID, "%s: NULL sampling", fn);
+    PolicyGradArgs g{};
+    if (int rc = sampling_refusal(sampling, fn, g.sa)) return rc;
+    if (critic) {
+        if (critic->struct_size != (int32_t)sizeof(mgx_critic))
+            return fail(MGX_ERR_INVALID, "%s: critic->struct_size is %d, sizeof(mgx_critic) is %d", fn, critic->struct_size, (int)sizeof(mgx_critic));
+        if (!critic->w || !critic->b) return fail(MGX_ERR_INVALID, "%s: NULL critic weights", fn);
+        if (!pg->returns) return fail(MGX_ERR_INVALID, "%s: NULL returns with a critic", fn);
+        g.cr = CriticArgs{critic->w, critic->b};
+    } else if (pg->returns || pg->g_cw || pg->g_cb) {
+        return fail(MGX_ERR_INVALID, "%s: returns, g_cw or g_cb given without a critic", fn);
+    }
+    if (!pg->x || !pg->action_id || !pg->old_prob || !pg->advantage)
+        return fail(MGX_ERR_INVALID, "%s: NULL x, action_id, old_prob or advantage", fn);
+    if (pg->x_f32 != 0 && pg->x_f32 != 1) return fail(MGX_ERR_INVALID, "%s: x_f32 = %d (0: float64 rows, 1: float32 rows)", fn, pg->x_f32);
+    if (!(pg->clip_eps >= 0.0)) return fail(MGX_ERR_INVALID, "%s: clip_eps = %g is negative or NaN", fn, pg->clip_eps);
+    if (pg->vf_coef != pg->vf_coef || pg->ent_coef != pg->ent_coef) return fail(MGX_ERR_INVALID, "%s: a NaN coefficient", fn);
+    const int64_t need = policy_grad_workspace_bytes(N, K, policy->n_hidden);
+    if (!pg->workspace || pg->workspace_bytes < need)
+        return fail(MGX_ERR_INVALID, "%s: a workspace of %lld bytes, mgx_policy_grad_workspace asks for %lld", fn,
+                    (long long)(pg->workspace ? pg->workspace_bytes : 0), (long long)need);
+    int ndev = 0;
+    hipError_t e = hipGetDeviceCount(&ndev);
+    if (e != hipSuccess || ndev <= 0) return fail(MGX_ERR_DEVICE, "%s: no HIP device available -- this engine has no CPU path", fn);
+    const int32_t D = policy->n_in, nh = policy->n_hidden, n_staged = (policy->n_out + 3) / 4 * 4;    // (the discrete launch's groups of four)
+    const int32_t stride = ((critic ? policy_critic_set_doubles(D, nh, n_staged) : policy_set_doubles(D, nh, n_staged)) + 1) & ~1;
+    g.pol = PolicyArgs{policy->w1, policy->b1, policy->w2, policy->b2, nullptr, 1, nh, n_staged, policy->n_out, stride};
+    const PolicyGradShape s = policy_grad_shape(N, K);
+    g.N = N; g.K = K; g.kc = s.kc; g.x_f32 = pg->x_f32;
+    g.x = pg->x; g.action_id = pg->action_id; g.old_prob = pg->old_prob; g.advantage = pg->advantage; g.returns = pg->returns;
+    g.mask = pg->mask;
+    g.hi = 1.0 + pg->clip_eps; g.lo = 1.0 - pg->clip_eps; g.vf_coef = pg->vf_coef; g.ent_coef = pg->ent_coef;
+    g.ratio_out = pg->ratio_out; g.ws = (double *)pg->workspace;
+    const unsigned lds = (unsigned)stride * (unsigned)sizeof(double);
+    bool (*const part[])(const PolicyGradArgs &, int32_t, bool, unsigned, hipStream_t) = {launch_policy_grad_p0, launch_policy_grad_p1,
+                                                                                         launch_policy_grad_p2, launch_policy_grad_p3};
+    if (!part[(D - 1) / PG_PART_DIMS](g, D, critic != nullptr, lds, (hipStream_t)stream))
+        return fail(MGX_ERR_INVALID, "%s: no kernel for rows of %d columns", fn, D);
+    if (int rc = launched("policy_grad_kernel launch")) return rc;
+    launch_policy_grad_finish(PolicyGradFinishArgs{g.ws, (int32_t)(s.bx * s.by), nh, policy->n_out, D, pg->g_w1, pg->g_b1, pg->g_w2, pg->g_b2,
+                                                   pg->g_cw, pg->g_cb, pg->stats}, (hipStream_t)stream);
+    return launched("policy_grad_finish_kernel launch");
 }
 
 int mgx_normalise_series(mgx_handle *h, void *load_n, void *pv_n, void *grid_n, int32_t *clipped, mgx_stream stream)

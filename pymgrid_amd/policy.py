@@ -820,3 +820,238 @@ def gae(reward, done, value, last_value, final_value=None, gamma=0.99, lam=0.95,
         _lib.check(_lib.lib().mgx_gae(N, K, ptr(reward), ptr(d8), ptr(value), ptr(final_value), ptr(last_value), gamma, lam,
                                       ptr(res["advantages"]), ptr(res.get("returns")), torch.cuda.current_stream(dev).cuda_stream))
     return res
+
+
+def decision_rows(obs_before, obs):
+    """The rows the K decisions of a closed-loop launch were taken on, ``[K, N, D]``: ``cat(obs_before[None], obs[:-1])`` --
+    ``obs_before`` ``[N, D]`` is the observation the env showed before the launch, ``obs`` ``[K, N, D]`` what the launch returned
+    (``observations=True``).  ``obs[k]`` is what step k returned, hence the row decision k + 1 read, restarts included: after a restart
+    it is the first row of the new episode."""
+    if obs.dim() != 3 or obs_before.dim() != 2 or tuple(obs_before.shape) != tuple(obs.shape[1:]) or obs_before.dtype != obs.dtype:
+        raise ValueError(f"obs_before {tuple(obs_before.shape)} {obs_before.dtype} is not a row set of obs {tuple(obs.shape)} {obs.dtype}")
+    return torch.cat([obs_before.unsqueeze(0), obs[:-1]], dim=0).contiguous()
+
+
+PPO_GRAD_NAMES = ("W1", "b1", "W2", "b2", "w", "b")      # the gradients in the order ``ppo_grad_flat`` lays them out
+
+
+def _ppo_args(policy, critic, rows, actions, old_probs, advantages, returns, sampling, clip, vf_coef, ent_coef, mask):
+    """The checks ``ppo_grad`` and ``ppo_grad_host`` share (those of ``mgx_policy_grad``): ``(K, N, clip, vf_coef, ent_coef)``."""
+    if not isinstance(policy, MLPPolicy) or policy.head != "discrete":
+        raise ValueError("the gradient is offered for an MLPPolicy with the discrete head (the continuous head is a rule of its own)")
+    if policy.n_policies != 1 or policy.policy_index is not None:
+        raise ValueError("the gradient of a population (several parameter sets, a policy_index) is not offered")
+    if not isinstance(sampling, Sampling):
+        raise ValueError("sampling must be the Sampling of the launch that collected the data (temperature and scale are read)")
+    if critic is not None:
+        if not isinstance(critic, ValueHead):
+            raise ValueError("critic must be a ValueHead or None")
+        critic.check(policy)
+        if returns is None:
+            raise ValueError("a critic needs `returns`")
+    elif returns is not None:
+        raise ValueError("`returns` goes with a critic")
+    clip, vf_coef, ent_coef = float(clip), float(vf_coef), float(ent_coef)
+    if not clip >= 0.0:
+        raise ValueError(f"clip = {clip}: >= 0 (inf: no clipping)")
+    if vf_coef != vf_coef or ent_coef != ent_coef:
+        raise ValueError("a NaN coefficient")
+    if not torch.is_tensor(rows) or rows.dim() != 3 or rows.shape[2] != policy.n_in or rows.dtype not in (torch.float32, torch.float64):
+        raise ValueError(f"rows must be float32 or float64 [K, N, {policy.n_in}], not {getattr(rows, 'dtype', type(rows))} "
+                         f"{tuple(getattr(rows, 'shape', ()))}")
+    K, N = int(rows.shape[0]), int(rows.shape[1])
+    if K < 1 or N < 1:
+        raise ValueError(f"rows {tuple(rows.shape)}: K and N must be positive")
+    for name, t, dts in (("actions", actions, (torch.uint8,)), ("old_probs", old_probs, (torch.float64,)),
+                         ("advantages", advantages, (torch.float64,)), ("returns", returns, (torch.float64,)),
+                         ("mask", mask, (torch.uint8, torch.bool))):
+        if t is None and name in ("returns", "mask"):
+            continue
+        if not torch.is_tensor(t) or t.dtype not in dts or tuple(t.shape) != (K, N):
+            raise ValueError(f"{name} must be a {' or '.join(str(d) for d in dts)} tensor [{K}, {N}], not "
+                             f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
+        if t.device != rows.device:
+            raise ValueError(f"{name} lies on {t.device}, rows on {rows.device}")
+    return K, N, clip, vf_coef, ent_coef
+
+
+def ppo_grad_flat(grads):
+    """The gradients of a ``ppo_grad`` / ``ppo_grad_host`` result as one vector ``[P]``, in the order ``PPO_GRAD_NAMES`` (absent ones
+    skipped): the columns of ``ppo_grad_host(per_sample=True)["terms"]``."""
+    return torch.cat([grads[n].reshape(-1) for n in PPO_GRAD_NAMES if grads.get(n) is not None])
+
+
+def ppo_grad_host(policy, critic, rows, actions, old_probs, advantages, returns=None, sampling=None, clip=0.2, vf_coef=0.5, ent_coef=0.0,
+                  mask=None, ratio=False, per_sample=False):
+    """The rule of ``mgx_policy_grad`` (include/mgx.h) in torch, on any device, operation by operation: the gradient of
+    ``mean(policy loss) + vf_coef * mean(value loss) - ent_coef * mean(entropy)`` over the live samples with respect to the
+    parameters, ``{"W1", "b1", "W2", "b2", "w", "b", "stats"[, "ratio"]}`` (``W1`` / ``b1`` None for a linear policy, ``w`` / ``b`` None
+    without a critic; ``stats``: the means of policy loss, value loss, entropy, clipped fraction).  Per sample every operation is the
+    device's; the sum over the samples is torch's (the device's goes through the matrix cores: the two agree within the any-order
+    summation bound, and exactly for one live sample).  ``per_sample=True`` adds ``"terms"`` ``[M, P]``, the unreduced terms of the M
+    live samples in the column order of ``ppo_grad_flat``, and ``"stat_terms"`` ``[M, 4]``."""
+    K, N, clip, vf_coef, ent_coef = _ppo_args(policy, critic, rows, actions, old_probs, advantages, returns, sampling, clip, vf_coef,
+                                              ent_coef, mask)
+    dev = rows.device
+    me = policy.to(dev)
+    n = K * N
+    x = rows.reshape(n, me.n_in).to(torch.float64)
+    if me.n_hidden:
+        hp = MLPPolicy._layer(me.W1, me.b1, None, x)
+        h = torch.where(hp > 0, hp, torch.zeros_like(hp))
+    else:
+        h = x
+    y = MLPPolicy._layer(me.W2, me.b2, None, h)
+    zero, one = torch.zeros(n, dtype=torch.float64, device=dev), torch.ones(n, dtype=torch.float64, device=dev)
+    g, best = me._greedy(y)
+    tau = zero + sampling.temperature
+    scale = sampling.scale_on(dev, N)
+    if scale is not None:
+        tau = sampling.temperature * scale.repeat(K)
+    samp = tau > 0
+    b = torch.where(samp, 1.0 / torch.where(samp, tau, one), zero)
+    a = actions.reshape(n).long()
+    e, d, S = [], [], zero
+    for o in range(me.n_out):
+        dd = (y[:, o] - best) * b
+        ok = dd >= EXP_MIN                                                 # (False for a NaN)
+        eo = torch.where(ok, policy_exp(torch.where(ok, dd, torch.full_like(dd, EXP_MIN))), zero)
+        e.append(torch.where(g == o, one, eo))
+        d.append(torch.where(g == o, zero, dd))
+        S = S + e[-1]
+    e_a = zero
+    for o in range(me.n_out):
+        e_a = torch.where(a == o, e[o], e_a)
+    rho = torch.where(samp, e_a / S, one) / old_probs.reshape(n)
+    A = advantages.reshape(n)
+    hi, lo = 1.0 + clip, 1.0 - clip
+    active = ~(((A > 0) & (rho > hi)) | ((A < 0) & (rho < lo)))
+    c = torch.where(samp & active, -(A * rho), zero)
+    pl = torch.where(samp, torch.where(active, c, -(A * torch.where(A > 0, zero + hi, zero + lo))), zero)
+    lnS = policy_log(S)
+    pi, logpi, Hs = [], [], zero
+    for o in range(me.n_out):
+        pi.append(e[o] / S)
+        logpi.append(d[o] - lnS)
+        Hs = torch.where(e[o] > 0, Hs + pi[o] * logpi[o], Hs)
+    H = -Hs
+    dy = []
+    for o in range(me.n_out):
+        t = torch.where(e[o] > 0, pi[o] * (logpi[o] + H), zero)
+        v = b * (c * ((a == o).to(torch.float64) - pi[o]) + ent_coef * t)
+        dy.append(torch.where(samp, v, zero))
+    dy = torch.stack(dy, dim=1)
+    dv = vl = None
+    if critic is not None:
+        cw, cb = critic.w.to(dev), critic.b.to(dev)
+        V = MLPPolicy._layer(cw.unsqueeze(1), cb.unsqueeze(1), None, h)[:, 0]
+        diff = V - returns.reshape(n)
+        dv, vl = vf_coef * diff, 0.5 * (diff * diff)
+    cols = []
+    if me.n_hidden:
+        q = torch.zeros_like(h)
+        for o in range(me.n_out):
+            q = q + me.W2[0][o].unsqueeze(0) * dy[:, o:o + 1]
+        if critic is not None:
+            q = q + cw[0].unsqueeze(0) * dv.unsqueeze(1)
+        dh = torch.where(h > 0, q, torch.zeros_like(q))
+        cols += [(dh.unsqueeze(2) * x.unsqueeze(1)).reshape(n, -1), dh]
+    cols += [(dy.unsqueeze(2) * h.unsqueeze(1)).reshape(n, -1), dy]
+    if critic is not None:
+        cols += [dv.unsqueeze(1) * h, dv.unsqueeze(1)]
+    terms = torch.cat(cols, dim=1)
+    st = torch.stack([pl, vl if vl is not None else zero, torch.where(samp, H, zero), (samp & ~active).to(torch.float64)], dim=1)
+    if mask is not None:
+        keep = mask.reshape(n) != 0
+        terms, st = terms[keep], st[keep]
+    M = terms.shape[0]
+    inv = 1.0 / M if M else 0.0
+    flat, stats = inv * terms.sum(dim=0), inv * st.sum(dim=0)
+    res, at = {}, 0
+    n_mid = me.n_hidden or me.n_in
+    shapes = {"W1": (me.n_hidden, me.n_in) if me.n_hidden else None, "b1": (me.n_hidden,) if me.n_hidden else None,
+              "W2": (me.n_out, n_mid), "b2": (me.n_out,), "w": (n_mid,) if critic is not None else None,
+              "b": (1,) if critic is not None else None}
+    for name in PPO_GRAD_NAMES:
+        if shapes[name] is None:
+            res[name] = None
+            continue
+        size = int(np.prod(shapes[name]))
+        res[name] = flat[at:at + size].reshape(shapes[name])
+        at += size
+    res["stats"] = stats
+    if ratio:
+        res["ratio"] = rho.reshape(K, N)
+    if per_sample:
+        res["terms"], res["stat_terms"] = terms, st
+    return res
+
+
+def ppo_grad(policy, critic, rows, actions, old_probs, advantages, returns=None, sampling=None, clip=0.2, vf_coef=0.5, ent_coef=0.0,
+             mask=None, ratio=False, out=None):
+    """The gradient of the PPO-clip loss (``clip=float("inf")``: A2C, the unclipped surrogate) of a discrete ``MLPPolicy`` and the
+    ``ValueHead`` on its trunk over the ``[K, N]`` samples of a collection, on the device (``mgx_policy_grad``: one kernel over the
+    samples, the sum on the matrix cores, and a small one that adds the partials in a fixed order): ``ppo_grad_host``'s values, exactly
+    for one live sample and within the any-order summation bound for many, identical from run to run.  The forward pass is the
+    sampling launch's own, so with the parameters that collected the data ``ratio`` is exactly 1.0.
+
+    ``rows`` ``[K, N, n_in]`` float64 or float32 (``decision_rows``), ``actions`` uint8, ``old_probs`` / ``advantages`` / ``returns``
+    float64 ``[K, N]`` (``out["action_ids"]``, ``out["probs"]`` of ``rollout_policy`` and ``gae``'s results), ``sampling`` the launch's
+    ``Sampling``, ``mask`` uint8 or bool ``[K, N]`` (0: the sample contributes nothing -- minibatches).  Returns ``{"W1", "b1", "W2",
+    "b2", "w", "b", "stats"[, "ratio"]}``: tensors shaped like the parameters without the population axis (None where there is none),
+    ``stats`` = the means of policy loss, value loss, entropy, clipped fraction.  ``out``: a dict with your own contiguous float64
+    tensors for any of them (e.g. the ``.grad`` of the parameters).  Contiguous device tensors only."""
+    K, N, clip, vf_coef, ent_coef = _ppo_args(policy, critic, rows, actions, old_probs, advantages, returns, sampling, clip, vf_coef,
+                                              ent_coef, mask)
+    dev = rows.device
+    if dev.type != "cuda":
+        raise ValueError(f"ppo_grad runs on the GPU (mgx_policy_grad); the tensors lie on {dev} -- ppo_grad_host states the same rule anywhere")
+    for name, t in (("rows", rows), ("actions", actions), ("old_probs", old_probs), ("advantages", advantages), ("returns", returns),
+                    ("mask", mask)):
+        if t is not None and not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
+    n_mid = policy.n_hidden or policy.n_in
+    shapes = {"W1": (policy.n_hidden, policy.n_in) if policy.n_hidden else None, "b1": (policy.n_hidden,) if policy.n_hidden else None,
+              "W2": (policy.n_out, n_mid), "b2": (policy.n_out,), "w": (n_mid,) if critic is not None else None,
+              "b": (1,) if critic is not None else None, "stats": (4,), "ratio": (K, N) if ratio else None}
+    out = out or {}
+    unknown = set(out) - set(shapes)
+    if unknown:
+        raise ValueError(f"unknown outputs {sorted(unknown)}")
+    res = {}
+    for name, shape in shapes.items():
+        t = out.get(name)
+        if shape is None:
+            if t is not None:
+                raise ValueError(f"out[{name!r}] given, but this call has no such output")
+            if name != "ratio":
+                res[name] = None
+            continue
+        if t is None:                                      # (a masked sample's ratio is not written: NaN there)
+            t = torch.full(shape, float("nan"), dtype=torch.float64, device=dev) if name == "ratio" and mask is not None else \
+                torch.empty(shape, dtype=torch.float64, device=dev)
+        elif not torch.is_tensor(t) or t.dtype != torch.float64 or t.device != dev or not t.is_contiguous() or t.numel() != int(np.prod(shape)):
+            raise ValueError(f"out[{name!r}] must be a contiguous float64 tensor of {list(shape)} on {dev}")
+        res[name] = t
+    lib = _lib.lib()
+    ptr = lambda t: None if t is None else t.data_ptr()     # noqa: E731
+    with torch.cuda.device(dev):
+        pol, keep_p = policy.c_struct(dev, N)
+        smp, keep_s = sampling.c_struct(dev, N)
+        cr, keep_c = critic.c_struct(dev, N) if critic is not None else (None, None)
+        need = C.c_int64()
+        _lib.check(lib.mgx_policy_grad_workspace(N, K, C.byref(pol), C.byref(need)))
+        ws = torch.empty((need.value + 7) // 8, dtype=torch.float64, device=dev)
+        m8 = mask.view(torch.uint8) if mask is not None and mask.dtype == torch.bool else mask
+        pg = _lib.PolicyGrad()
+        pg.struct_size = C.sizeof(_lib.PolicyGrad)
+        pg.x_f32 = int(rows.dtype == torch.float32)
+        pg.x, pg.action_id, pg.old_prob, pg.advantage = ptr(rows), ptr(actions), ptr(old_probs), ptr(advantages)
+        pg.returns, pg.mask = ptr(returns), ptr(m8)
+        pg.clip_eps, pg.vf_coef, pg.ent_coef = clip, vf_coef, ent_coef
+        pg.g_w1, pg.g_b1, pg.g_w2, pg.g_b2 = ptr(res["W1"]), ptr(res["b1"]), ptr(res["W2"]), ptr(res["b2"])
+        pg.g_cw, pg.g_cb, pg.stats, pg.ratio_out = ptr(res["w"]), ptr(res["b"]), ptr(res["stats"]), ptr(res.get("ratio"))
+        pg.workspace, pg.workspace_bytes = ws.data_ptr(), ws.numel() * 8
+        _lib.check(lib.mgx_policy_grad(N, K, C.byref(pol), C.byref(cr) if cr is not None else None, C.byref(smp), C.byref(pg),
+                                       torch.cuda.current_stream(dev).cuda_stream))
+    return res
