@@ -952,6 +952,65 @@ int mgx_step_k_policy_gaussian_episodes(mgx_handle *h, const mgx_policy *policy,
                                         double *value_out, double *final_value_out, double *last_value_out,
                                         const mgx_episode_stats *stats, const mgx_episode_rows *rows, mgx_stream stream);
 
+/* THE GRADIENT of the same loss for the GAUSSIAN head of the continuous policy (mgx_gaussian, stated above): with respect to the
+ * parameters of a continuous mgx_policy, the mgx_critic on its trunk and log sigma, from what mgx_step_k_policy_gaussian_episodes
+ * returned (rows, the pre-clip actions raw, their log-density) and mgx_gae made of it; handle-free on the current device.  Samples,
+ * x, mask and M as in mgx_policy_grad.  THE RULE (stated here once; every multiply and add separate, sums in index order; L of
+ * mgx_gaussian, E of mgx_sampling; A = n_out = the action dim, 1 .. 4):
+ *     forward:    y[0 .. A), V, h[u] by mgx_policy / mgx_critic on x = x[k, i, :]
+ *                 s[o] = scale ? sigma[o] * scale[i] : sigma[o];  column o is LIVE iff s[o] > 0           (mgx_gaussian)
+ *                 C = mgx_gaussian's log-probability constant: the sum over the live o of L(s[o]) + 0.9189385332046727
+ *     density:    zeta[o] = (raw[k, i, o] - y[o]) / s[o]  on the live o     (a subtraction, then the IEEE division)
+ *                 Q = 0.0;  for each live o in order:  Q = Q + zeta[o] * zeta[o];     logp = (-0.5 * Q) - C
+ *                 D = logp - old_logp[s]
+ *                 rho = D <= 0 ? E(D < -708 ? -708 : D) : 1.0 / E(-D < -708 ? -708 : -D);   a NaN D: rho = NaN by a select (E sees 0.0)
+ *     surrogate:  A_s = advantage[s], hi, lo, active, c and the sample's policy loss: word for word mgx_policy_grad
+ *     entropy:    H = 0.0;  for each live o in order:  H = H + (L(s[o]) + 1.4189385332046727)     (a constant of the grid: once per lane)
+ *     means:      dy[o]  = live ? c * (zeta[o] / s[o]) : 0.0
+ *     log sigma:  dls[o] = live ? (c * (zeta[o] * zeta[o] - 1.0)) - ent_coef : 0.0        -> g_log_sigma[o]
+ *     value, trunk, per-sample terms, result = (1.0 / M) * the sum over the live samples: word for word mgx_policy_grad, n_out = A
+ *     a grid without a live column (every sigma 0, or scale[i] == 0): its policy loss, entropy, clipped flag, kl and dy are zero, the
+ *                 value term stays; rho is still the formula's (logp = -0.0)
+ *     stats[0 .. 5) = the means over the live samples of policy loss, value loss, H, the clipped flag (!active) and
+ *                 kl = (rho - 1.0) - D       (the usual early-stopping estimate of the divergence from the collecting policy)
+ *     ratio_out[s] = rho on the live samples; masked samples keep the caller's bytes
+ * These are the gradient of mean(policy loss) + vf_coef * mean(value loss) - ent_coef * mean(H).  g_log_sigma[o] is the gradient
+ * with respect to log sigma[o]: the entropy of a Gaussian whose sigma does not depend on the state does not depend on the mean, so
+ * ent_coef appears there alone.  Sigma stays a host value of mgx_gaussian: who learns it keeps log sigma, steps it with g_log_sigma
+ * and hands the next launch exp(log sigma) -- four numbers cross to the host per iteration.
+ * THE RATIO of an un-updated policy is NOT exactly 1.0, unlike mgx_policy_grad's: raw = y + s * z is rounded, so (raw - y) / s is not
+ * z bit for bit.  With u = 2^-53, delta[o] = u * (4 |zeta[o]| + 2 |raw[o]| / s[o]) and
+ * B = sum over the live o of |zeta[o]| * delta[o] + 5 u Q + 2 u |logp|, it stays within |rho - 1| <= 1.01 * B + 8 u.
+ * The sums over the samples, their order and what is unknown about the MFMA: as mgx_policy_grad states them. */
+struct mgx_policy_grad_gaussian {
+    int32_t struct_size;      /* = sizeof(struct mgx_policy_grad_gaussian) */
+    int32_t x_f32;            /* 0: x is float64; 1: float32 */
+    const void    *x;         /* [K, N, n_in]: the row decision (k, i) was taken on */
+    const double  *raw_action;/* [K, N, n_out]: raw_actions_out of the launch */
+    const double  *old_logp;  /* [K, N]: logp_out of the launch */
+    const double  *advantage; /* [K, N] */
+    const double  *returns;   /* [K, N]; NULL without a critic */
+    const uint8_t *mask;      /* [K, N] or NULL */
+    double clip_eps;          /* >= 0; +inf: no clipping */
+    double vf_coef, ent_coef;
+    double *g_w1, *g_b1;      /* [n_hidden, n_in], [n_hidden]; each output may be NULL */
+    double *g_w2, *g_b2;      /* [n_out, n_mid], [n_out] */
+    double *g_cw, *g_cb;      /* [n_mid], [1]; NULL without a critic */
+    double *g_log_sigma;      /* [4]; entries o >= n_out and those of a dead column are 0.0 */
+    double *stats;            /* [5] */
+    double *ratio_out;        /* [K, N] */
+    void   *workspace;        /* mgx_policy_grad_workspace bytes, at least (it serves both calls); 8-byte aligned */
+    int64_t workspace_bytes;
+};
+
+/* Two launches: policy_grad_kernel with the Gaussian head and policy_grad_finish_kernel.  Of `gaussian` only sigma[0 .. n_out) and
+ * scale are read (all four sigma are checked): no draw is made.  critic may be NULL as in mgx_policy_grad.  Nothing is launched when
+ * the call is refused: everything mgx_policy_grad refuses, with gaussian / raw_action / old_logp in the place of sampling / action_id
+ * / old_prob; MGX_ERR_INVALID on top for gaussian->struct_size != sizeof(mgx_gaussian), a sigma[o] that is negative, NaN, infinite
+ * or positive and subnormal, and n_out outside 1 .. 4.  An ADDITION to ABI 9 that leaves MGX_ABI_MINOR at 3: found by name (dlsym). */
+int mgx_policy_grad_gaussian(int64_t N, int32_t K, const mgx_policy *policy, const mgx_critic *critic, const mgx_gaussian *gaussian,
+                             const struct mgx_policy_grad_gaussian *pg, mgx_stream stream);
+
 /* WHAT-IF roll-outs of candidate plans ("shooting" model-predictive control): what would grid i earn over the next H steps under
  * plan c, without taking those steps.  It stands in for the horizon loop of ModelPredictiveControl (algos/mpc/mpc.py: the cost of
  * running the microgrid over the forecast horizon, on the series a forecaster="oracle" shows) with the simulator in the place of the

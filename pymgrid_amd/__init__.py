@@ -13,7 +13,8 @@ from .graph import GraphedRollout  # noqa: F401
 from .hetero import BucketedFleet, PerGridWindowEnv, PerGridWindowFleet  # noqa: F401
 from .mpc import CEMPlanner, ShootingMPC, cem_key, lookahead_host, shooting_candidates  # noqa: F401
 from .policy import (Exploration, GaussianSampling, MLPPolicy, Sampling, ValueHead, cem_candidates_host,  # noqa: F401
-                     cem_refit_host, decision_rows, gae, ppo_grad, ppo_grad_flat, ppo_grad_host)
+                     cem_refit_host, decision_rows, gae, ppo_grad, ppo_grad_flat, ppo_grad_gaussian, ppo_grad_gaussian_host,
+                     ppo_grad_host)
 from .priority_list import get_priority_lists  # noqa: F401
 from .rbc import RuleBasedControl  # noqa: F401
 from .trajectory import (BatteryDischargeShaper, DeterministicTrajectory,  # noqa: F401

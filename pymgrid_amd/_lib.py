@@ -28,7 +28,7 @@ UNITS = (
     ("mgx_policy_head_episodes.hip", "MGX_EPISODE_PART", 2),            # ... the closed-loop roll-out with a head (UNIT_HEADS)
     ("mgx_step_policy_head_episodes.hip", "MGX_EPISODE_PART", 2),       # ... and its continuous twin,
     ("mgx_gae.hip", None, 1),                                           # the advantages of what such launches return (mgx_gae)
-    ("mgx_policy_grad.hip", "MGX_POLICY_GRAD_PART", 4),                 # ... and the PPO / A2C gradient of them (mgx_policy_grad), sliced by row width
+    ("mgx_policy_grad.hip", "MGX_POLICY_GRAD_PART", 4),                 # ... and the PPO / A2C gradient of them (mgx_policy_grad[_gaussian]), sliced by row width (UNIT_HEADS)
     ("mgx_lookahead_episodes.hip", "MGX_EPISODE_PART", 2),              # what-if roll-outs of candidate plans, nothing committed
     ("mgx_lookahead_step_episodes.hip", "MGX_EPISODE_PART", 2),         # ... and their continuous twin
     ("mgx_lookahead_gaussian_episodes.hip", "MGX_EPISODE_PART", 2),     # ... with the candidates drawn inside the launch (CEM)
@@ -39,6 +39,7 @@ UNITS = (
 UNIT_HEADS = {
     "mgx_policy_head_episodes.hip": ("MGX_POLICY_HEAD", (1, 2, 3)),         # exploring, sampling, sampling with a critic
     "mgx_step_policy_head_episodes.hip": ("MGX_POLICY_HEAD", (1, 4, 5)),    # exploring, Gaussian, Gaussian with a critic
+    "mgx_policy_grad.hip": ("MGX_POLICY_GRAD_HEAD", (0, 1)),                # PolicyGradHead (csrc/mgx_policy_grad.hpp): softmax, Gaussian
 }
 # everything a built library is stamped with (source_hash): a file missing here would leave a stale libmgx.so looking current
 SOURCES = [os.path.join(_PKG, "csrc", f) for f in [u[0] for u in UNITS] + ["mgx_kernels.hpp", "mgx_core.hpp", "mgx_step_hot.hpp", "mgx_episode_loop.hpp", "mgx_episode_rows.hpp", "mgx_policy.hpp", "mgx_gae.hpp", "mgx_policy_grad.hpp", "mgx_lookahead.hpp", "mgx_cem.hpp"]] + \
@@ -223,6 +224,16 @@ class PolicyGrad(C.Structure):
                [("workspace_bytes", C.c_int64)]
 
 
+class PolicyGradGaussian(C.Structure):
+    """mgx_policy_grad_gaussian (include/mgx.h): ``PolicyGrad`` for the Gaussian head -- ``raw_action`` [K, N, n_out] and ``old_logp`` in
+    the place of the ids and their probabilities, ``g_log_sigma`` [4] among the outputs, ``stats`` [5]."""
+    _fields_ = [("struct_size", C.c_int32), ("x_f32", C.c_int32)] + \
+               [(n, C.c_void_p) for n in ("x", "raw_action", "old_logp", "advantage", "returns", "mask")] + \
+               [(n, C.c_double) for n in ("clip_eps", "vf_coef", "ent_coef")] + \
+               [(n, C.c_void_p) for n in ("g_w1", "g_b1", "g_w2", "g_b2", "g_cw", "g_cb", "g_log_sigma", "stats", "ratio_out", "workspace")] + \
+               [("workspace_bytes", C.c_int64)]
+
+
 POLICY_MAX_HIDDEN = 64     # MGX_POLICY_MAX_HIDDEN
 POLICY_LDS_BYTES = 32768   # MGX_POLICY_LDS_BYTES
 
@@ -321,6 +332,8 @@ SYMBOLS = {
     "mgx_policy_grad_workspace": (C.c_int, [C.c_int64, C.c_int32, C.POINTER(Policy), C.POINTER(C.c_int64)]),
     "mgx_policy_grad": (C.c_int, [C.c_int64, C.c_int32, C.POINTER(Policy), C.POINTER(Critic), C.POINTER(Sampling), C.POINTER(PolicyGrad),
                                   C.c_void_p]),
+    "mgx_policy_grad_gaussian": (C.c_int, [C.c_int64, C.c_int32, C.POINTER(Policy), C.POINTER(Critic), C.POINTER(Gaussian),
+                                           C.POINTER(PolicyGradGaussian), C.c_void_p]),
     "mgx_lookahead_episodes": (C.c_int, [C.c_void_p, C.c_void_p, c_i32_p, C.c_int32, C.POINTER(Lookahead), C.c_void_p]),
     "mgx_lookahead_step_k_episodes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(Lookahead), C.c_void_p]),
     "mgx_lookahead_gaussian_episodes": (C.c_int, [C.c_void_p, C.POINTER(Cem), C.POINTER(Lookahead), C.c_void_p]),

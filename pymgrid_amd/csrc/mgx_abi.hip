@@ -2490,18 +2490,23 @@ struct GaussianCall {
     const CriticCall *cc;
     double *raw_out, *logp_out;
 };
-static int gaussian_refusal(const GaussianCall &gc, const char *fn, EpisodePolicyLaunch &P)
+// (the struct alone: what mgx_policy_grad_gaussian checks of it too)
+static int gaussian_struct_refusal(const mgx_gaussian *gs, const char *fn, GaussianArgs &ga)
 {
-    const mgx_gaussian *gs = gc.gaussian;
     if (gs->struct_size != (int32_t)sizeof(mgx_gaussian))
         return fail(MGX_ERR_INVALID, "%s: gaussian->struct_size is %d, sizeof(mgx_gaussian) is %d", fn, gs->struct_size, (int)sizeof(mgx_gaussian));
-    P.gs = GaussianArgs{gs->seed, {0.0, 0.0, 0.0, 0.0}, gs->scale};
+    ga = GaussianArgs{gs->seed, {0.0, 0.0, 0.0, 0.0}, gs->scale};
     for (int32_t o = 0; o < 4; o++) {
         const double v = gs->sigma[o];
         if (!(v == 0.0 || (v >= 2.2250738585072014e-308 && v < __builtin_inf())))      // (DBL_MIN: L needs a normal number)
             return fail(MGX_ERR_INVALID, "%s: gaussian->sigma[%d] is %g: 0 or a positive, finite, normal number", fn, o, v);
-        P.gs.sigma[o] = v == 0.0 ? 0.0 : v;                                              // (-0.0 becomes +0.0)
+        ga.sigma[o] = v == 0.0 ? 0.0 : v;                                                // (-0.0 becomes +0.0)
     }
+    return MGX_OK;
+}
+static int gaussian_refusal(const GaussianCall &gc, const char *fn, EpisodePolicyLaunch &P)
+{
+    if (int rc = gaussian_struct_refusal(gc.gaussian, fn, P.gs)) return rc;
     P.raw_out = gc.raw_out; P.logp_out = gc.logp_out;
     const CriticCall &cc = *gc.cc;
     if (!cc.critic) {
@@ -2990,6 +2995,76 @@ int mgx_policy_grad_workspace(int64_t N, int32_t K, const mgx_policy *policy, in
     return MGX_OK;
 }
 
+// What the two gradient calls share behind the checks of their head: a view of the caller's struct (mgx_policy_grad,
+// mgx_policy_grad_gaussian), the rest of the refusals and the two launches.  `g` arrives with the head's part filled in.
+struct PolicyGradCall {
+    int32_t x_f32;
+    const void *x, *taken;           // taken: action_id / raw_action
+    const double *old, *advantage, *returns;
+    const uint8_t *mask;
+    double clip_eps, vf_coef, ent_coef;
+    double *g_w1, *g_b1, *g_w2, *g_b2, *g_cw, *g_cb, *g_ls, *stats, *ratio_out;
+    void *workspace;
+    int64_t workspace_bytes;
+    int head;                        // PolicyGradHead
+    const char *inputs;              // the names of x, taken, old and advantage in the caller's struct
+};
+// (a macro: the two structs share field names, not a type, and this part of the file has C linkage)
+#define MGX_POLICY_GRAD_VIEW(pg, taken, old, g_ls, head, inputs)                                                                    \
+    PolicyGradCall{(pg)->x_f32, (pg)->x, taken, old, (pg)->advantage, (pg)->returns, (pg)->mask, (pg)->clip_eps, (pg)->vf_coef,     \
+                   (pg)->ent_coef, (pg)->g_w1, (pg)->g_b1, (pg)->g_w2, (pg)->g_b2, (pg)->g_cw, (pg)->g_cb, g_ls, (pg)->stats,        \
+                   (pg)->ratio_out, (pg)->workspace, (pg)->workspace_bytes, head, inputs}
+
+static int policy_grad_call(int64_t N, int32_t K, const mgx_policy *policy, const mgx_critic *critic, const PolicyGradCall &c,
+                            PolicyGradArgs &g, mgx_stream stream, const char *fn)
+{
+    if (critic) {
+        if (critic->struct_size != (int32_t)sizeof(mgx_critic))
+            return fail(MGX_ERR_INVALID, "%s: critic->struct_size is %d, sizeof(mgx_critic) is %d", fn, critic->struct_size, (int)sizeof(mgx_critic));
+        if (!critic->w || !critic->b) return fail(MGX_ERR_INVALID, "%s: NULL critic weights", fn);
+        if (!c.returns) return fail(MGX_ERR_INVALID, "%s: NULL returns with a critic", fn);
+        g.cr = CriticArgs{critic->w, critic->b};
+    } else if (c.returns || c.g_cw || c.g_cb) {
+        return fail(MGX_ERR_INVALID, "%s: returns, g_cw or g_cb given without a critic", fn);
+    }
+    if (!c.x || !c.taken || !c.old || !c.advantage) return fail(MGX_ERR_INVALID, "%s: NULL %s", fn, c.inputs);
+    if (c.x_f32 != 0 && c.x_f32 != 1) return fail(MGX_ERR_INVALID, "%s: x_f32 = %d (0: float64 rows, 1: float32 rows)", fn, c.x_f32);
+    if (!(c.clip_eps >= 0.0)) return fail(MGX_ERR_INVALID, "%s: clip_eps = %g is negative or NaN", fn, c.clip_eps);
+    if (c.vf_coef != c.vf_coef || c.ent_coef != c.ent_coef) return fail(MGX_ERR_INVALID, "%s: a NaN coefficient", fn);
+    const int64_t need = policy_grad_workspace_bytes(N, K, policy->n_hidden);
+    if (!c.workspace || c.workspace_bytes < need)
+        return fail(MGX_ERR_INVALID, "%s: a workspace of %lld bytes, mgx_policy_grad_workspace asks for %lld", fn,
+                    (long long)(c.workspace ? c.workspace_bytes : 0), (long long)need);
+    int ndev = 0;
+    hipError_t e = hipGetDeviceCount(&ndev);
+    if (e != hipSuccess || ndev <= 0) return fail(MGX_ERR_DEVICE, "%s: no HIP device available -- this engine has no CPU path", fn);
+    // (groups of four outputs: the discrete launch's; the continuous policy padded to four, its y[o] bit for bit the launch's -- each output's sum is its own)
+    const int32_t D = policy->n_in, nh = policy->n_hidden, n_staged = (policy->n_out + 3) / 4 * 4;
+    const int32_t stride = ((critic ? policy_critic_set_doubles(D, nh, n_staged) : policy_set_doubles(D, nh, n_staged)) + 1) & ~1;
+    g.pol = PolicyArgs{policy->w1, policy->b1, policy->w2, policy->b2, nullptr, 1, nh, n_staged, policy->n_out, stride};
+    const PolicyGradShape s = policy_grad_shape(N, K);
+    g.N = N; g.K = K; g.kc = s.kc; g.x_f32 = c.x_f32;
+    g.x = c.x; g.old_prob = c.old; g.advantage = c.advantage; g.returns = c.returns;
+    if (c.head == PG_HEAD_GAUSSIAN) g.raw_action = (const double *)c.taken;
+    else g.action_id = (const uint8_t *)c.taken;
+    g.mask = c.mask;
+    g.hi = 1.0 + c.clip_eps; g.lo = 1.0 - c.clip_eps; g.vf_coef = c.vf_coef; g.ent_coef = c.ent_coef;
+    g.ratio_out = c.ratio_out; g.ws = (double *)c.workspace;
+    const unsigned lds = (unsigned)stride * (unsigned)sizeof(double);
+    typedef bool (*Part)(const PolicyGradArgs &, int32_t, bool, unsigned, hipStream_t);
+    static const Part part[2][4] = {{launch_policy_grad_p0, launch_policy_grad_p1, launch_policy_grad_p2, launch_policy_grad_p3},
+                                    {launch_policy_grad_gaussian_p0, launch_policy_grad_gaussian_p1, launch_policy_grad_gaussian_p2,
+                                     launch_policy_grad_gaussian_p3}};
+    if (!part[c.head][(D - 1) / PG_PART_DIMS](g, D, critic != nullptr, lds, (hipStream_t)stream))
+        return fail(MGX_ERR_INVALID, "%s: no kernel for rows of %d columns", fn, D);
+    if (int rc = launched("policy_grad_kernel launch")) return rc;
+    const bool gaussian = c.head == PG_HEAD_GAUSSIAN;
+    launch_policy_grad_finish(PolicyGradFinishArgs{g.ws, (int32_t)(s.bx * s.by), nh, policy->n_out, D, c.g_w1, c.g_b1, c.g_w2, c.g_b2, c.g_cw,
+                                                   c.g_cb, c.stats, gaussian ? c.g_ls : nullptr, gaussian && c.stats ? c.stats + 4 : nullptr},
+                              (hipStream_t)stream);
+    return launched("policy_grad_finish_kernel launch");
+}
+
 int mgx_policy_grad(int64_t N, int32_t K, const mgx_policy *policy, const mgx_critic *critic, const mgx_sampling *sampling,
                     const struct mgx_policy_grad *pg, mgx_stream stream)
 {
@@ -3003,45 +3078,28 @@ int mgx_policy_grad(int64_t N, int32_t K, const mgx_policy *policy, const mgx_cr
     if (!sampling) return fail(MGX_ERR_INVALID, "%s: NULL sampling", fn);
     PolicyGradArgs g{};
     if (int rc = sampling_refusal(sampling, fn, g.sa)) return rc;
-    if (critic) {
-        if (critic->struct_size != (int32_t)sizeof(mgx_critic))
-            return fail(MGX_ERR_INVALID, "%s: critic->struct_size is %d, sizeof(mgx_critic) is %d", fn, critic->struct_size, (int)sizeof(mgx_critic));
-        if (!critic->w || !critic->b) return fail(MGX_ERR_INVALID, "%s: NULL critic weights", fn);
-        if (!pg->returns) return fail(MGX_ERR_INVALID, "%s: NULL returns with a critic", fn);
-        g.cr = CriticArgs{critic->w, critic->b};
-    } else if (pg->returns || pg->g_cw || pg->g_cb) {
-        return fail(MGX_ERR_INVALID, "%s: returns, g_cw or g_cb given without a critic", fn);
-    }
-    if (!pg->x || !pg->action_id || !pg->old_prob || !pg->advantage)
-        return fail(MGX_ERR_INVALID, "%s: NULL x, action_id, old_prob or advantage", fn);
-    if (pg->x_f32 != 0 && pg->x_f32 != 1) return fail(MGX_ERR_INVALID, "%s: x_f32 = %d (0: float64 rows, 1: float32 rows)", fn, pg->x_f32);
-    if (!(pg->clip_eps >= 0.0)) return fail(MGX_ERR_INVALID, "%s: clip_eps = %g is negative or NaN", fn, pg->clip_eps);
-    if (pg->vf_coef != pg->vf_coef || pg->ent_coef != pg->ent_coef) return fail(MGX_ERR_INVALID, "%s: a NaN coefficient", fn);
-    const int64_t need = policy_grad_workspace_bytes(N, K, policy->n_hidden);
-    if (!pg->workspace || pg->workspace_bytes < need)
-        return fail(MGX_ERR_INVALID, "%s: a workspace of %lld bytes, mgx_policy_grad_workspace asks for %lld", fn,
-                    (long long)(pg->workspace ? pg->workspace_bytes : 0), (long long)need);
-    int ndev = 0;
-    hipError_t e = hipGetDeviceCount(&ndev);
-    if (e != hipSuccess || ndev <= 0) return fail(MGX_ERR_DEVICE, "%s: no HIP device available -- this engine has no CPU path", fn);
-    const int32_t D = policy->n_in, nh = policy->n_hidden, n_staged = (policy->n_out + 3) / 4 * 4;    // (the discrete launch's groups of four)
-    const int32_t stride = ((critic ? policy_critic_set_doubles(D, nh, n_staged) : policy_set_doubles(D, nh, n_staged)) + 1) & ~1;
-    g.pol = PolicyArgs{policy->w1, policy->b1, policy->w2, policy->b2, nullptr, 1, nh, n_staged, policy->n_out, stride};
-    const PolicyGradShape s = policy_grad_shape(N, K);
-    g.N = N; g.K = K; g.kc = s.kc; g.x_f32 = pg->x_f32;
-    g.x = pg->x; g.action_id = pg->action_id; g.old_prob = pg->old_prob; g.advantage = pg->advantage; g.returns = pg->returns;
-    g.mask = pg->mask;
-    g.hi = 1.0 + pg->clip_eps; g.lo = 1.0 - pg->clip_eps; g.vf_coef = pg->vf_coef; g.ent_coef = pg->ent_coef;
-    g.ratio_out = pg->ratio_out; g.ws = (double *)pg->workspace;
-    const unsigned lds = (unsigned)stride * (unsigned)sizeof(double);
-    bool (*const part[])(const PolicyGradArgs &, int32_t, bool, unsigned, hipStream_t) = {launch_policy_grad_p0, launch_policy_grad_p1,
-                                                                                         launch_policy_grad_p2, launch_policy_grad_p3};
-    if (!part[(D - 1) / PG_PART_DIMS](g, D, critic != nullptr, lds, (hipStream_t)stream))
-        return fail(MGX_ERR_INVALID, "%s: no kernel for rows of %d columns", fn, D);
-    if (int rc = launched("policy_grad_kernel launch")) return rc;
-    launch_policy_grad_finish(PolicyGradFinishArgs{g.ws, (int32_t)(s.bx * s.by), nh, policy->n_out, D, pg->g_w1, pg->g_b1, pg->g_w2, pg->g_b2,
-                                                   pg->g_cw, pg->g_cb, pg->stats}, (hipStream_t)stream);
-    return launched("policy_grad_finish_kernel launch");
+    return policy_grad_call(N, K, policy, critic, MGX_POLICY_GRAD_VIEW(pg, pg->action_id, pg->old_prob, nullptr, PG_HEAD_SOFTMAX,
+                                                                       "x, action_id, old_prob or advantage"), g, stream, fn);
+}
+
+int mgx_policy_grad_gaussian(int64_t N, int32_t K, const mgx_policy *policy, const mgx_critic *critic, const mgx_gaussian *gaussian,
+                             const struct mgx_policy_grad_gaussian *pg, mgx_stream stream)
+{
+    g_err[0] = 0;
+    const char *fn = "mgx_policy_grad_gaussian";
+    if (!pg) return fail(MGX_ERR_INVALID, "%s: NULL pg", fn);
+    if (pg->struct_size != (int32_t)sizeof(struct mgx_policy_grad_gaussian))
+        return fail(MGX_ERR_INVALID, "%s: pg->struct_size is %d, sizeof(struct mgx_policy_grad_gaussian) is %d", fn, pg->struct_size,
+                    (int)sizeof(struct mgx_policy_grad_gaussian));
+    if (int rc = policy_grad_dims_refusal(N, K, policy, fn)) return rc;
+    if (policy->n_out > PG_NO_GAUSSIAN)
+        return fail(MGX_ERR_INVALID, "%s: policy->n_out is %d: a continuous policy has 1 .. %d action columns", fn, policy->n_out, PG_NO_GAUSSIAN);
+    if (!gaussian) return fail(MGX_ERR_INVALID, "%s: NULL gaussian", fn);
+    PolicyGradArgs g{};
+    if (int rc = gaussian_struct_refusal(gaussian, fn, g.gs)) return rc;
+    for (int32_t o = policy->n_out; o < 4; o++) g.gs.sigma[o] = 0.0;       // (a column the policy does not have is dead: its raw action is never read)
+    return policy_grad_call(N, K, policy, critic, MGX_POLICY_GRAD_VIEW(pg, pg->raw_action, pg->old_logp, pg->g_log_sigma, PG_HEAD_GAUSSIAN,
+                                                                       "x, raw_action, old_logp or advantage"), g, stream, fn);
 }
 
 int mgx_normalise_series(mgx_handle *h, void *load_n, void *pv_n, void *grid_n, int32_t *clipped, mgx_stream stream)

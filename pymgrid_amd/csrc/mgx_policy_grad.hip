@@ -8,10 +8,18 @@
 // chunk.  One tile serves all four operands in turn: the operands of X and dY are kept in registers (16 doubles each) across the
 // hidden tiles.  At the end the four waves of a workgroup are added in wave order and the workgroup's partial goes to the workspace
 // with vector stores; policy_grad_finish_kernel adds the partials in a fixed order, multiplies by 1 / M and scatters.  No atomics.
+// ONE kernel text for the two heads (PolicyGradHead, the last template argument): the softmax head of the discrete policy
+// (mgx_policy_grad) and the Gaussian head of the continuous one (mgx_policy_grad_gaussian: the density of the pre-clip action by the
+// rule of mgx_gaussian, policy_log / policy_exp / gaussian_lane_const of mgx_policy.hpp).  A head (PgHead) is what lies between the
+// forward outputs and dy, the statistic rows and rows 0 .. 11 of the dY tile; everything else -- the operand reads, the MFMAs, the
+// hidden-tile passes, the epilogue, the finish kernel -- is stated once.  An object holds one head of one slice.
 #include "mgx_policy_grad.hpp"
 
 #ifndef MGX_POLICY_GRAD_PART
 #define MGX_POLICY_GRAD_PART 0
+#endif
+#ifndef MGX_POLICY_GRAD_HEAD
+#define MGX_POLICY_GRAD_HEAD 0
 #endif
 
 namespace mgx {
@@ -62,59 +70,30 @@ __device__ __forceinline__ void pg_store_tile(const pg_f64x4 &acc, double *tiles
     __syncthreads();
 }
 
-template <int D, bool CRITIC>
-__global__ __launch_bounds__(BLOCK_K) void policy_grad_kernel(const PolicyGradArgs g)
-{
-    constexpr int NO = PG_NO;
-    static_assert(BLOCK_K == PG_TILE_DOUBLES, "one thread per element of an accumulator tile");
-    extern __shared__ __attribute__((aligned(16))) double policy_lds[];
-    __shared__ __attribute__((aligned(16))) double tiles[PG_WAVES * 64 * PG_PITCH];
-    __shared__ long long counts[PG_WAVES][2];
-    if constexpr (CRITIC) stage_policy_critic(g.pol, g.cr, D, policy_lds);      // (ends in a barrier; no lane leaves before the end)
-    else stage_policy(g.pol, D, policy_lds);
-    const int lane = threadIdx.x & 63;
-    double *tile = tiles + (threadIdx.x >> 6) * (64 * PG_PITCH);
-    double *row = tile + lane * PG_PITCH;
-    const int64_t N = g.N;
-    const int64_t i = (int64_t)blockIdx.x * BLOCK_K + threadIdx.x;
-    const bool in = i < N;
-    const int64_t ic = in ? i : N - 1;                                          // a lane past N reads grid N - 1 and supplies zeros
-    const int32_t nh = g.pol.n_hidden, no = g.pol.n_out, nr = g.pol.n_real;
-    const int32_t nt = (nh + PG_TILE - 1) / PG_TILE;
-    const int32_t rec = D + 1 + no + (CRITIC ? 1 : 0);                          // a unit's record in the staged set
-    const double *units = policy_lds + no + (CRITIC ? 1 : 0);
-    const double beta = sample_lane_beta(g.sa, ic);
-    const bool sampling = beta >= 0.0;                                          // (false: the greedy head, no policy and entropy terms)
-    const double b = sampling ? beta : 0.0;
-    const uint8_t *__restrict__ mask = g.mask;
-    const double hi = g.hi, lo = g.lo, vf = g.vf_coef, ec = g.ent_coef;
-    pg_f64x4 acc0 = {0.0, 0.0, 0.0, 0.0};
-    pg_f64x4 acc_w2[PG_MAX_HIDDEN_TILES], acc_w1[PG_MAX_HIDDEN_TILES];
-#pragma unroll
-    for (int t = 0; t < PG_MAX_HIDDEN_TILES; t++) acc_w2[t] = acc_w1[t] = acc0;
-    long long n_live = 0, n_clip = 0;
-    const int32_t k0 = (int32_t)blockIdx.y * g.kc;
-    const int32_t k1 = k0 + g.kc < g.K ? k0 + g.kc : g.K;
-#pragma nounroll
-    for (int32_t k = k0; k < k1; k++) {
-        const int64_t e64 = (int64_t)k * N + ic;
-        const bool live = in && (!mask || mask[e64] != 0);
-        double x[D], y[NO];
-        if (g.x_f32) {
-            const float *__restrict__ xp = (const float *)g.x + e64 * D;
-#pragma unroll
-            for (int j = 0; j < D; j++) x[j] = (double)xp[j];
-        } else {
-            const double *__restrict__ xp = (const double *)g.x + e64 * D;
-#pragma unroll
-            for (int j = 0; j < D; j++) x[j] = xp[j];
-        }
+// ---- the heads: from the forward outputs y of one sample to dy, its ratio, policy loss and entropy, and to rows 0 .. 11 of the
+// dY tile.  `on`: the head is on for the lane (off: no policy and entropy terms, the value term stays); `active`: the surrogate's gate.
+template <int HEAD>
+struct PgHead;
+
+// The softmax head of the discrete policy: the rule of mgx_policy_grad, the forward text that of the sampling launch (policy_argmax,
+// policy_exp: mgx_policy.hpp), so the probability ratio of an un-updated policy is exactly 1.0.
+template <>
+struct PgHead<PG_HEAD_SOFTMAX> {
+    static constexpr int NO = PG_NO;
+    struct Sample {
+        double rho, pl, H;
+        bool on, active;
+    };
+    double beta;                                                                // of the lane's grid; negative: the greedy head (off)
+    __device__ __forceinline__ PgHead(const PolicyGradArgs &g, int64_t ic) : beta(sample_lane_beta(g.sa, ic)) {}
+    __device__ __forceinline__ Sample sample(const PolicyGradArgs &g, int64_t e64, int32_t nr, bool live, double A, const double (&y)[NO],
+                                             double (&dy)[NO]) const
+    {
+        const bool sampling = beta >= 0.0;                                      // (false: the greedy head, no policy and entropy terms)
+        const double b = sampling ? beta : 0.0;
+        const double hi = g.hi, lo = g.lo, ec = g.ent_coef;
         const int32_t a = (int32_t)g.action_id[e64];
-        const double old = g.old_prob[e64], A = g.advantage[e64];
-        // ---- forward: the launch's own text ----
-        [[maybe_unused]] double V = 0.0;
-        if constexpr (CRITIC) policy_outputs_value<D, NO>(policy_lds, nh, no, x, y, V);
-        else policy_outputs<D, NO>(policy_lds, nh, no, x, y);
+        const double old = g.old_prob[e64];
         double best;
         const int32_t gid = policy_argmax<NO>(y, nr, best);
         double d[NO], e[NO];                                                    // d[o], and the weights e[o] of mgx_sampling
@@ -139,10 +118,12 @@ __global__ __launch_bounds__(BLOCK_K) void policy_grad_kernel(const PolicyGradAr
         double e_a = 0.0;
 #pragma unroll
         for (int o = 0; o < NO; o++) e_a = o == a ? e[o] : e_a;
-        const double rho = (sampling ? e_a / S : 1.0) / old;
-        const bool active = !((A > 0.0 && rho > hi) || (A < 0.0 && rho < lo));
-        const double c_s = sampling && active ? -(A * rho) : 0.0;
-        const double pl = sampling ? (active ? c_s : -(A * (A > 0.0 ? hi : lo))) : 0.0;
+        Sample r;
+        r.on = sampling;
+        r.rho = (sampling ? e_a / S : 1.0) / old;
+        r.active = !((A > 0.0 && r.rho > hi) || (A < 0.0 && r.rho < lo));
+        const double c_s = sampling && r.active ? -(A * r.rho) : 0.0;
+        r.pl = sampling ? (r.active ? c_s : -(A * (A > 0.0 ? hi : lo))) : 0.0;
         const double lnS = policy_log(S);
         double pi[NO], Hs = 0.0;
 #pragma unroll
@@ -151,23 +132,164 @@ __global__ __launch_bounds__(BLOCK_K) void policy_grad_kernel(const PolicyGradAr
             d[o] = d[o] - lnS;                                                  // logpi[o], where e[o] > 0
             Hs = e[o] > 0.0 ? Hs + pi[o] * d[o] : Hs;
         }
-        const double H = -Hs;
-        double dy[NO];
+        r.H = -Hs;
 #pragma unroll
         for (int o = 0; o < NO; o++) {
-            const double ent = e[o] > 0.0 ? pi[o] * (d[o] + H) : 0.0;
+            const double ent = e[o] > 0.0 ? pi[o] * (d[o] + r.H) : 0.0;
             const double v = b * (c_s * ((o == a ? 1.0 : 0.0) - pi[o]) + ec * ent);
             dy[o] = live && sampling ? v : 0.0;
         }
+        return r;
+    }
+    __device__ __forceinline__ void rows(double *row, bool, const double (&dy)[NO], const Sample &) const
+    {
+#pragma unroll
+        for (int o = 0; o < NO; o++) row[o] = dy[o];
+    }
+};
+
+// The Gaussian head of the continuous policy: the rule of mgx_policy_grad_gaussian.  s[o], the live columns and the constant C are
+// those of mgx_gaussian (gaussian_lane_const); the density is that of the pre-clip action the launch returned.  sigma[o] past the
+// policy's n_out is 0.0 (the host side sees to it): such a column is dead, and its raw action is never read.
+template <>
+struct PgHead<PG_HEAD_GAUSSIAN> {
+    static constexpr int NO = PG_NO_GAUSSIAN;
+    struct Sample {
+        double rho, pl, H;
+        bool on, active;
+        double dls[NO], kl;
+    };
+    double sc, C, Hc;                                                           // the lane's scale, its C and its entropy: constants of the grid
+    __device__ __forceinline__ PgHead(const PolicyGradArgs &g, int64_t ic)
+    {
+        sc = explore_lane_scale(g.gs.scale, ic);
+        C = gaussian_lane_const<NO>([&](int o) { return g.gs.sigma[o]; }, sc);
+        double H = 0.0;
+#pragma unroll
+        for (int o = 0; o < NO; o++) {
+            const double s = g.gs.sigma[o] * sc;
+            const bool lv = s > 0.0;
+            const double term = policy_log(lv ? s : 1.0) + 1.4189385332046727;  // (1 + log(2 pi)) / 2
+            H = lv ? H + term : H;
+        }
+        Hc = H;
+    }
+    __device__ __forceinline__ Sample sample(const PolicyGradArgs &g, int64_t e64, int32_t nr, bool live, double A, const double (&y)[NO],
+                                             double (&dy)[NO]) const
+    {
+        const double hi = g.hi, lo = g.lo, ec = g.ent_coef;
+        const double *__restrict__ rp = g.raw_action + e64 * nr;
+        double zeta[NO], sd[NO], Q = 0.0;
+        bool lv[NO], any = false;
+#pragma unroll
+        for (int o = 0; o < NO; o++) {
+            const double s = g.gs.sigma[o] * sc;
+            lv[o] = s > 0.0;                                                    // (false past n_out: sigma is 0.0 there)
+            sd[o] = lv[o] ? s : 1.0;
+            const double raw = o < nr ? rp[o] : 0.0;
+            zeta[o] = (raw - y[o]) / sd[o];
+            Q = lv[o] ? Q + zeta[o] * zeta[o] : Q;
+            any = any || lv[o];
+        }
+        const double logp = (-0.5 * Q) - C;
+        const double Dl = logp - g.old_prob[e64];
+        const bool nan = Dl != Dl;
+        const double Dz = nan ? 0.0 : Dl;
+        const bool down = Dz <= 0.0;
+        const double m = down ? Dz : -Dz;
+        const double E = policy_exp(m < -708.0 ? -708.0 : m);
+        Sample r;
+        r.on = any;
+        r.rho = nan ? __builtin_nan("") : (down ? E : 1.0 / E);
+        r.active = !((A > 0.0 && r.rho > hi) || (A < 0.0 && r.rho < lo));
+        const double c_s = any && r.active ? -(A * r.rho) : 0.0;
+        r.pl = any ? (r.active ? c_s : -(A * (A > 0.0 ? hi : lo))) : 0.0;
+        r.H = Hc;
+        r.kl = any ? (r.rho - 1.0) - Dl : 0.0;
+#pragma unroll
+        for (int o = 0; o < NO; o++) {
+            const bool on = live && lv[o];
+            dy[o] = on ? c_s * (zeta[o] / sd[o]) : 0.0;
+            r.dls[o] = on ? (c_s * (zeta[o] * zeta[o] - 1.0)) - ec : 0.0;
+        }
+        return r;
+    }
+    __device__ __forceinline__ void rows(double *row, bool live, const double (&dy)[NO], const Sample &r) const
+    {
+#pragma unroll
+        for (int o = 0; o < NO; o++) {
+            row[o] = dy[o];
+            row[PG_ROW_DLS + o] = r.dls[o];
+        }
+        row[PG_ROW_KL] = live ? r.kl : 0.0;
+#pragma unroll
+        for (int j = PG_ROW_KL + 1; j < PG_ROW_DV; j++) row[j] = 0.0;
+    }
+};
+
+template <int D, bool CRITIC, int HEAD>
+__global__ __launch_bounds__(BLOCK_K) void policy_grad_kernel(const PolicyGradArgs g)
+{
+    constexpr int NO = PgHead<HEAD>::NO;
+    static_assert(BLOCK_K == PG_TILE_DOUBLES, "one thread per element of an accumulator tile");
+    static_assert(NO <= PG_ROW_DV && PG_ROW_DV == 12 && PG_ROW_STATS == 13, "the rows of the dY tile");
+    extern __shared__ __attribute__((aligned(16))) double policy_lds[];
+    __shared__ __attribute__((aligned(16))) double tiles[PG_WAVES * 64 * PG_PITCH];
+    __shared__ long long counts[PG_WAVES][2];
+    if constexpr (CRITIC) stage_policy_critic(g.pol, g.cr, D, policy_lds);      // (ends in a barrier; no lane leaves before the end)
+    else stage_policy(g.pol, D, policy_lds);
+    const int lane = threadIdx.x & 63;
+    double *tile = tiles + (threadIdx.x >> 6) * (64 * PG_PITCH);
+    double *row = tile + lane * PG_PITCH;
+    const int64_t N = g.N;
+    const int64_t i = (int64_t)blockIdx.x * BLOCK_K + threadIdx.x;
+    const bool in = i < N;
+    const int64_t ic = in ? i : N - 1;                                          // a lane past N reads grid N - 1 and supplies zeros
+    const int32_t nh = g.pol.n_hidden, no = g.pol.n_out, nr = g.pol.n_real;
+    const int32_t nt = (nh + PG_TILE - 1) / PG_TILE;
+    const int32_t rec = D + 1 + no + (CRITIC ? 1 : 0);                          // a unit's record in the staged set
+    const double *units = policy_lds + no + (CRITIC ? 1 : 0);
+    const PgHead<HEAD> head(g, ic);
+    const uint8_t *__restrict__ mask = g.mask;
+    const double vf = g.vf_coef;
+    pg_f64x4 acc0 = {0.0, 0.0, 0.0, 0.0};
+    pg_f64x4 acc_w2[PG_MAX_HIDDEN_TILES], acc_w1[PG_MAX_HIDDEN_TILES];
+#pragma unroll
+    for (int t = 0; t < PG_MAX_HIDDEN_TILES; t++) acc_w2[t] = acc_w1[t] = acc0;
+    long long n_live = 0, n_clip = 0;
+    const int32_t k0 = (int32_t)blockIdx.y * g.kc;
+    const int32_t k1 = k0 + g.kc < g.K ? k0 + g.kc : g.K;
+#pragma nounroll
+    for (int32_t k = k0; k < k1; k++) {
+        const int64_t e64 = (int64_t)k * N + ic;
+        const bool live = in && (!mask || mask[e64] != 0);
+        double x[D], y[NO];
+        if (g.x_f32) {
+            const float *__restrict__ xp = (const float *)g.x + e64 * D;
+#pragma unroll
+            for (int j = 0; j < D; j++) x[j] = (double)xp[j];
+        } else {
+            const double *__restrict__ xp = (const double *)g.x + e64 * D;
+#pragma unroll
+            for (int j = 0; j < D; j++) x[j] = xp[j];
+        }
+        const double A = g.advantage[e64];
+        // ---- forward: the launch's own text ----
+        [[maybe_unused]] double V = 0.0;
+        if constexpr (CRITIC) policy_outputs_value<D, NO>(policy_lds, nh, no, x, y, V);
+        else policy_outputs<D, NO>(policy_lds, nh, no, x, y);
+        // ---- the head: dy, the ratio, the sample's policy loss and entropy ----
+        double dy[NO];
+        const typename PgHead<HEAD>::Sample smp = head.sample(g, e64, nr, live, A, y, dy);
         double dv = 0.0, vl = 0.0;
         if constexpr (CRITIC) {
             const double diff = V - g.returns[e64];
             dv = live ? vf * diff : 0.0;
             vl = 0.5 * (diff * diff);
         }
-        if (live && g.ratio_out) g.ratio_out[e64] = rho;
+        if (live && g.ratio_out) g.ratio_out[e64] = smp.rho;
         n_live += __builtin_popcountll(__ballot(live));
-        n_clip += __builtin_popcountll(__ballot(live && sampling && !active));
+        n_clip += __builtin_popcountll(__ballot(live && smp.on && !smp.active));
         // ---- the reduction: X | 1, then dY | dv | the three statistics, then per hidden tile H_t and dH_t through the wave's tile ----
         double xop[16], dyop[16], op[16];
 #pragma unroll
@@ -175,12 +297,11 @@ __global__ __launch_bounds__(BLOCK_K) void policy_grad_kernel(const PolicyGradAr
         pg_wave_sync();
         pg_read_operands(tile, lane, xop);
         pg_wave_sync();
-#pragma unroll
-        for (int o = 0; o < NO; o++) row[o] = dy[o];
-        row[12] = dv;
-        row[13] = live ? pl : 0.0;
-        row[14] = live ? vl : 0.0;
-        row[15] = live && sampling ? H : 0.0;
+        head.rows(row, live, dy, smp);
+        row[PG_ROW_DV] = dv;
+        row[PG_ROW_STATS] = live ? smp.pl : 0.0;
+        row[PG_ROW_STATS + 1] = live ? vl : 0.0;
+        row[PG_ROW_STATS + 2] = live && smp.on ? smp.H : 0.0;
         pg_wave_sync();
         pg_read_operands(tile, lane, dyop);
         pg_wave_sync();
@@ -253,13 +374,18 @@ static void policy_grad_launch(const PolicyGradArgs &g, bool critic, unsigned ld
 {
     const PolicyGradShape s = policy_grad_shape(g.N, g.K);
     const dim3 grid(s.bx, s.by);
-    if (critic) policy_grad_kernel<D, true><<<grid, BLOCK_K, lds_bytes, stream>>>(g);
-    else policy_grad_kernel<D, false><<<grid, BLOCK_K, lds_bytes, stream>>>(g);
+    if (critic) policy_grad_kernel<D, true, MGX_POLICY_GRAD_HEAD><<<grid, BLOCK_K, lds_bytes, stream>>>(g);
+    else policy_grad_kernel<D, false, MGX_POLICY_GRAD_HEAD><<<grid, BLOCK_K, lds_bytes, stream>>>(g);
 }
 
 #define MGX_PG_CAT2(a, b) a##b
 #define MGX_PG_CAT(a, b) MGX_PG_CAT2(a, b)
-bool MGX_PG_CAT(launch_policy_grad_p, MGX_POLICY_GRAD_PART)(const PolicyGradArgs &g, int32_t D, bool critic, unsigned lds_bytes, hipStream_t stream)
+#if MGX_POLICY_GRAD_HEAD == 0
+#define MGX_PG_LAUNCH launch_policy_grad_p
+#else
+#define MGX_PG_LAUNCH launch_policy_grad_gaussian_p
+#endif
+bool MGX_PG_CAT(MGX_PG_LAUNCH, MGX_POLICY_GRAD_PART)(const PolicyGradArgs &g, int32_t D, bool critic, unsigned lds_bytes, hipStream_t stream)
 {
     constexpr int D0 = MGX_POLICY_GRAD_PART * PG_PART_DIMS + 1;
     switch (D - D0) {
@@ -270,7 +396,7 @@ bool MGX_PG_CAT(launch_policy_grad_p, MGX_POLICY_GRAD_PART)(const PolicyGradArgs
     }
 }
 
-#if MGX_POLICY_GRAD_PART == 0
+#if MGX_POLICY_GRAD_PART == 0 && MGX_POLICY_GRAD_HEAD == 0
 // The partials added up, times 1 / M, into the caller's arrays.  A workgroup serves FIN_ELEMS elements of the tiles: thread
 // (seg, el) adds the partials of its segment of workgroups in ascending order, thread (0, el) the segments in ascending order -- a
 // fixed tree, the same from run to run.  M and the clipped count are integer sums, formed by every workgroup for itself.
@@ -315,8 +441,10 @@ __global__ __launch_bounds__(BLOCK_K) void policy_grad_finish_kernel(const Polic
     if (ti == 0) {                                               // (dY | dv | stats)^T (X | 1): row o / 12 / 13 .. 15, column j / 12
         if (c == 12) {
             if (r < nr) dst = f.g_b2 ? f.g_b2 + r : nullptr;
-            else if (r == 12) dst = f.g_cb;
-            else if (r >= 13) dst = f.stats ? f.stats + (r - 13) : nullptr;
+            else if (r == PG_ROW_DV) dst = f.g_cb;
+            else if (r >= PG_ROW_STATS) dst = f.stats ? f.stats + (r - PG_ROW_STATS) : nullptr;
+            else if (r >= PG_ROW_DLS && r < PG_ROW_DLS + PG_NO_GAUSSIAN) dst = f.g_ls ? f.g_ls + (r - PG_ROW_DLS) : nullptr;   // (the Gaussian head's rows)
+            else if (r == PG_ROW_KL) dst = f.kl;
         } else if (nh == 0 && c < D) {
             if (r < nr) dst = f.g_w2 ? f.g_w2 + r * D + c : nullptr;
             else if (r == 12) dst = f.g_cw ? f.g_cw + c : nullptr;

@@ -833,16 +833,20 @@ def decision_rows(obs_before, obs):
 
 
 PPO_GRAD_NAMES = ("W1", "b1", "W2", "b2", "w", "b")      # the gradients in the order ``ppo_grad_flat`` lays them out
+PPO_GRAD_NAMES_GAUSSIAN = PPO_GRAD_NAMES + ("log_sigma",)  # ... of the Gaussian head: ``log_sigma`` [4] behind them
 
 
-def _ppo_args(policy, critic, rows, actions, old_probs, advantages, returns, sampling, clip, vf_coef, ent_coef, mask):
-    """The checks ``ppo_grad`` and ``ppo_grad_host`` share (those of ``mgx_policy_grad``): ``(K, N, clip, vf_coef, ent_coef)``."""
-    if not isinstance(policy, MLPPolicy) or policy.head != "discrete":
-        raise ValueError("the gradient is offered for an MLPPolicy with the discrete head (the continuous head is a rule of its own)")
+def _ppo_checks(policy, head, other, critic, rows, per_sample, returns, sampling, sampling_cls, clip, vf_coef, ent_coef, mask):
+    """The checks the gradients of the two heads share (those of ``mgx_policy_grad`` / ``mgx_policy_grad_gaussian``): ``(K, N, clip,
+    vf_coef, ent_coef)``.  ``per_sample``: ``(name, tensor, dtypes, trailing shape)`` of the head's own ``[K, N, ...]`` inputs."""
+    if not isinstance(policy, MLPPolicy) or policy.head != head:
+        raise ValueError(f"this gradient is offered for an MLPPolicy with the {head} head (the {'continuous' if head == 'discrete' else 'discrete'} "
+                         f"head: {other})")
     if policy.n_policies != 1 or policy.policy_index is not None:
         raise ValueError("the gradient of a population (several parameter sets, a policy_index) is not offered")
-    if not isinstance(sampling, Sampling):
-        raise ValueError("sampling must be the Sampling of the launch that collected the data (temperature and scale are read)")
+    if not isinstance(sampling, sampling_cls):
+        raise ValueError(f"sampling must be the {sampling_cls.__name__} of the launch that collected the data "
+                         f"({'temperature' if head == 'discrete' else 'sigma'} and scale are read)")
     if critic is not None:
         if not isinstance(critic, ValueHead):
             raise ValueError("critic must be a ValueHead or None")
@@ -862,23 +866,62 @@ def _ppo_args(policy, critic, rows, actions, old_probs, advantages, returns, sam
     K, N = int(rows.shape[0]), int(rows.shape[1])
     if K < 1 or N < 1:
         raise ValueError(f"rows {tuple(rows.shape)}: K and N must be positive")
-    for name, t, dts in (("actions", actions, (torch.uint8,)), ("old_probs", old_probs, (torch.float64,)),
-                         ("advantages", advantages, (torch.float64,)), ("returns", returns, (torch.float64,)),
-                         ("mask", mask, (torch.uint8, torch.bool))):
+    for name, t, dts, tail in tuple(per_sample) + (("returns", returns, (torch.float64,), ()), ("mask", mask, (torch.uint8, torch.bool), ())):
         if t is None and name in ("returns", "mask"):
             continue
-        if not torch.is_tensor(t) or t.dtype not in dts or tuple(t.shape) != (K, N):
-            raise ValueError(f"{name} must be a {' or '.join(str(d) for d in dts)} tensor [{K}, {N}], not "
+        if not torch.is_tensor(t) or t.dtype not in dts or tuple(t.shape) != (K, N) + tail:
+            raise ValueError(f"{name} must be a {' or '.join(str(d) for d in dts)} tensor {[K, N] + list(tail)}, not "
                              f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
         if t.device != rows.device:
             raise ValueError(f"{name} lies on {t.device}, rows on {rows.device}")
     return K, N, clip, vf_coef, ent_coef
 
 
+def _ppo_args(policy, critic, rows, actions, old_probs, advantages, returns, sampling, clip, vf_coef, ent_coef, mask):
+    """The checks ``ppo_grad`` and ``ppo_grad_host`` share (those of ``mgx_policy_grad``): ``(K, N, clip, vf_coef, ent_coef)``."""
+    per_sample = (("actions", actions, (torch.uint8,), ()), ("old_probs", old_probs, (torch.float64,), ()),
+                  ("advantages", advantages, (torch.float64,), ()))
+    return _ppo_checks(policy, "discrete", "ppo_grad_gaussian", critic, rows, per_sample, returns, sampling, Sampling, clip, vf_coef,
+                       ent_coef, mask)
+
+
+def _ppo_gaussian_args(policy, critic, rows, raw_actions, old_logp, advantages, returns, sampling, clip, vf_coef, ent_coef, mask):
+    """... and ``ppo_grad_gaussian`` and ``ppo_grad_gaussian_host`` (those of ``mgx_policy_grad_gaussian``)."""
+    n_out = policy.n_out if isinstance(policy, MLPPolicy) else 0
+    per_sample = (("raw_actions", raw_actions, (torch.float64,), (n_out,)), ("old_logp", old_logp, (torch.float64,), ()),
+                  ("advantages", advantages, (torch.float64,), ()))
+    res = _ppo_checks(policy, "continuous", "ppo_grad", critic, rows, per_sample, returns, sampling, GaussianSampling, clip, vf_coef,
+                      ent_coef, mask)
+    if policy.n_out < 1:
+        raise ValueError("a policy without an action column has no density")
+    return res
+
+
 def ppo_grad_flat(grads):
     """The gradients of a ``ppo_grad`` / ``ppo_grad_host`` result as one vector ``[P]``, in the order ``PPO_GRAD_NAMES`` (absent ones
-    skipped): the columns of ``ppo_grad_host(per_sample=True)["terms"]``."""
-    return torch.cat([grads[n].reshape(-1) for n in PPO_GRAD_NAMES if grads.get(n) is not None])
+    skipped): the columns of ``ppo_grad_host(per_sample=True)["terms"]``.  A result of the Gaussian head (``ppo_grad_gaussian`` /
+    ``ppo_grad_gaussian_host``) carries ``log_sigma`` [4] behind them."""
+    return torch.cat([grads[n].reshape(-1) for n in PPO_GRAD_NAMES_GAUSSIAN if grads.get(n) is not None])
+
+
+def _ppo_result(flat, stats, me, critic, log_sigma=False):
+    """``flat`` (in the order of ``ppo_grad_flat``) cut into the result of a host rule."""
+    res, at = {}, 0
+    n_mid = me.n_hidden or me.n_in
+    shapes = {"W1": (me.n_hidden, me.n_in) if me.n_hidden else None, "b1": (me.n_hidden,) if me.n_hidden else None,
+              "W2": (me.n_out, n_mid), "b2": (me.n_out,), "w": (n_mid,) if critic is not None else None,
+              "b": (1,) if critic is not None else None}
+    if log_sigma:
+        shapes["log_sigma"] = (MAX_CONTROLS,)
+    for name, shape in shapes.items():
+        if shape is None:
+            res[name] = None
+            continue
+        size = int(np.prod(shape))
+        res[name] = flat[at:at + size].reshape(shape)
+        at += size
+    res["stats"] = stats
+    return res
 
 
 def ppo_grad_host(policy, critic, rows, actions, old_probs, advantages, returns=None, sampling=None, clip=0.2, vf_coef=0.5, ent_coef=0.0,
@@ -967,23 +1010,35 @@ def ppo_grad_host(policy, critic, rows, actions, old_probs, advantages, returns=
     M = terms.shape[0]
     inv = 1.0 / M if M else 0.0
     flat, stats = inv * terms.sum(dim=0), inv * st.sum(dim=0)
-    res, at = {}, 0
-    n_mid = me.n_hidden or me.n_in
-    shapes = {"W1": (me.n_hidden, me.n_in) if me.n_hidden else None, "b1": (me.n_hidden,) if me.n_hidden else None,
-              "W2": (me.n_out, n_mid), "b2": (me.n_out,), "w": (n_mid,) if critic is not None else None,
-              "b": (1,) if critic is not None else None}
-    for name in PPO_GRAD_NAMES:
-        if shapes[name] is None:
-            res[name] = None
-            continue
-        size = int(np.prod(shapes[name]))
-        res[name] = flat[at:at + size].reshape(shapes[name])
-        at += size
-    res["stats"] = stats
+    res = _ppo_result(flat, stats, me, critic)
     if ratio:
         res["ratio"] = rho.reshape(K, N)
     if per_sample:
         res["terms"], res["stat_terms"] = terms, st
+    return res
+
+
+def _ppo_outputs(shapes, out, dev, masked):
+    """The output tensors of a device gradient call: the caller's (``out``) where given and fitting, fresh ones elsewhere."""
+    out = out or {}
+    unknown = set(out) - set(shapes)
+    if unknown:
+        raise ValueError(f"unknown outputs {sorted(unknown)}")
+    res = {}
+    for name, shape in shapes.items():
+        t = out.get(name)
+        if shape is None:
+            if t is not None:
+                raise ValueError(f"out[{name!r}] given, but this call has no such output")
+            if name != "ratio":
+                res[name] = None
+            continue
+        if t is None:                                      # (a masked sample's ratio is not written: NaN there)
+            t = torch.full(shape, float("nan"), dtype=torch.float64, device=dev) if name == "ratio" and masked else \
+                torch.empty(shape, dtype=torch.float64, device=dev)
+        elif not torch.is_tensor(t) or t.dtype != torch.float64 or t.device != dev or not t.is_contiguous() or t.numel() != int(np.prod(shape)):
+            raise ValueError(f"out[{name!r}] must be a contiguous float64 tensor of {list(shape)} on {dev}")
+        res[name] = t
     return res
 
 
@@ -1014,25 +1069,7 @@ def ppo_grad(policy, critic, rows, actions, old_probs, advantages, returns=None,
     shapes = {"W1": (policy.n_hidden, policy.n_in) if policy.n_hidden else None, "b1": (policy.n_hidden,) if policy.n_hidden else None,
               "W2": (policy.n_out, n_mid), "b2": (policy.n_out,), "w": (n_mid,) if critic is not None else None,
               "b": (1,) if critic is not None else None, "stats": (4,), "ratio": (K, N) if ratio else None}
-    out = out or {}
-    unknown = set(out) - set(shapes)
-    if unknown:
-        raise ValueError(f"unknown outputs {sorted(unknown)}")
-    res = {}
-    for name, shape in shapes.items():
-        t = out.get(name)
-        if shape is None:
-            if t is not None:
-                raise ValueError(f"out[{name!r}] given, but this call has no such output")
-            if name != "ratio":
-                res[name] = None
-            continue
-        if t is None:                                      # (a masked sample's ratio is not written: NaN there)
-            t = torch.full(shape, float("nan"), dtype=torch.float64, device=dev) if name == "ratio" and mask is not None else \
-                torch.empty(shape, dtype=torch.float64, device=dev)
-        elif not torch.is_tensor(t) or t.dtype != torch.float64 or t.device != dev or not t.is_contiguous() or t.numel() != int(np.prod(shape)):
-            raise ValueError(f"out[{name!r}] must be a contiguous float64 tensor of {list(shape)} on {dev}")
-        res[name] = t
+    res = _ppo_outputs(shapes, out, dev, mask is not None)
     lib = _lib.lib()
     ptr = lambda t: None if t is None else t.data_ptr()     # noqa: E731
     with torch.cuda.device(dev):
@@ -1054,4 +1091,147 @@ def ppo_grad(policy, critic, rows, actions, old_probs, advantages, returns=None,
         pg.workspace, pg.workspace_bytes = ws.data_ptr(), ws.numel() * 8
         _lib.check(lib.mgx_policy_grad(N, K, C.byref(pol), C.byref(cr) if cr is not None else None, C.byref(smp), C.byref(pg),
                                        torch.cuda.current_stream(dev).cuda_stream))
+    return res
+
+
+ENTROPY_CONST = 1.4189385332046727     # (1 + log(2 pi)) / 2: the entropy of a unit normal (include/mgx.h, mgx_policy_grad_gaussian)
+
+
+def ppo_grad_gaussian_host(policy, critic, rows, raw_actions, old_logp, advantages, returns=None, sampling=None, clip=0.2, vf_coef=0.5,
+                           ent_coef=0.0, mask=None, ratio=False, per_sample=False):
+    """The rule of ``mgx_policy_grad_gaussian`` (include/mgx.h) in torch, on any device, operation by operation: ``ppo_grad_host`` for the
+    Gaussian head of a continuous ``MLPPolicy`` -- the gradient of ``mean(policy loss) + vf_coef * mean(value loss) - ent_coef *
+    mean(entropy)`` with respect to the parameters and to ``log sigma``, ``{"W1", "b1", "W2", "b2", "w", "b", "log_sigma", "stats"[,
+    "ratio"]}``: ``log_sigma`` ``[4]`` (0.0 past ``n_out`` and on a column with sigma 0), ``stats`` ``[5]``: the means of policy loss,
+    value loss, entropy, clipped fraction and ``kl = (rho - 1) - (logp - old_logp)``.  ``per_sample=True`` adds ``"terms"`` ``[M, P]`` in
+    the column order of ``ppo_grad_flat`` and ``"stat_terms"`` ``[M, 5]``."""
+    K, N, clip, vf_coef, ent_coef = _ppo_gaussian_args(policy, critic, rows, raw_actions, old_logp, advantages, returns, sampling, clip,
+                                                       vf_coef, ent_coef, mask)
+    dev = rows.device
+    me = policy.to(dev)
+    n, nA = K * N, me.n_out
+    x = rows.reshape(n, me.n_in).to(torch.float64)
+    if me.n_hidden:
+        hp = MLPPolicy._layer(me.W1, me.b1, None, x)
+        h = torch.where(hp > 0, hp, torch.zeros_like(hp))
+    else:
+        h = x
+    y = MLPPolicy._layer(me.W2, me.b2, None, h)
+    zero, one = torch.zeros(n, dtype=torch.float64, device=dev), torch.ones(n, dtype=torch.float64, device=dev)
+    scale = sampling.scale_on(dev, N)
+    s = [zero + sampling.sigma[o] if scale is None else sampling.sigma[o] * scale.repeat(K) for o in range(nA)]
+    lv = [v > 0 for v in s]
+    sd = [torch.where(lv[o], s[o], one) for o in range(nA)]
+    Cn, Hc, anyl = zero, zero, torch.zeros(n, dtype=torch.bool, device=dev)
+    for o in range(nA):
+        L = policy_log(sd[o])
+        Cn = torch.where(lv[o], Cn + (L + HALF_LOG_2PI), Cn)
+        Hc = torch.where(lv[o], Hc + (L + ENTROPY_CONST), Hc)
+        anyl = anyl | lv[o]
+    raw = raw_actions.reshape(n, nA)
+    zeta, Q = [], zero
+    for o in range(nA):
+        zeta.append((raw[:, o] - y[:, o]) / sd[o])
+        Q = torch.where(lv[o], Q + zeta[o] * zeta[o], Q)
+    logp = (-0.5 * Q) - Cn
+    Dl = logp - old_logp.reshape(n)
+    nan = Dl != Dl
+    Dz = torch.where(nan, zero, Dl)
+    down = Dz <= 0
+    m = torch.where(down, Dz, -Dz)
+    E = policy_exp(torch.where(m < EXP_MIN, torch.full_like(m, EXP_MIN), m))
+    rho = torch.where(nan, torch.full_like(E, float("nan")), torch.where(down, E, 1.0 / E))
+    A = advantages.reshape(n)
+    hi, lo = 1.0 + clip, 1.0 - clip
+    active = ~(((A > 0) & (rho > hi)) | ((A < 0) & (rho < lo)))
+    c = torch.where(anyl & active, -(A * rho), zero)
+    pl = torch.where(anyl, torch.where(active, c, -(A * torch.where(A > 0, zero + hi, zero + lo))), zero)
+    kl = torch.where(anyl, (rho - 1.0) - Dl, zero)
+    dy = torch.stack([torch.where(lv[o], c * (zeta[o] / sd[o]), zero) for o in range(nA)], dim=1)
+    dls = torch.stack([torch.where(lv[o], (c * (zeta[o] * zeta[o] - 1.0)) - ent_coef, zero) if o < nA else zero
+                       for o in range(MAX_CONTROLS)], dim=1)
+    dv = vl = None
+    if critic is not None:
+        cw, cb = critic.w.to(dev), critic.b.to(dev)
+        V = MLPPolicy._layer(cw.unsqueeze(1), cb.unsqueeze(1), None, h)[:, 0]
+        diff = V - returns.reshape(n)
+        dv, vl = vf_coef * diff, 0.5 * (diff * diff)
+    cols = []
+    if me.n_hidden:
+        q = torch.zeros_like(h)
+        for o in range(nA):
+            q = q + me.W2[0][o].unsqueeze(0) * dy[:, o:o + 1]
+        if critic is not None:
+            q = q + cw[0].unsqueeze(0) * dv.unsqueeze(1)
+        dh = torch.where(h > 0, q, torch.zeros_like(q))
+        cols += [(dh.unsqueeze(2) * x.unsqueeze(1)).reshape(n, -1), dh]
+    cols += [(dy.unsqueeze(2) * h.unsqueeze(1)).reshape(n, -1), dy]
+    if critic is not None:
+        cols += [dv.unsqueeze(1) * h, dv.unsqueeze(1)]
+    terms = torch.cat(cols + [dls], dim=1)
+    st = torch.stack([pl, vl if vl is not None else zero, Hc, (anyl & ~active).to(torch.float64), kl], dim=1)
+    if mask is not None:
+        keep = mask.reshape(n) != 0
+        terms, st = terms[keep], st[keep]
+    M = terms.shape[0]
+    inv = 1.0 / M if M else 0.0
+    res = _ppo_result(inv * terms.sum(dim=0), inv * st.sum(dim=0), me, critic, log_sigma=True)
+    if ratio:
+        res["ratio"] = rho.reshape(K, N)
+    if per_sample:
+        res["terms"], res["stat_terms"] = terms, st
+    return res
+
+
+def ppo_grad_gaussian(policy, critic, rows, raw_actions, old_logp, advantages, returns=None, sampling=None, clip=0.2, vf_coef=0.5,
+                      ent_coef=0.0, mask=None, ratio=False, out=None):
+    """``ppo_grad`` for the Gaussian head: the gradient of the PPO-clip loss (``clip=float("inf")``: A2C) of a continuous ``MLPPolicy``,
+    the ``ValueHead`` on its trunk and ``log sigma`` over the ``[K, N]`` samples of a collection, on the device
+    (``mgx_policy_grad_gaussian``: the kernels of ``ppo_grad`` with the Gaussian head) -- ``ppo_grad_gaussian_host``'s values, exactly
+    for one live sample and within the any-order summation bound for many, identical from run to run.
+
+    ``rows`` ``[K, N, n_in]`` float64 or float32 (``decision_rows``), ``raw_actions`` float64 ``[K, N, n_out]`` and ``old_logp`` float64
+    ``[K, N]`` (``out["raw_actions"]``, ``out["logp"]`` of ``step_k_policy``), ``advantages`` / ``returns`` as ``gae`` made them,
+    ``sampling`` the launch's ``GaussianSampling`` (sigma and scale are read).  Returns what ``ppo_grad`` returns plus ``"log_sigma"``
+    ``[4]``, the gradient with respect to ``log sigma[o]`` (0.0 past ``n_out`` and where sigma is 0), with ``stats`` ``[5]``: policy
+    loss, value loss, entropy, clipped fraction, ``kl``.  Who learns sigma keeps a ``log_sigma`` tensor, steps it with this gradient
+    and builds the next ``GaussianSampling`` from ``log_sigma.exp().tolist()``.  With the parameters that collected the data ``ratio``
+    is 1.0 up to the rounding of ``raw = y + s * z`` (the bound: include/mgx.h), not exactly."""
+    K, N, clip, vf_coef, ent_coef = _ppo_gaussian_args(policy, critic, rows, raw_actions, old_logp, advantages, returns, sampling, clip,
+                                                       vf_coef, ent_coef, mask)
+    dev = rows.device
+    if dev.type != "cuda":
+        raise ValueError(f"ppo_grad_gaussian runs on the GPU (mgx_policy_grad_gaussian); the tensors lie on {dev} -- "
+                         "ppo_grad_gaussian_host states the same rule anywhere")
+    for name, t in (("rows", rows), ("raw_actions", raw_actions), ("old_logp", old_logp), ("advantages", advantages), ("returns", returns),
+                    ("mask", mask)):
+        if t is not None and not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
+    n_mid = policy.n_hidden or policy.n_in
+    shapes = {"W1": (policy.n_hidden, policy.n_in) if policy.n_hidden else None, "b1": (policy.n_hidden,) if policy.n_hidden else None,
+              "W2": (policy.n_out, n_mid), "b2": (policy.n_out,), "w": (n_mid,) if critic is not None else None,
+              "b": (1,) if critic is not None else None, "log_sigma": (MAX_CONTROLS,), "stats": (5,), "ratio": (K, N) if ratio else None}
+    res = _ppo_outputs(shapes, out, dev, mask is not None)
+    lib = _lib.lib()
+    ptr = lambda t: None if t is None else t.data_ptr()     # noqa: E731
+    with torch.cuda.device(dev):
+        pol, keep_p = policy.c_struct(dev, N)
+        smp, keep_s = sampling.c_struct(dev, N)
+        cr, keep_c = critic.c_struct(dev, N) if critic is not None else (None, None)
+        need = C.c_int64()
+        _lib.check(lib.mgx_policy_grad_workspace(N, K, C.byref(pol), C.byref(need)))
+        ws = torch.empty((need.value + 7) // 8, dtype=torch.float64, device=dev)
+        m8 = mask.view(torch.uint8) if mask is not None and mask.dtype == torch.bool else mask
+        pg = _lib.PolicyGradGaussian()
+        pg.struct_size = C.sizeof(_lib.PolicyGradGaussian)
+        pg.x_f32 = int(rows.dtype == torch.float32)
+        pg.x, pg.raw_action, pg.old_logp, pg.advantage = ptr(rows), ptr(raw_actions), ptr(old_logp), ptr(advantages)
+        pg.returns, pg.mask = ptr(returns), ptr(m8)
+        pg.clip_eps, pg.vf_coef, pg.ent_coef = clip, vf_coef, ent_coef
+        pg.g_w1, pg.g_b1, pg.g_w2, pg.g_b2 = ptr(res["W1"]), ptr(res["b1"]), ptr(res["W2"]), ptr(res["b2"])
+        pg.g_cw, pg.g_cb, pg.g_log_sigma = ptr(res["w"]), ptr(res["b"]), ptr(res["log_sigma"])
+        pg.stats, pg.ratio_out = ptr(res["stats"]), ptr(res.get("ratio"))
+        pg.workspace, pg.workspace_bytes = ws.data_ptr(), ws.numel() * 8
+        _lib.check(lib.mgx_policy_grad_gaussian(N, K, C.byref(pol), C.byref(cr) if cr is not None else None, C.byref(smp), C.byref(pg),
+                                                torch.cuda.current_stream(dev).cuda_stream))
     return res

@@ -113,7 +113,7 @@ def main():
                   f"    (t)/(d) = {mt / md:.2f}   {moved / 1e6:.1f} MB moved per call, {tbs:.3f} TB/s = "
                   f"{tbs / 8.0:.3f} of the 8 TB/s peak"]
         for name in sorted(usage):
-            if f"policy_grad_kernel<{n_in}, true>" in name or "policy_grad_finish_kernel" in name:
+            if f"policy_grad_kernel<{n_in}, true, 0>" in name or "policy_grad_finish_kernel" in name:
                 lines.append(f"#   {name}: {json.dumps(usage[name], sort_keys=True)}")
         summary.append(dict(layout=layout, n_in=n_in, n_out=n_out, d=round(md, 1), t=round(mt, 1), tb_s=round(tbs, 4),
                             diff=diff))
