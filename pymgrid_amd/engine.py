@@ -34,6 +34,17 @@ CRITIC_NEEDS_GAUSSIAN = ("critic= goes with sampling=: the critic sits beside th
                          "GaussianSampling(seed, 0.0) is the greedy head")
 
 
+def _value_names(critic, values):
+    """``values=`` of a critic launch -- True, or the names wanted -- as the names of ``VALUE_OUTPUTS`` it asks for; refused without
+    a ``critic``.  Called before anything touches the handle; ``StepEngine._values_out`` then makes the buffers."""
+    if values and critic is None:
+        raise ValueError("values= goes with critic=: a ValueHead on the policy's trunk")
+    names = VALUE_OUTPUTS if values is True else tuple(values or ())
+    if set(names) - set(VALUE_OUTPUTS):
+        raise ValueError(f"values names {sorted(set(names) - set(VALUE_OUTPUTS))}: True or any of {VALUE_OUTPUTS}")
+    return names
+
+
 class StepEngine:
     def __init__(self, batch, obs_dtype=torch.float64, action_dtype=torch.float64):
         if batch.device.type != "cuda":
@@ -945,6 +956,16 @@ class StepEngine:
         res[name] = t
         return t
 
+    def _values_out(self, res, out, K, names):
+        """The three buffers of a critic launch in the order of ``VALUE_OUTPUTS`` (None where ``names``, of ``_value_names``, does not
+        ask for one): from ``out`` or allocated, a fresh ``final_values`` zero-filled."""
+        fresh = "final_values" in names and out.get("final_values") is None
+        vals = tuple(self._actions_out(res, out, name in names, (self.N,) if name == "last_value" else (K, self.N), torch.float64, name=name)
+                     for name in VALUE_OUTPUTS)
+        if fresh:
+            res["final_values"].zero_()          # (only the entries of the grids a step restarts are written)
+        return vals
+
     def rollout_policy_episodes(self, policy, table, K, reward=True, done=False, soc_trace=False, status_trace=False, actions=False,
                                 stats=None, out=None, obs=False, final_obs=False, exploration=None, sampling=None, probs=False,
                                 critic=None, values=False):
@@ -969,21 +990,13 @@ class StepEngine:
             raise ValueError("probs=True goes with sampling=: the other heads take their id with certainty or by a uniform draw")
         if critic is not None and sampling is None:
             raise ValueError(CRITIC_NEEDS_SAMPLING)
-        if values and critic is None:
-            raise ValueError("values= goes with critic=: a ValueHead on the policy's trunk")
-        names = VALUE_OUTPUTS if values is True else tuple(values or ())
-        if set(names) - set(VALUE_OUTPUTS):
-            raise ValueError(f"values names {sorted(set(names) - set(VALUE_OUTPUTS))}: True or any of {VALUE_OUTPUTS}")
+        names = _value_names(critic, values)
         st = self._episode_stats(stats)
         tptr, n_lists = self._table_ptr(table)
         res, r, d, s, g, _ = self._fused_outputs(out, K, reward, done, soc_trace, status_trace)
         taken = self._actions_out(res, out, actions, (K, self.N), torch.uint8)
         pr = self._actions_out(res, out, probs, (K, self.N), torch.float64, name="probs")
-        fresh = "final_values" in names and out.get("final_values") is None
-        vals = tuple(self._actions_out(res, out, name in names, (self.N,) if name == "last_value" else (K, self.N), torch.float64, name=name)
-                     for name in VALUE_OUTPUTS)
-        if fresh:
-            res["final_values"].zero_()          # (only the entries of the grids a step restarts are written)
+        vals = self._values_out(res, out, K, names)
         return self._launch_policy_episodes("mgx_rollout_policy_episodes", policy, exploration, (tptr, n_lists, K), K, res, (r, d, s, g),
                                             taken, st, out, obs, final_obs, sampling=sampling, probs=pr, critic=critic, values=vals)
 
@@ -1037,11 +1050,7 @@ class StepEngine:
             raise ValueError("exploration= and sampling= exclude each other: the Gaussian head draws from the policy's own distribution")
         if not isinstance(sampling, GaussianSampling):
             raise ValueError("sampling= of the continuous head is a GaussianSampling (softmax sampling is the discrete head's)")
-        if values and critic is None:
-            raise ValueError("values= goes with critic=: a ValueHead on the policy's trunk")
-        names = VALUE_OUTPUTS if values is True else tuple(values or ())
-        if set(names) - set(VALUE_OUTPUTS):
-            raise ValueError(f"values names {sorted(set(names) - set(VALUE_OUTPUTS))}: True or any of {VALUE_OUTPUTS}")
+        names = _value_names(critic, values)
         if critic is not None:
             critic.check(policy)
         st = self._episode_stats(stats)
@@ -1049,11 +1058,7 @@ class StepEngine:
         taken = self._actions_out(res, out, actions, (K, self.N, self.action_dim), torch.float64)
         raw = self._actions_out(res, out, raw_actions, (K, self.N, self.action_dim), torch.float64, name="raw_actions")
         lp = self._actions_out(res, out, logp, (K, self.N), torch.float64, name="logp")
-        fresh = "final_values" in names and out.get("final_values") is None
-        vals = tuple(self._actions_out(res, out, name in names, (self.N,) if name == "last_value" else (K, self.N), torch.float64, name=name)
-                     for name in VALUE_OUTPUTS)
-        if fresh:
-            res["final_values"].zero_()          # (only the entries of the grids a step restarts are written)
+        vals = self._values_out(res, out, K, names)
         pst, keep = policy.c_struct(self.device, self.N)
         gst, keep_g = sampling.c_struct(self.device, self.N)
         cst, keep_c = critic.c_struct(self.device, self.N) if critic is not None else (None, None)

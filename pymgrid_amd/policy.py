@@ -69,33 +69,30 @@ def explore_normal(seed, grid, counter, column, device=None):
     return (S.to(torch.float64) - 6138.0) * (1.0 / 1024.0)
 
 
-class Exploration:
-    """What the exploring closed-loop launches add to an ``MLPPolicy`` (``mgx_exploration``, include/mgx.h): epsilon-greedy on the
-    discrete head, additive noise ``sigma[o] * z`` on control ``o`` of the continuous head before its clip, both drawn from a
-    counter-based generator keyed by ``seed`` -- a draw depends on (seed, grid, step counter, number) alone.  ``sigma``: one value
-    for every action column or up to four, one per column; ``scale`` (float64 ``[N]``, numpy or torch): multiplies ``epsilon`` and
-    every ``sigma`` of grid i (an exploration ladder; 0 switches a grid back to the greedy head).  Validated as the C calls do."""
+def _seed(seed):
+    """``seed`` as the 64-bit unsigned key of a counter-based draw."""
+    if not 0 <= int(seed) < 2 ** 64:
+        raise ValueError(f"seed = {seed}: a 64-bit unsigned key")
+    return int(seed)
 
-    def __init__(self, seed, epsilon=0.0, sigma=None, scale=None):
-        self.seed = int(seed)
-        if not 0 <= self.seed < 2 ** 64:
-            raise ValueError(f"seed = {seed}: a 64-bit unsigned key")
-        self.epsilon = float(epsilon)
-        if not 0.0 <= self.epsilon <= 1.0:
-            raise ValueError(f"epsilon = {epsilon}: a probability in [0, 1]")
-        sg = [0.0] if sigma is None else [float(v) for v in np.atleast_1d(np.asarray(sigma, dtype=np.float64))]
-        if len(sg) > MAX_CONTROLS:
-            raise ValueError(f"sigma holds {len(sg)} values: a layout has at most {MAX_CONTROLS} action columns")
-        self._shared_sigma = sigma is None or np.ndim(sigma) == 0
-        if not all(v >= 0.0 for v in sg):
-            raise ValueError(f"sigma = {sigma}: standard deviations are >= 0")
-        self.sigma = tuple(sg * MAX_CONTROLS if self._shared_sigma else sg + [0.0] * (MAX_CONTROLS - len(sg)))
-        self.scale = None
-        if scale is not None:
-            t = scale if torch.is_tensor(scale) else torch.as_tensor(np.asarray(scale))
-            if t.dtype != torch.float64 or t.dim() != 1:
-                raise ValueError(f"scale must be a float64 vector [N], not {t.dtype} {tuple(t.shape)}")
-            self.scale = t.contiguous()
+
+def _scale(scale):
+    """``scale`` (None, or float64 ``[N]``, numpy or torch) as a contiguous tensor."""
+    if scale is None:
+        return None
+    t = scale if torch.is_tensor(scale) else torch.as_tensor(np.asarray(scale))
+    if t.dtype != torch.float64 or t.dim() != 1:
+        raise ValueError(f"scale must be a float64 vector [N], not {t.dtype} {tuple(t.shape)}")
+    return t.contiguous()
+
+
+def _sigma_columns(sg, shared):
+    """The four ``sigma`` columns of the C structs: one value for every column (``shared``), or ``sg`` with 0.0 behind it."""
+    return tuple(sg * MAX_CONTROLS if shared else sg + [0.0] * (MAX_CONTROLS - len(sg)))
+
+
+class _Draws:
+    """What ``Exploration``, ``Sampling`` and ``GaussianSampling`` share: the per-grid ``scale`` and the head of their C struct."""
 
     def scale_on(self, device, n):
         """``scale`` on ``device`` (None: there is none), checked against the ``n`` grids it names."""
@@ -105,15 +102,41 @@ class Exploration:
             raise ValueError(f"scale names {self.scale.shape[0]} grids, not {n}")
         return self.scale.to(device)
 
-    def c_struct(self, device, n_grids):
-        """``(mgx_exploration, keep-alive)`` with ``scale`` on ``device``."""
-        st = _lib.Exploration()
-        st.struct_size = C.sizeof(_lib.Exploration)
-        st.seed, st.epsilon = self.seed, self.epsilon
-        for o, v in enumerate(self.sigma):
+    def _c_struct(self, cls, device, n_grids):
+        """``(cls, keep-alive)`` with its size, ``seed``, the ``sigma`` columns if it has any and ``scale`` on ``device``."""
+        st = cls()
+        st.struct_size, st.seed = C.sizeof(cls), self.seed
+        for o, v in enumerate(getattr(self, "sigma", ())):
             st.sigma[o] = v
         sc = self.scale_on(device, n_grids)
         st.scale = None if sc is None else sc.data_ptr()
+        return st, sc
+
+
+class Exploration(_Draws):
+    """What the exploring closed-loop launches add to an ``MLPPolicy`` (``mgx_exploration``, include/mgx.h): epsilon-greedy on the
+    discrete head, additive noise ``sigma[o] * z`` on control ``o`` of the continuous head before its clip, both drawn from a
+    counter-based generator keyed by ``seed`` -- a draw depends on (seed, grid, step counter, number) alone.  ``sigma``: one value
+    for every action column or up to four, one per column; ``scale`` (float64 ``[N]``, numpy or torch): multiplies ``epsilon`` and
+    every ``sigma`` of grid i (an exploration ladder; 0 switches a grid back to the greedy head).  Validated as the C calls do."""
+
+    def __init__(self, seed, epsilon=0.0, sigma=None, scale=None):
+        self.seed = _seed(seed)
+        self.epsilon = float(epsilon)
+        if not 0.0 <= self.epsilon <= 1.0:
+            raise ValueError(f"epsilon = {epsilon}: a probability in [0, 1]")
+        sg = [0.0] if sigma is None else [float(v) for v in np.atleast_1d(np.asarray(sigma, dtype=np.float64))]
+        if len(sg) > MAX_CONTROLS:
+            raise ValueError(f"sigma holds {len(sg)} values: a layout has at most {MAX_CONTROLS} action columns")
+        if not all(v >= 0.0 for v in sg):
+            raise ValueError(f"sigma = {sigma}: standard deviations are >= 0")
+        self.sigma = _sigma_columns(sg, sigma is None or np.ndim(sigma) == 0)
+        self.scale = _scale(scale)
+
+    def c_struct(self, device, n_grids):
+        """``(mgx_exploration, keep-alive)`` with ``scale`` on ``device``."""
+        st, sc = self._c_struct(_lib.Exploration, device, n_grids)
+        st.epsilon = self.epsilon
         return st, sc
 
 
@@ -134,35 +157,23 @@ def policy_exp(d):
     return p * ((k.to(torch.int64) + 1023) << 52).view(torch.float64)
 
 
-class Sampling:
+class Sampling(_Draws):
     """What the sampling closed-loop launch adds to a discrete ``MLPPolicy`` (``mgx_sampling``, include/mgx.h): the id of every step is
     drawn from ``softmax(y / temperature)`` by a counter-based draw keyed by ``seed``, and the launch returns the probability of the id
     taken.  ``scale`` (float64 ``[N]``, numpy or torch) multiplies the temperature of grid i (a ladder; 0 switches a grid back to the
     greedy head, as ``temperature=0`` does for all).  Validated as the C call does."""
 
     def __init__(self, seed, temperature=1.0, scale=None):
-        self.seed = int(seed)
-        if not 0 <= self.seed < 2 ** 64:
-            raise ValueError(f"seed = {seed}: a 64-bit unsigned key")
+        self.seed = _seed(seed)
         self.temperature = float(temperature)
         if not 0.0 <= self.temperature < float("inf"):
             raise ValueError(f"temperature = {temperature}: finite and >= 0")
-        self.scale = None
-        if scale is not None:
-            t = scale if torch.is_tensor(scale) else torch.as_tensor(np.asarray(scale))
-            if t.dtype != torch.float64 or t.dim() != 1:
-                raise ValueError(f"scale must be a float64 vector [N], not {t.dtype} {tuple(t.shape)}")
-            self.scale = t.contiguous()
-
-    scale_on = Exploration.scale_on
+        self.scale = _scale(scale)
 
     def c_struct(self, device, n_grids):
         """``(mgx_sampling, keep-alive)`` with ``scale`` on ``device``."""
-        st = _lib.Sampling()
-        st.struct_size = C.sizeof(_lib.Sampling)
-        st.seed, st.temperature = self.seed, self.temperature
-        sc = self.scale_on(device, n_grids)
-        st.scale = None if sc is None else sc.data_ptr()
+        st, sc = self._c_struct(_lib.Sampling, device, n_grids)
+        st.temperature = self.temperature
         return st, sc
 
 
@@ -380,7 +391,7 @@ def cem_refit_host(ret, steps, mean, sigma, key, n_elite, alpha=1.0, sigma_min=0
             "best_plan": xs[0].to(dtype).contiguous()}
 
 
-class GaussianSampling:
+class GaussianSampling(_Draws):
     """What the Gaussian closed-loop launch adds to a continuous ``MLPPolicy`` (``mgx_gaussian``, include/mgx.h): control ``o`` is
     drawn from ``N(y[o], s[o]**2)``, ``s[o] = sigma[o] * scale[i]``, by a counter-based Box-Muller draw keyed by ``seed``, clipped
     as the greedy head clips; the launch returns the pre-clip action and its exact log-density.  ``sigma``: one value for every
@@ -389,35 +400,18 @@ class GaussianSampling:
     the C call does: a sigma is 0 or a positive NORMAL float64 (the rule's logarithm reads exponent and mantissa)."""
 
     def __init__(self, seed, sigma, scale=None):
-        self.seed = int(seed)
-        if not 0 <= self.seed < 2 ** 64:
-            raise ValueError(f"seed = {seed}: a 64-bit unsigned key")
+        self.seed = _seed(seed)
         sg = [float(v) for v in np.atleast_1d(np.asarray(sigma, dtype=np.float64))]
         if not 1 <= len(sg) <= MAX_CONTROLS:
             raise ValueError(f"sigma holds {len(sg)} values: one, or one per action column (at most {MAX_CONTROLS})")
         if not all(v == 0.0 or np.finfo(np.float64).tiny <= v < float("inf") for v in sg):
             raise ValueError(f"sigma = {sigma}: standard deviations are 0 or positive, finite and not subnormal")
-        shared = np.ndim(sigma) == 0
-        self.sigma = tuple(sg * MAX_CONTROLS if shared else sg + [0.0] * (MAX_CONTROLS - len(sg)))
-        self.scale = None
-        if scale is not None:
-            t = scale if torch.is_tensor(scale) else torch.as_tensor(np.asarray(scale))
-            if t.dtype != torch.float64 or t.dim() != 1:
-                raise ValueError(f"scale must be a float64 vector [N], not {t.dtype} {tuple(t.shape)}")
-            self.scale = t.contiguous()
-
-    scale_on = Exploration.scale_on
+        self.sigma = _sigma_columns(sg, np.ndim(sigma) == 0)
+        self.scale = _scale(scale)
 
     def c_struct(self, device, n_grids):
         """``(mgx_gaussian, keep-alive)`` with ``scale`` on ``device``."""
-        st = _lib.Gaussian()
-        st.struct_size = C.sizeof(_lib.Gaussian)
-        st.seed = self.seed
-        for o, v in enumerate(self.sigma):
-            st.sigma[o] = v
-        sc = self.scale_on(device, n_grids)
-        st.scale = None if sc is None else sc.data_ptr()
-        return st, sc
+        return self._c_struct(_lib.Gaussian, device, n_grids)
 
 
 class MLPPolicy:
@@ -519,8 +513,17 @@ class MLPPolicy:
             acc = acc + Wn[:, :, j] * v[:, j:j + 1]
         return acc
 
-    def outputs(self, obs):
-        """``y`` [N, n_out] for observation rows ``obs`` [N, n_in] (float32 rows are widened to float64, not re-rounded)."""
+    def _trunk(self, x, idx):
+        """``(h, y)`` for float64 rows ``x`` [n, n_in] on the parameters' device: the hidden vector after its ReLU (``x`` itself for a
+        linear policy) and the outputs [n, n_out]; ``idx``: what ``_sets`` gave."""
+        h = x
+        if self.n_hidden:
+            hp = self._layer(self.W1, self.b1, idx, x)
+            h = torch.where(hp > 0, hp, torch.zeros_like(hp))
+        return h, self._layer(self.W2, self.b2, idx, h)
+
+    def _forward(self, obs):
+        """``(h, y, idx)`` of ``_trunk`` for observation rows ``obs`` [N, n_in], row n the row of grid n."""
         if not torch.is_tensor(obs):
             obs = torch.as_tensor(np.asarray(obs))
         if obs.dim() != 2 or obs.shape[1] != self.n_in or obs.dtype not in (torch.float32, torch.float64):
@@ -528,10 +531,11 @@ class MLPPolicy:
         me = self.to(obs.device)
         x = obs.to(torch.float64)
         idx = me._sets(x.shape[0], x.device)
-        if me.n_hidden:
-            h = self._layer(me.W1, me.b1, idx, x)
-            x = torch.where(h > 0, h, torch.zeros_like(h))
-        return self._layer(me.W2, me.b2, idx, x)
+        return me._trunk(x, idx) + (idx,)
+
+    def outputs(self, obs):
+        """``y`` [N, n_out] for observation rows ``obs`` [N, n_in] (float32 rows are widened to float64, not re-rounded)."""
+        return self._forward(obs)[1]
 
     def act(self, obs, exploration=None, counter=None, return_prob=False, return_logp=False, return_raw=False):
         """The actions for observation rows ``obs`` [N, n_in]: priority-list ids (int32 [N]) or normalised controls (float64
@@ -578,7 +582,7 @@ class MLPPolicy:
                     s = exploration.sigma[o] if scale is None else exploration.sigma[o] * scale
                     cols.append(y[:, o] + s * explore_normal(exploration.seed, grid, int(counter), o))
                 y = torch.stack(cols, dim=1)
-            return torch.where(~(y > 0), torch.zeros_like(y), torch.where(y > 1, torch.ones_like(y), y))
+            return policy_clip(y)
         ids, _ = self._greedy(y)
         if exploration is not None:
             r = philox_words(exploration.seed, grid, int(counter), EXPLORE_TAG)
@@ -603,23 +607,32 @@ class MLPPolicy:
         """``(e, S, g, live)`` of the sampling head (``mgx_sampling``) on the outputs ``y`` [N, n_out]: the unnormalised weights
         ``e`` [N, n_out], their sum in index order, the greedy ids and which grids sample at all (``tau > 0``; the others' weights
         are not used)."""
+        e, _, S, g, live, _ = self._softmax(y, sampling)
+        return torch.stack(e, dim=1), S, g, live
+
+    def _softmax(self, y, sampling, K=1):
+        """What lies between the outputs ``y`` [K * N, n_out] (K rows per grid, grid-minor) and the probabilities of the sampling head
+        (``mgx_sampling``): ``(e, d, S, g, live, beta)`` -- the columns ``e[o]`` of the unnormalised weights and ``d[o]`` of their
+        exponents (1.0 and 0.0 on the greedy id), the sum of the weights in index order, the greedy ids, which rows sample at all
+        (``tau > 0``) and ``1 / tau`` of every row (1.0 where it does not sample: nothing of such a row is used)."""
         n, dev = y.shape[0], y.device
         g, best = self._greedy(y)
-        scale = sampling.scale_on(dev, n)
+        scale = sampling.scale_on(dev, n // K)
         tau = torch.full((n,), sampling.temperature, dtype=torch.float64, device=dev)
         if scale is not None:
-            tau = tau * scale
+            tau = tau * scale.repeat(K)
         live = tau > 0
-        beta = 1.0 / torch.where(live, tau, torch.ones_like(tau))
-        cols = []
-        S = torch.zeros(n, dtype=torch.float64, device=dev)
+        zero, one = torch.zeros_like(tau), torch.ones_like(tau)
+        beta = 1.0 / torch.where(live, tau, one)
+        e, d, S = [], [], zero
         for o in range(self.n_out):
-            d = (y[:, o] - best) * beta
-            ok = d >= EXP_MIN                                          # (False for a NaN)
-            e = torch.where(ok, policy_exp(torch.where(ok, d, torch.full_like(d, EXP_MIN))), torch.zeros_like(d))
-            cols.append(torch.where(g == o, torch.ones_like(e), e))
-            S = S + cols[-1]
-        return torch.stack(cols, dim=1), S, g, live
+            dd = (y[:, o] - best) * beta
+            ok = dd >= EXP_MIN                                         # (False for a NaN)
+            eo = torch.where(ok, policy_exp(torch.where(ok, dd, torch.full_like(dd, EXP_MIN))), zero)
+            e.append(torch.where(g == o, one, eo))
+            d.append(torch.where(g == o, zero, dd))
+            S = S + e[-1]
+        return e, d, S, g, live, beta
 
     def _sample(self, y, sampling, counter):
         """``(ids, prob)`` by the rule of ``mgx_sampling``: inverse CDF on the unnormalised weights with draw number 1."""
@@ -643,22 +656,32 @@ class MLPPolicy:
         columns (``s > 0``), its clip, and the log-density of ``raw`` over the live columns."""
         n, dev = y.shape[0], y.device
         grid = torch.arange(n, dtype=torch.int64, device=dev)
-        scale = gs.scale_on(dev, n)
-        zero = torch.zeros(n, dtype=torch.float64, device=dev)
-        s = [zero + gs.sigma[o] if scale is None else gs.sigma[o] * scale for o in range(self.n_out)]
-        live = [v > 0 for v in s]
-        Cn = zero
-        for o in range(self.n_out):
-            Cn = torch.where(live[o], Cn + (policy_log(torch.where(live[o], s[o], torch.ones_like(zero))) + HALF_LOG_2PI), Cn)
-        Q, cols = zero, []
+        s, live, _, _, Cn = self._gaussian_consts(gs, n, dev)
+        Q, cols = torch.zeros_like(Cn), []
         for p in range((self.n_out + 1) // 2):
             for o, z in zip((2 * p, 2 * p + 1), gaussian_pair(gs.seed, grid, counter, p)):
                 if o < self.n_out:
                     cols.append(torch.where(live[o], y[:, o] + s[o] * z, y[:, o]))
                     Q = torch.where(live[o], Q + z * z, Q)
         raw = torch.stack(cols, dim=1) if cols else y
-        u = torch.where(~(raw > 0), torch.zeros_like(raw), torch.where(raw > 1, torch.ones_like(raw), raw))
-        return u, (-0.5 * Q) - Cn, raw
+        return policy_clip(raw), (-0.5 * Q) - Cn, raw
+
+    def _gaussian_consts(self, gs, n, dev, K=1):
+        """What the Gaussian head (``mgx_gaussian``) knows of a row before it sees ``y``, for ``n = K * N`` rows (K per grid,
+        grid-minor): ``(s, live, sd, L, Cn)`` -- per action column ``s[o] = sigma[o] * scale``, whether it is live (``s > 0``), ``sd[o]``
+        (``s[o]``, 1.0 on a dead column) and ``L[o] = policy_log(sd[o])``; ``Cn`` the normalising constant over the live columns."""
+        scale = gs.scale_on(dev, n // K)
+        if scale is not None:
+            scale = scale.repeat(K)
+        zero = torch.zeros(n, dtype=torch.float64, device=dev)
+        s = [zero + gs.sigma[o] if scale is None else gs.sigma[o] * scale for o in range(self.n_out)]
+        live = [v > 0 for v in s]
+        sd = [torch.where(live[o], s[o], torch.ones_like(zero)) for o in range(self.n_out)]
+        L = [policy_log(v) for v in sd]
+        Cn = zero
+        for o in range(self.n_out):
+            Cn = torch.where(live[o], Cn + (L[o] + HALF_LOG_2PI), Cn)
+        return s, live, sd, L, Cn
 
     def c_struct(self, device, n_grids):
         """``(mgx_policy, keep-alive)`` with the parameters on ``device``."""
@@ -724,17 +747,12 @@ class ValueHead:
         """``V`` (float64 [N]) for observation rows ``obs`` [N, n_in] (float32 rows are widened): the host statement of the rule,
         what the critic launch writes bit for bit -- row n of ``obs`` is grid n."""
         self.check(policy)
-        if not torch.is_tensor(obs):
-            obs = torch.as_tensor(np.asarray(obs))
-        if obs.dim() != 2 or obs.shape[1] != policy.n_in or obs.dtype not in (torch.float32, torch.float64):
-            raise ValueError(f"obs must be float32 or float64 rows [N, {policy.n_in}], not {obs.dtype} {tuple(obs.shape)}")
-        me = policy.to(obs.device)
-        x = obs.to(torch.float64)
-        idx = me._sets(x.shape[0], x.device)
-        if me.n_hidden:
-            h = MLPPolicy._layer(me.W1, me.b1, idx, x)
-            x = torch.where(h > 0, h, torch.zeros_like(h))
-        return MLPPolicy._layer(self.w.to(x.device).unsqueeze(1), self.b.to(x.device).unsqueeze(1), idx, x)[:, 0]
+        h, _, idx = policy._forward(obs)
+        return self._on(h, idx)
+
+    def _on(self, h, idx):
+        """``V`` [n] on the trunk's ``h`` [n, n_mid] (``MLPPolicy._trunk``), ``idx`` the parameter set of every row or None."""
+        return MLPPolicy._layer(self.w.to(h.device).unsqueeze(1), self.b.to(h.device).unsqueeze(1), idx, h)[:, 0]
 
     def c_struct(self, device, n_grids):
         """``(mgx_critic, keep-alive)`` with the parameters on ``device``."""
@@ -836,17 +854,19 @@ PPO_GRAD_NAMES = ("W1", "b1", "W2", "b2", "w", "b")      # the gradients in the 
 PPO_GRAD_NAMES_GAUSSIAN = PPO_GRAD_NAMES + ("log_sigma",)  # ... of the Gaussian head: ``log_sigma`` [4] behind them
 
 
-def _ppo_checks(policy, head, other, critic, rows, per_sample, returns, sampling, sampling_cls, clip, vf_coef, ent_coef, mask):
-    """The checks the gradients of the two heads share (those of ``mgx_policy_grad`` / ``mgx_policy_grad_gaussian``): ``(K, N, clip,
-    vf_coef, ent_coef)``.  ``per_sample``: ``(name, tensor, dtypes, trailing shape)`` of the head's own ``[K, N, ...]`` inputs."""
-    if not isinstance(policy, MLPPolicy) or policy.head != head:
-        raise ValueError(f"this gradient is offered for an MLPPolicy with the {head} head (the {'continuous' if head == 'discrete' else 'discrete'} "
-                         f"head: {other})")
+def _ppo_checks(head, policy, critic, rows, taken, old, advantages, returns, sampling, clip, vf_coef, ent_coef, mask):
+    """The checks of a gradient of ``head`` (a ``_SoftmaxGrad`` or ``_GaussianGrad``: those of ``mgx_policy_grad`` /
+    ``mgx_policy_grad_gaussian``), on the host and on the device: ``(K, N, clip, vf_coef, ent_coef)``."""
+    if not isinstance(policy, MLPPolicy) or policy.head != head.policy_head:
+        raise ValueError(f"this gradient is offered for an MLPPolicy with the {head.policy_head} head (the "
+                         f"{'continuous' if head.policy_head == 'discrete' else 'discrete'} head: {head.other})")
     if policy.n_policies != 1 or policy.policy_index is not None:
         raise ValueError("the gradient of a population (several parameter sets, a policy_index) is not offered")
-    if not isinstance(sampling, sampling_cls):
-        raise ValueError(f"sampling must be the {sampling_cls.__name__} of the launch that collected the data "
-                         f"({'temperature' if head == 'discrete' else 'sigma'} and scale are read)")
+    if not isinstance(sampling, head.sampling):
+        raise ValueError(f"sampling must be the {head.sampling.__name__} of the launch that collected the data "
+                         f"({head.reads} and scale are read)")
+    per_sample = ((head.taken, taken, (head.taken_dtype,), (policy.n_out,) if head.taken_columns else ()),
+                  (head.old, old, (torch.float64,), ()), ("advantages", advantages, (torch.float64,), ()))
     if critic is not None:
         if not isinstance(critic, ValueHead):
             raise ValueError("critic must be a ValueHead or None")
@@ -866,7 +886,7 @@ def _ppo_checks(policy, head, other, critic, rows, per_sample, returns, sampling
     K, N = int(rows.shape[0]), int(rows.shape[1])
     if K < 1 or N < 1:
         raise ValueError(f"rows {tuple(rows.shape)}: K and N must be positive")
-    for name, t, dts, tail in tuple(per_sample) + (("returns", returns, (torch.float64,), ()), ("mask", mask, (torch.uint8, torch.bool), ())):
+    for name, t, dts, tail in per_sample + (("returns", returns, (torch.float64,), ()), ("mask", mask, (torch.uint8, torch.bool), ())):
         if t is None and name in ("returns", "mask"):
             continue
         if not torch.is_tensor(t) or t.dtype not in dts or tuple(t.shape) != (K, N) + tail:
@@ -874,27 +894,9 @@ def _ppo_checks(policy, head, other, critic, rows, per_sample, returns, sampling
                              f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
         if t.device != rows.device:
             raise ValueError(f"{name} lies on {t.device}, rows on {rows.device}")
-    return K, N, clip, vf_coef, ent_coef
-
-
-def _ppo_args(policy, critic, rows, actions, old_probs, advantages, returns, sampling, clip, vf_coef, ent_coef, mask):
-    """The checks ``ppo_grad`` and ``ppo_grad_host`` share (those of ``mgx_policy_grad``): ``(K, N, clip, vf_coef, ent_coef)``."""
-    per_sample = (("actions", actions, (torch.uint8,), ()), ("old_probs", old_probs, (torch.float64,), ()),
-                  ("advantages", advantages, (torch.float64,), ()))
-    return _ppo_checks(policy, "discrete", "ppo_grad_gaussian", critic, rows, per_sample, returns, sampling, Sampling, clip, vf_coef,
-                       ent_coef, mask)
-
-
-def _ppo_gaussian_args(policy, critic, rows, raw_actions, old_logp, advantages, returns, sampling, clip, vf_coef, ent_coef, mask):
-    """... and ``ppo_grad_gaussian`` and ``ppo_grad_gaussian_host`` (those of ``mgx_policy_grad_gaussian``)."""
-    n_out = policy.n_out if isinstance(policy, MLPPolicy) else 0
-    per_sample = (("raw_actions", raw_actions, (torch.float64,), (n_out,)), ("old_logp", old_logp, (torch.float64,), ()),
-                  ("advantages", advantages, (torch.float64,), ()))
-    res = _ppo_checks(policy, "continuous", "ppo_grad", critic, rows, per_sample, returns, sampling, GaussianSampling, clip, vf_coef,
-                      ent_coef, mask)
-    if policy.n_out < 1:
+    if head.taken_columns and policy.n_out < 1:
         raise ValueError("a policy without an action column has no density")
-    return res
+    return K, N, clip, vf_coef, ent_coef
 
 
 def ppo_grad_flat(grads):
@@ -904,15 +906,17 @@ def ppo_grad_flat(grads):
     return torch.cat([grads[n].reshape(-1) for n in PPO_GRAD_NAMES_GAUSSIAN if grads.get(n) is not None])
 
 
-def _ppo_result(flat, stats, me, critic, log_sigma=False):
+def _ppo_shapes(head, policy, critic):
+    """The shapes of the gradients of ``head`` in the order of ``ppo_grad_flat`` (None: the policy has no such parameter)."""
+    n_mid = policy.n_hidden or policy.n_in
+    return {"W1": (policy.n_hidden, policy.n_in) if policy.n_hidden else None, "b1": (policy.n_hidden,) if policy.n_hidden else None,
+            "W2": (policy.n_out, n_mid), "b2": (policy.n_out,), "w": (n_mid,) if critic is not None else None,
+            "b": (1,) if critic is not None else None, **head.extra}
+
+
+def _ppo_result(flat, stats, shapes):
     """``flat`` (in the order of ``ppo_grad_flat``) cut into the result of a host rule."""
     res, at = {}, 0
-    n_mid = me.n_hidden or me.n_in
-    shapes = {"W1": (me.n_hidden, me.n_in) if me.n_hidden else None, "b1": (me.n_hidden,) if me.n_hidden else None,
-              "W2": (me.n_out, n_mid), "b2": (me.n_out,), "w": (n_mid,) if critic is not None else None,
-              "b": (1,) if critic is not None else None}
-    if log_sigma:
-        shapes["log_sigma"] = (MAX_CONTROLS,)
     for name, shape in shapes.items():
         if shape is None:
             res[name] = None
@@ -921,6 +925,137 @@ def _ppo_result(flat, stats, me, critic, log_sigma=False):
         res[name] = flat[at:at + size].reshape(shape)
         at += size
     res["stats"] = stats
+    return res
+
+
+ENTROPY_CONST = 1.4189385332046727     # (1 + log(2 pi)) / 2: the entropy of a unit normal (include/mgx.h, mgx_policy_grad_gaussian)
+
+
+class _SoftmaxGrad:
+    """What the softmax head of the discrete policy adds to the gradient rule (``PgHead<PG_HEAD_SOFTMAX>`` of the kernel).  ``sample``:
+    from ``y`` [n, n_out], the ids taken and their old probabilities to ``(rho, on, H, further statistics, back)`` -- ``on``: the
+    row samples at all; ``back(c)`` turns the gated ``c`` into ``(dy, further term columns)``.  The forward is ``MLPPolicy._softmax``,
+    the sampling launch's own, so the ratio of an un-updated policy is exactly 1.0."""
+    policy_head, other, sampling, reads = "discrete", "ppo_grad_gaussian", Sampling, "temperature"
+    taken, taken_dtype, taken_columns, old = "actions", torch.uint8, False, "old_probs"
+    extra, n_stats = {}, 4
+    struct, fields, symbol = _lib.PolicyGrad, ("action_id", "old_prob"), "mgx_policy_grad"
+
+    @staticmethod
+    def sample(me, y, actions, old_probs, sampling, K, ent_coef):
+        n = y.shape[0]
+        e, d, S, _, samp, beta = me._softmax(y, sampling, K)
+        zero, one = torch.zeros_like(S), torch.ones_like(S)
+        b = torch.where(samp, beta, zero)
+        a = actions.reshape(n).long()
+        e_a = zero
+        for o in range(me.n_out):
+            e_a = torch.where(a == o, e[o], e_a)
+        lnS = policy_log(S)
+        pi, logpi, Hs = [], [], zero
+        for o in range(me.n_out):
+            pi.append(e[o] / S)
+            logpi.append(d[o] - lnS)
+            Hs = torch.where(e[o] > 0, Hs + pi[o] * logpi[o], Hs)
+        H = -Hs
+
+        def back(c):
+            dy = []
+            for o in range(me.n_out):
+                t = torch.where(e[o] > 0, pi[o] * (logpi[o] + H), zero)
+                v = b * (c * ((a == o).to(torch.float64) - pi[o]) + ent_coef * t)
+                dy.append(torch.where(samp, v, zero))
+            return torch.stack(dy, dim=1), []
+        return torch.where(samp, e_a / S, one) / old_probs.reshape(n), samp, torch.where(samp, H, zero), [], back
+
+
+class _GaussianGrad:
+    """... and the Gaussian head of the continuous one (``PgHead<PG_HEAD_GAUSSIAN>``): from ``y``, the pre-clip actions and their old
+    log-densities; ``on``: a column is live; the further statistic is ``kl``, the further term columns ``dls`` [n, 4] of ``log
+    sigma``.  The constants are ``MLPPolicy._gaussian_consts``, the Gaussian launch's own."""
+    policy_head, other, sampling, reads = "continuous", "ppo_grad", GaussianSampling, "sigma"
+    taken, taken_dtype, taken_columns, old = "raw_actions", torch.float64, True, "old_logp"
+    extra, n_stats = {"log_sigma": (MAX_CONTROLS,)}, 5
+    struct, fields, symbol = _lib.PolicyGradGaussian, ("raw_action", "old_logp"), "mgx_policy_grad_gaussian"
+
+    @staticmethod
+    def sample(me, y, raw_actions, old_logp, sampling, K, ent_coef):
+        n, nA = y.shape[0], me.n_out
+        _, lv, sd, L, Cn = me._gaussian_consts(sampling, n, y.device, K)
+        zero = torch.zeros_like(Cn)
+        Hc, anyl = zero, torch.zeros(n, dtype=torch.bool, device=y.device)
+        for o in range(nA):
+            Hc = torch.where(lv[o], Hc + (L[o] + ENTROPY_CONST), Hc)
+            anyl = anyl | lv[o]
+        raw = raw_actions.reshape(n, nA)
+        zeta, Q = [], zero
+        for o in range(nA):
+            zeta.append((raw[:, o] - y[:, o]) / sd[o])
+            Q = torch.where(lv[o], Q + zeta[o] * zeta[o], Q)
+        logp = (-0.5 * Q) - Cn
+        Dl = logp - old_logp.reshape(n)
+        nan = Dl != Dl
+        Dz = torch.where(nan, zero, Dl)
+        down = Dz <= 0
+        m = torch.where(down, Dz, -Dz)
+        E = policy_exp(torch.where(m < EXP_MIN, torch.full_like(m, EXP_MIN), m))
+        rho = torch.where(nan, torch.full_like(E, float("nan")), torch.where(down, E, 1.0 / E))
+
+        def back(c):
+            dy = torch.stack([torch.where(lv[o], c * (zeta[o] / sd[o]), zero) for o in range(nA)], dim=1)
+            dls = torch.stack([torch.where(lv[o], (c * (zeta[o] * zeta[o] - 1.0)) - ent_coef, zero) if o < nA else zero
+                               for o in range(MAX_CONTROLS)], dim=1)
+            return dy, [dls]
+        return rho, anyl, Hc, [torch.where(anyl, (rho - 1.0) - Dl, zero)], back
+
+
+def _ppo_grad_host(head, policy, critic, rows, taken, old, advantages, returns, sampling, clip, vf_coef, ent_coef, mask, ratio, per_sample):
+    """The host gradient rule, stated once for both heads (``head``: ``_SoftmaxGrad`` or ``_GaussianGrad``): the trunk, the head's
+    ``rho``, the clip gate, the critic's term, the back-propagation into the trunk, the term columns in the order of ``ppo_grad_flat``,
+    the mask and the mean over the live samples."""
+    K, N, clip, vf_coef, ent_coef = _ppo_checks(head, policy, critic, rows, taken, old, advantages, returns, sampling, clip, vf_coef,
+                                                ent_coef, mask)
+    dev = rows.device
+    me = policy.to(dev)
+    n = K * N
+    x = rows.reshape(n, me.n_in).to(torch.float64)
+    h, y = me._trunk(x, None)
+    zero = torch.zeros(n, dtype=torch.float64, device=dev)
+    rho, on, H, more_stats, back = head.sample(me, y, taken, old, sampling, K, ent_coef)
+    A = advantages.reshape(n)
+    hi, lo = 1.0 + clip, 1.0 - clip
+    active = ~(((A > 0) & (rho > hi)) | ((A < 0) & (rho < lo)))
+    c = torch.where(on & active, -(A * rho), zero)
+    pl = torch.where(on, torch.where(active, c, -(A * torch.where(A > 0, zero + hi, zero + lo))), zero)
+    dy, more_cols = back(c)
+    dv = vl = None
+    if critic is not None:
+        diff = critic._on(h, None) - returns.reshape(n)
+        dv, vl = vf_coef * diff, 0.5 * (diff * diff)
+    cols = []
+    if me.n_hidden:
+        q = torch.zeros_like(h)
+        for o in range(me.n_out):
+            q = q + me.W2[0][o].unsqueeze(0) * dy[:, o:o + 1]
+        if critic is not None:
+            q = q + critic.w.to(dev)[0].unsqueeze(0) * dv.unsqueeze(1)
+        dh = torch.where(h > 0, q, torch.zeros_like(q))
+        cols += [(dh.unsqueeze(2) * x.unsqueeze(1)).reshape(n, -1), dh]
+    cols += [(dy.unsqueeze(2) * h.unsqueeze(1)).reshape(n, -1), dy]
+    if critic is not None:
+        cols += [dv.unsqueeze(1) * h, dv.unsqueeze(1)]
+    terms = torch.cat(cols + more_cols, dim=1)
+    st = torch.stack([pl, vl if vl is not None else zero, H, (on & ~active).to(torch.float64)] + more_stats, dim=1)
+    if mask is not None:
+        keep = mask.reshape(n) != 0
+        terms, st = terms[keep], st[keep]
+    M = terms.shape[0]
+    inv = 1.0 / M if M else 0.0
+    res = _ppo_result(inv * terms.sum(dim=0), inv * st.sum(dim=0), _ppo_shapes(head, me, critic))
+    if ratio:
+        res["ratio"] = rho.reshape(K, N)
+    if per_sample:
+        res["terms"], res["stat_terms"] = terms, st
     return res
 
 
@@ -933,89 +1068,20 @@ def ppo_grad_host(policy, critic, rows, actions, old_probs, advantages, returns=
     device's; the sum over the samples is torch's (the device's goes through the matrix cores: the two agree within the any-order
     summation bound, and exactly for one live sample).  ``per_sample=True`` adds ``"terms"`` ``[M, P]``, the unreduced terms of the M
     live samples in the column order of ``ppo_grad_flat``, and ``"stat_terms"`` ``[M, 4]``."""
-    K, N, clip, vf_coef, ent_coef = _ppo_args(policy, critic, rows, actions, old_probs, advantages, returns, sampling, clip, vf_coef,
-                                              ent_coef, mask)
-    dev = rows.device
-    me = policy.to(dev)
-    n = K * N
-    x = rows.reshape(n, me.n_in).to(torch.float64)
-    if me.n_hidden:
-        hp = MLPPolicy._layer(me.W1, me.b1, None, x)
-        h = torch.where(hp > 0, hp, torch.zeros_like(hp))
-    else:
-        h = x
-    y = MLPPolicy._layer(me.W2, me.b2, None, h)
-    zero, one = torch.zeros(n, dtype=torch.float64, device=dev), torch.ones(n, dtype=torch.float64, device=dev)
-    g, best = me._greedy(y)
-    tau = zero + sampling.temperature
-    scale = sampling.scale_on(dev, N)
-    if scale is not None:
-        tau = sampling.temperature * scale.repeat(K)
-    samp = tau > 0
-    b = torch.where(samp, 1.0 / torch.where(samp, tau, one), zero)
-    a = actions.reshape(n).long()
-    e, d, S = [], [], zero
-    for o in range(me.n_out):
-        dd = (y[:, o] - best) * b
-        ok = dd >= EXP_MIN                                                 # (False for a NaN)
-        eo = torch.where(ok, policy_exp(torch.where(ok, dd, torch.full_like(dd, EXP_MIN))), zero)
-        e.append(torch.where(g == o, one, eo))
-        d.append(torch.where(g == o, zero, dd))
-        S = S + e[-1]
-    e_a = zero
-    for o in range(me.n_out):
-        e_a = torch.where(a == o, e[o], e_a)
-    rho = torch.where(samp, e_a / S, one) / old_probs.reshape(n)
-    A = advantages.reshape(n)
-    hi, lo = 1.0 + clip, 1.0 - clip
-    active = ~(((A > 0) & (rho > hi)) | ((A < 0) & (rho < lo)))
-    c = torch.where(samp & active, -(A * rho), zero)
-    pl = torch.where(samp, torch.where(active, c, -(A * torch.where(A > 0, zero + hi, zero + lo))), zero)
-    lnS = policy_log(S)
-    pi, logpi, Hs = [], [], zero
-    for o in range(me.n_out):
-        pi.append(e[o] / S)
-        logpi.append(d[o] - lnS)
-        Hs = torch.where(e[o] > 0, Hs + pi[o] * logpi[o], Hs)
-    H = -Hs
-    dy = []
-    for o in range(me.n_out):
-        t = torch.where(e[o] > 0, pi[o] * (logpi[o] + H), zero)
-        v = b * (c * ((a == o).to(torch.float64) - pi[o]) + ent_coef * t)
-        dy.append(torch.where(samp, v, zero))
-    dy = torch.stack(dy, dim=1)
-    dv = vl = None
-    if critic is not None:
-        cw, cb = critic.w.to(dev), critic.b.to(dev)
-        V = MLPPolicy._layer(cw.unsqueeze(1), cb.unsqueeze(1), None, h)[:, 0]
-        diff = V - returns.reshape(n)
-        dv, vl = vf_coef * diff, 0.5 * (diff * diff)
-    cols = []
-    if me.n_hidden:
-        q = torch.zeros_like(h)
-        for o in range(me.n_out):
-            q = q + me.W2[0][o].unsqueeze(0) * dy[:, o:o + 1]
-        if critic is not None:
-            q = q + cw[0].unsqueeze(0) * dv.unsqueeze(1)
-        dh = torch.where(h > 0, q, torch.zeros_like(q))
-        cols += [(dh.unsqueeze(2) * x.unsqueeze(1)).reshape(n, -1), dh]
-    cols += [(dy.unsqueeze(2) * h.unsqueeze(1)).reshape(n, -1), dy]
-    if critic is not None:
-        cols += [dv.unsqueeze(1) * h, dv.unsqueeze(1)]
-    terms = torch.cat(cols, dim=1)
-    st = torch.stack([pl, vl if vl is not None else zero, torch.where(samp, H, zero), (samp & ~active).to(torch.float64)], dim=1)
-    if mask is not None:
-        keep = mask.reshape(n) != 0
-        terms, st = terms[keep], st[keep]
-    M = terms.shape[0]
-    inv = 1.0 / M if M else 0.0
-    flat, stats = inv * terms.sum(dim=0), inv * st.sum(dim=0)
-    res = _ppo_result(flat, stats, me, critic)
-    if ratio:
-        res["ratio"] = rho.reshape(K, N)
-    if per_sample:
-        res["terms"], res["stat_terms"] = terms, st
-    return res
+    return _ppo_grad_host(_SoftmaxGrad, policy, critic, rows, actions, old_probs, advantages, returns, sampling, clip, vf_coef, ent_coef,
+                          mask, ratio, per_sample)
+
+
+def ppo_grad_gaussian_host(policy, critic, rows, raw_actions, old_logp, advantages, returns=None, sampling=None, clip=0.2, vf_coef=0.5,
+                           ent_coef=0.0, mask=None, ratio=False, per_sample=False):
+    """The rule of ``mgx_policy_grad_gaussian`` (include/mgx.h) in torch, on any device, operation by operation: ``ppo_grad_host`` for the
+    Gaussian head of a continuous ``MLPPolicy`` -- the gradient of ``mean(policy loss) + vf_coef * mean(value loss) - ent_coef *
+    mean(entropy)`` with respect to the parameters and to ``log sigma``, ``{"W1", "b1", "W2", "b2", "w", "b", "log_sigma", "stats"[,
+    "ratio"]}``: ``log_sigma`` ``[4]`` (0.0 past ``n_out`` and on a column with sigma 0), ``stats`` ``[5]``: the means of policy loss,
+    value loss, entropy, clipped fraction and ``kl = (rho - 1) - (logp - old_logp)``.  ``per_sample=True`` adds ``"terms"`` ``[M, P]`` in
+    the column order of ``ppo_grad_flat`` and ``"stat_terms"`` ``[M, 5]``."""
+    return _ppo_grad_host(_GaussianGrad, policy, critic, rows, raw_actions, old_logp, advantages, returns, sampling, clip, vf_coef,
+                          ent_coef, mask, ratio, per_sample)
 
 
 def _ppo_outputs(shapes, out, dev, masked):
@@ -1042,6 +1108,46 @@ def _ppo_outputs(shapes, out, dev, masked):
     return res
 
 
+def _ppo_grad_device(head, fn, policy, critic, rows, taken, old, advantages, returns, sampling, clip, vf_coef, ent_coef, mask, ratio, out):
+    """The device call of ``fn`` (``ppo_grad`` / ``ppo_grad_gaussian``), stated once: ``head`` names the struct, its two fields for the
+    action taken and the old density, the gradients and statistics beyond the common ones, and the symbol."""
+    K, N, clip, vf_coef, ent_coef = _ppo_checks(head, policy, critic, rows, taken, old, advantages, returns, sampling, clip, vf_coef,
+                                                ent_coef, mask)
+    dev = rows.device
+    if dev.type != "cuda":
+        raise ValueError(f"{fn} runs on the GPU ({head.symbol}); the tensors lie on {dev} -- {fn}_host states the same rule anywhere")
+    for name, t in (("rows", rows), (head.taken, taken), (head.old, old), ("advantages", advantages), ("returns", returns), ("mask", mask)):
+        if t is not None and not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
+    shapes = {**_ppo_shapes(head, policy, critic), "stats": (head.n_stats,), "ratio": (K, N) if ratio else None}
+    res = _ppo_outputs(shapes, out, dev, mask is not None)
+    lib = _lib.lib()
+    ptr = lambda t: None if t is None else t.data_ptr()     # noqa: E731
+    with torch.cuda.device(dev):
+        pol, keep_p = policy.c_struct(dev, N)
+        smp, keep_s = sampling.c_struct(dev, N)
+        cr, keep_c = critic.c_struct(dev, N) if critic is not None else (None, None)
+        need = C.c_int64()
+        _lib.check(lib.mgx_policy_grad_workspace(N, K, C.byref(pol), C.byref(need)))
+        ws = torch.empty((need.value + 7) // 8, dtype=torch.float64, device=dev)
+        m8 = mask.view(torch.uint8) if mask is not None and mask.dtype == torch.bool else mask
+        pg = head.struct()
+        pg.struct_size = C.sizeof(head.struct)
+        pg.x_f32 = int(rows.dtype == torch.float32)
+        pg.x, pg.advantage, pg.returns, pg.mask = ptr(rows), ptr(advantages), ptr(returns), ptr(m8)
+        for field, t in zip(head.fields, (taken, old)):
+            setattr(pg, field, ptr(t))
+        pg.clip_eps, pg.vf_coef, pg.ent_coef = clip, vf_coef, ent_coef
+        pg.g_w1, pg.g_b1, pg.g_w2, pg.g_b2 = ptr(res["W1"]), ptr(res["b1"]), ptr(res["W2"]), ptr(res["b2"])
+        pg.g_cw, pg.g_cb, pg.stats, pg.ratio_out = ptr(res["w"]), ptr(res["b"]), ptr(res["stats"]), ptr(res.get("ratio"))
+        for name in head.extra:
+            setattr(pg, "g_" + name, ptr(res[name]))
+        pg.workspace, pg.workspace_bytes = ws.data_ptr(), ws.numel() * 8
+        _lib.check(getattr(lib, head.symbol)(N, K, C.byref(pol), C.byref(cr) if cr is not None else None, C.byref(smp), C.byref(pg),
+                                             torch.cuda.current_stream(dev).cuda_stream))
+    return res
+
+
 def ppo_grad(policy, critic, rows, actions, old_probs, advantages, returns=None, sampling=None, clip=0.2, vf_coef=0.5, ent_coef=0.0,
              mask=None, ratio=False, out=None):
     """The gradient of the PPO-clip loss (``clip=float("inf")``: A2C, the unclipped surrogate) of a discrete ``MLPPolicy`` and the
@@ -1056,131 +1162,8 @@ def ppo_grad(policy, critic, rows, actions, old_probs, advantages, returns=None,
     "b2", "w", "b", "stats"[, "ratio"]}``: tensors shaped like the parameters without the population axis (None where there is none),
     ``stats`` = the means of policy loss, value loss, entropy, clipped fraction.  ``out``: a dict with your own contiguous float64
     tensors for any of them (e.g. the ``.grad`` of the parameters).  Contiguous device tensors only."""
-    K, N, clip, vf_coef, ent_coef = _ppo_args(policy, critic, rows, actions, old_probs, advantages, returns, sampling, clip, vf_coef,
-                                              ent_coef, mask)
-    dev = rows.device
-    if dev.type != "cuda":
-        raise ValueError(f"ppo_grad runs on the GPU (mgx_policy_grad); the tensors lie on {dev} -- ppo_grad_host states the same rule anywhere")
-    for name, t in (("rows", rows), ("actions", actions), ("old_probs", old_probs), ("advantages", advantages), ("returns", returns),
-                    ("mask", mask)):
-        if t is not None and not t.is_contiguous():
-            raise ValueError(f"{name} must be contiguous")
-    n_mid = policy.n_hidden or policy.n_in
-    shapes = {"W1": (policy.n_hidden, policy.n_in) if policy.n_hidden else None, "b1": (policy.n_hidden,) if policy.n_hidden else None,
-              "W2": (policy.n_out, n_mid), "b2": (policy.n_out,), "w": (n_mid,) if critic is not None else None,
-              "b": (1,) if critic is not None else None, "stats": (4,), "ratio": (K, N) if ratio else None}
-    res = _ppo_outputs(shapes, out, dev, mask is not None)
-    lib = _lib.lib()
-    ptr = lambda t: None if t is None else t.data_ptr()     # noqa: E731
-    with torch.cuda.device(dev):
-        pol, keep_p = policy.c_struct(dev, N)
-        smp, keep_s = sampling.c_struct(dev, N)
-        cr, keep_c = critic.c_struct(dev, N) if critic is not None else (None, None)
-        need = C.c_int64()
-        _lib.check(lib.mgx_policy_grad_workspace(N, K, C.byref(pol), C.byref(need)))
-        ws = torch.empty((need.value + 7) // 8, dtype=torch.float64, device=dev)
-        m8 = mask.view(torch.uint8) if mask is not None and mask.dtype == torch.bool else mask
-        pg = _lib.PolicyGrad()
-        pg.struct_size = C.sizeof(_lib.PolicyGrad)
-        pg.x_f32 = int(rows.dtype == torch.float32)
-        pg.x, pg.action_id, pg.old_prob, pg.advantage = ptr(rows), ptr(actions), ptr(old_probs), ptr(advantages)
-        pg.returns, pg.mask = ptr(returns), ptr(m8)
-        pg.clip_eps, pg.vf_coef, pg.ent_coef = clip, vf_coef, ent_coef
-        pg.g_w1, pg.g_b1, pg.g_w2, pg.g_b2 = ptr(res["W1"]), ptr(res["b1"]), ptr(res["W2"]), ptr(res["b2"])
-        pg.g_cw, pg.g_cb, pg.stats, pg.ratio_out = ptr(res["w"]), ptr(res["b"]), ptr(res["stats"]), ptr(res.get("ratio"))
-        pg.workspace, pg.workspace_bytes = ws.data_ptr(), ws.numel() * 8
-        _lib.check(lib.mgx_policy_grad(N, K, C.byref(pol), C.byref(cr) if cr is not None else None, C.byref(smp), C.byref(pg),
-                                       torch.cuda.current_stream(dev).cuda_stream))
-    return res
-
-
-ENTROPY_CONST = 1.4189385332046727     # (1 + log(2 pi)) / 2: the entropy of a unit normal (include/mgx.h, mgx_policy_grad_gaussian)
-
-
-def ppo_grad_gaussian_host(policy, critic, rows, raw_actions, old_logp, advantages, returns=None, sampling=None, clip=0.2, vf_coef=0.5,
-                           ent_coef=0.0, mask=None, ratio=False, per_sample=False):
-    """The rule of ``mgx_policy_grad_gaussian`` (include/mgx.h) in torch, on any device, operation by operation: ``ppo_grad_host`` for the
-    Gaussian head of a continuous ``MLPPolicy`` -- the gradient of ``mean(policy loss) + vf_coef * mean(value loss) - ent_coef *
-    mean(entropy)`` with respect to the parameters and to ``log sigma``, ``{"W1", "b1", "W2", "b2", "w", "b", "log_sigma", "stats"[,
-    "ratio"]}``: ``log_sigma`` ``[4]`` (0.0 past ``n_out`` and on a column with sigma 0), ``stats`` ``[5]``: the means of policy loss,
-    value loss, entropy, clipped fraction and ``kl = (rho - 1) - (logp - old_logp)``.  ``per_sample=True`` adds ``"terms"`` ``[M, P]`` in
-    the column order of ``ppo_grad_flat`` and ``"stat_terms"`` ``[M, 5]``."""
-    K, N, clip, vf_coef, ent_coef = _ppo_gaussian_args(policy, critic, rows, raw_actions, old_logp, advantages, returns, sampling, clip,
-                                                       vf_coef, ent_coef, mask)
-    dev = rows.device
-    me = policy.to(dev)
-    n, nA = K * N, me.n_out
-    x = rows.reshape(n, me.n_in).to(torch.float64)
-    if me.n_hidden:
-        hp = MLPPolicy._layer(me.W1, me.b1, None, x)
-        h = torch.where(hp > 0, hp, torch.zeros_like(hp))
-    else:
-        h = x
-    y = MLPPolicy._layer(me.W2, me.b2, None, h)
-    zero, one = torch.zeros(n, dtype=torch.float64, device=dev), torch.ones(n, dtype=torch.float64, device=dev)
-    scale = sampling.scale_on(dev, N)
-    s = [zero + sampling.sigma[o] if scale is None else sampling.sigma[o] * scale.repeat(K) for o in range(nA)]
-    lv = [v > 0 for v in s]
-    sd = [torch.where(lv[o], s[o], one) for o in range(nA)]
-    Cn, Hc, anyl = zero, zero, torch.zeros(n, dtype=torch.bool, device=dev)
-    for o in range(nA):
-        L = policy_log(sd[o])
-        Cn = torch.where(lv[o], Cn + (L + HALF_LOG_2PI), Cn)
-        Hc = torch.where(lv[o], Hc + (L + ENTROPY_CONST), Hc)
-        anyl = anyl | lv[o]
-    raw = raw_actions.reshape(n, nA)
-    zeta, Q = [], zero
-    for o in range(nA):
-        zeta.append((raw[:, o] - y[:, o]) / sd[o])
-        Q = torch.where(lv[o], Q + zeta[o] * zeta[o], Q)
-    logp = (-0.5 * Q) - Cn
-    Dl = logp - old_logp.reshape(n)
-    nan = Dl != Dl
-    Dz = torch.where(nan, zero, Dl)
-    down = Dz <= 0
-    m = torch.where(down, Dz, -Dz)
-    E = policy_exp(torch.where(m < EXP_MIN, torch.full_like(m, EXP_MIN), m))
-    rho = torch.where(nan, torch.full_like(E, float("nan")), torch.where(down, E, 1.0 / E))
-    A = advantages.reshape(n)
-    hi, lo = 1.0 + clip, 1.0 - clip
-    active = ~(((A > 0) & (rho > hi)) | ((A < 0) & (rho < lo)))
-    c = torch.where(anyl & active, -(A * rho), zero)
-    pl = torch.where(anyl, torch.where(active, c, -(A * torch.where(A > 0, zero + hi, zero + lo))), zero)
-    kl = torch.where(anyl, (rho - 1.0) - Dl, zero)
-    dy = torch.stack([torch.where(lv[o], c * (zeta[o] / sd[o]), zero) for o in range(nA)], dim=1)
-    dls = torch.stack([torch.where(lv[o], (c * (zeta[o] * zeta[o] - 1.0)) - ent_coef, zero) if o < nA else zero
-                       for o in range(MAX_CONTROLS)], dim=1)
-    dv = vl = None
-    if critic is not None:
-        cw, cb = critic.w.to(dev), critic.b.to(dev)
-        V = MLPPolicy._layer(cw.unsqueeze(1), cb.unsqueeze(1), None, h)[:, 0]
-        diff = V - returns.reshape(n)
-        dv, vl = vf_coef * diff, 0.5 * (diff * diff)
-    cols = []
-    if me.n_hidden:
-        q = torch.zeros_like(h)
-        for o in range(nA):
-            q = q + me.W2[0][o].unsqueeze(0) * dy[:, o:o + 1]
-        if critic is not None:
-            q = q + cw[0].unsqueeze(0) * dv.unsqueeze(1)
-        dh = torch.where(h > 0, q, torch.zeros_like(q))
-        cols += [(dh.unsqueeze(2) * x.unsqueeze(1)).reshape(n, -1), dh]
-    cols += [(dy.unsqueeze(2) * h.unsqueeze(1)).reshape(n, -1), dy]
-    if critic is not None:
-        cols += [dv.unsqueeze(1) * h, dv.unsqueeze(1)]
-    terms = torch.cat(cols + [dls], dim=1)
-    st = torch.stack([pl, vl if vl is not None else zero, Hc, (anyl & ~active).to(torch.float64), kl], dim=1)
-    if mask is not None:
-        keep = mask.reshape(n) != 0
-        terms, st = terms[keep], st[keep]
-    M = terms.shape[0]
-    inv = 1.0 / M if M else 0.0
-    res = _ppo_result(inv * terms.sum(dim=0), inv * st.sum(dim=0), me, critic, log_sigma=True)
-    if ratio:
-        res["ratio"] = rho.reshape(K, N)
-    if per_sample:
-        res["terms"], res["stat_terms"] = terms, st
-    return res
+    return _ppo_grad_device(_SoftmaxGrad, "ppo_grad", policy, critic, rows, actions, old_probs, advantages, returns, sampling, clip,
+                            vf_coef, ent_coef, mask, ratio, out)
 
 
 def ppo_grad_gaussian(policy, critic, rows, raw_actions, old_logp, advantages, returns=None, sampling=None, clip=0.2, vf_coef=0.5,
@@ -1197,41 +1180,5 @@ def ppo_grad_gaussian(policy, critic, rows, raw_actions, old_logp, advantages, r
     loss, value loss, entropy, clipped fraction, ``kl``.  Who learns sigma keeps a ``log_sigma`` tensor, steps it with this gradient
     and builds the next ``GaussianSampling`` from ``log_sigma.exp().tolist()``.  With the parameters that collected the data ``ratio``
     is 1.0 up to the rounding of ``raw = y + s * z`` (the bound: include/mgx.h), not exactly."""
-    K, N, clip, vf_coef, ent_coef = _ppo_gaussian_args(policy, critic, rows, raw_actions, old_logp, advantages, returns, sampling, clip,
-                                                       vf_coef, ent_coef, mask)
-    dev = rows.device
-    if dev.type != "cuda":
-        raise ValueError(f"ppo_grad_gaussian runs on the GPU (mgx_policy_grad_gaussian); the tensors lie on {dev} -- "
-                         "ppo_grad_gaussian_host states the same rule anywhere")
-    for name, t in (("rows", rows), ("raw_actions", raw_actions), ("old_logp", old_logp), ("advantages", advantages), ("returns", returns),
-                    ("mask", mask)):
-        if t is not None and not t.is_contiguous():
-            raise ValueError(f"{name} must be contiguous")
-    n_mid = policy.n_hidden or policy.n_in
-    shapes = {"W1": (policy.n_hidden, policy.n_in) if policy.n_hidden else None, "b1": (policy.n_hidden,) if policy.n_hidden else None,
-              "W2": (policy.n_out, n_mid), "b2": (policy.n_out,), "w": (n_mid,) if critic is not None else None,
-              "b": (1,) if critic is not None else None, "log_sigma": (MAX_CONTROLS,), "stats": (5,), "ratio": (K, N) if ratio else None}
-    res = _ppo_outputs(shapes, out, dev, mask is not None)
-    lib = _lib.lib()
-    ptr = lambda t: None if t is None else t.data_ptr()     # noqa: E731
-    with torch.cuda.device(dev):
-        pol, keep_p = policy.c_struct(dev, N)
-        smp, keep_s = sampling.c_struct(dev, N)
-        cr, keep_c = critic.c_struct(dev, N) if critic is not None else (None, None)
-        need = C.c_int64()
-        _lib.check(lib.mgx_policy_grad_workspace(N, K, C.byref(pol), C.byref(need)))
-        ws = torch.empty((need.value + 7) // 8, dtype=torch.float64, device=dev)
-        m8 = mask.view(torch.uint8) if mask is not None and mask.dtype == torch.bool else mask
-        pg = _lib.PolicyGradGaussian()
-        pg.struct_size = C.sizeof(_lib.PolicyGradGaussian)
-        pg.x_f32 = int(rows.dtype == torch.float32)
-        pg.x, pg.raw_action, pg.old_logp, pg.advantage = ptr(rows), ptr(raw_actions), ptr(old_logp), ptr(advantages)
-        pg.returns, pg.mask = ptr(returns), ptr(m8)
-        pg.clip_eps, pg.vf_coef, pg.ent_coef = clip, vf_coef, ent_coef
-        pg.g_w1, pg.g_b1, pg.g_w2, pg.g_b2 = ptr(res["W1"]), ptr(res["b1"]), ptr(res["W2"]), ptr(res["b2"])
-        pg.g_cw, pg.g_cb, pg.g_log_sigma = ptr(res["w"]), ptr(res["b"]), ptr(res["log_sigma"])
-        pg.stats, pg.ratio_out = ptr(res["stats"]), ptr(res.get("ratio"))
-        pg.workspace, pg.workspace_bytes = ws.data_ptr(), ws.numel() * 8
-        _lib.check(lib.mgx_policy_grad_gaussian(N, K, C.byref(pol), C.byref(cr) if cr is not None else None, C.byref(smp), C.byref(pg),
-                                                torch.cuda.current_stream(dev).cuda_stream))
-    return res
+    return _ppo_grad_device(_GaussianGrad, "ppo_grad_gaussian", policy, critic, rows, raw_actions, old_logp, advantages, returns, sampling,
+                            clip, vf_coef, ent_coef, mask, ratio, out)

@@ -133,6 +133,24 @@ def test_greedy_rows_carry_only_the_value_term():
     assert (only_value["W2"] == 0.0).all() and (only_value["b2"] == 0.0).all() and only_value["w"].abs().sum() > 0.0
 
 
+@pytest.mark.parametrize("n_out", [12, 4])
+def test_ratio_of_the_collecting_policy_is_exactly_one(n_out):
+    """What the GPU end-to-end test states on the device, on the host: the gradient restates the forward of ``act`` operation by
+    operation, so the probabilities ``act`` returned, fed back with the same parameters, give ``ratio == 1.0`` exactly -- on the
+    grids of a temperature ladder and on the one whose ``scale`` of 0 makes it greedy."""
+    N = 64
+    c = make_case(1, N, 10, 16, n_out, critic=False, seed=23 + n_out)
+    scale = torch.linspace(0.25, 2.0, N, dtype=torch.float64)
+    scale[7] = 0.0
+    sampling = Sampling(7, 0.8, scale=scale)
+    obs = c["rows"][0]
+    ids, prob = c["policy"].act(obs, sampling, 5, return_prob=True)
+    assert prob[7] == 1.0 and 1 < len(set(ids.tolist())) and (prob < 1.0).sum() >= N - 2       # (a ladder that does sample)
+    res = ppo_grad_host(c["policy"], None, obs.unsqueeze(0), ids.to(torch.uint8).unsqueeze(0), prob.unsqueeze(0), c["advantages"],
+                        sampling=sampling, ratio=True)
+    assert res["ratio"].shape == (1, N) and (res["ratio"] == 1.0).all()
+
+
 def test_mask_all_zero_gives_zeros():
     c = make_case(2, 5, 6, 5, 4, seed=17)
     res = ppo_grad_host(**c, mask=torch.zeros(2, 5, dtype=torch.uint8))
