@@ -3,6 +3,8 @@ bit 3 grid before battery), carved out of ONE generated ``genset+battery+grid`` 
 dropped, everything else -- series, parameters, initial state -- is cloned, so the ten batches differ in their module set alone."""
 import dataclasses
 
+import numpy as np
+
 F_GENSET, F_BATTERY, F_GRID, F_GRID_FIRST = 1, 2, 4, 8
 LAYOUTS = (0, 1, 2, 3, 4, 5, 6, 7, 14, 15)
 FACTOR_GRID_COLUMNS = ("base_co2", "co2_profile", "tariff", "outage_bits")
@@ -41,3 +43,44 @@ def carve(full, flags):
     sub = MicrogridBatch(layout, cols, forecast_noise=full.forecast_noise)
     assert flags_of(sub.layout) == flags, (flags, sub.layout)
     return sub
+
+
+def walked(cols, rows):
+    """The columns of a batch (``numpy_columns()``) with the [K, N] series every grid walked in place of the [T, N] ones: ``rows``
+    int [K, N], grid i's series row at step k, restarts included."""
+    K = rows.shape[0]
+    assert rows.min() >= 0 and rows.max() < cols["layout"]["T"]
+    out = dict(cols)
+    out["layout"] = dict(cols["layout"], T=K, final_step=K)
+    out["load_ts"] = np.ascontiguousarray(np.take_along_axis(cols["load_ts"], rows, 0))
+    out["pv_ts"] = np.ascontiguousarray(np.take_along_axis(cols["pv_ts"], rows, 0))
+    if cols.get("grid_ts") is not None:
+        out["grid_ts"] = np.ascontiguousarray(np.take_along_axis(cols["grid_ts"], rows[:, None, :].repeat(4, 1), 0))
+    return out
+
+
+def replay(oracle, cols, trace, normalized=True, label=""):
+    """The fused launches of ``trace`` against the CPU oracle: the series every grid walked (its row at every step, restarts
+    included) out of ``cols``, the materialised columns of the batch before the first launch, replayed from row 0 -- a restart
+    keeps the module state and moves only the counter, so one batch run covers the restarts.  Rewards and the state after the last
+    launch must equal the fused ones on every grid: the oracle may leave none out.  ``trace``: ``launches`` (per launch ``rows``
+    [K, N], ``controls`` ids [K, N] or controls [K, N, A], ``reward`` [K, N]), ``state`` (the state columns after the last launch)
+    and, for ids, ``table`` (the priority lists)."""
+    st = {k: cols[k].copy() for k in ("charge", "soc", "gen_status") if k in cols}
+    rows = np.concatenate([ln["rows"].cpu().numpy() for ln in trace["launches"]]).astype(np.int64)
+    controls = np.concatenate([ln["controls"].double().cpu().numpy() if ln["controls"].is_floating_point() else ln["controls"].cpu().numpy()
+                               for ln in trace["launches"]])
+    reward = np.concatenate([ln["reward"].cpu().numpy() for ln in trace["launches"]])
+    K, n = rows.shape
+    assert len(np.unique(rows[0])) > 10 and (np.diff(rows, axis=0) != 1).any()         # own rows, and restarts among them
+    series = walked(cols, rows)
+    failed = np.zeros(n, dtype=np.uint8)
+    if trace.get("table") is not None:
+        ref = oracle.rollout_batch(series, st, 0, K, controls, trace["table"], nthreads=8, failed=failed)
+    else:
+        ref = oracle.run_batch(series, st, 0, K, controls, normalized=normalized, nthreads=8, failed=failed)
+    assert int(failed.sum()) == 0, f"{label}: the oracle left out {int(failed.sum())} of {n} grids"
+    assert np.array_equal(reward, ref), label
+    for name, want in st.items():
+        got = trace["state"][name].cpu().numpy()
+        assert np.array_equal(got.view(np.uint32) if name == "gen_status" else got, want), (label, name)

@@ -3,10 +3,10 @@ observation rows) on the seven module layouts that generate(arch=...) cannot dra
 from all three row sources, with the comparisons of test_rollout_episodes.py / test_step_k_episodes.py / test_episode_rows.py (the
 fused launches == a single-stepped twin, bit for bit, through restarts), the single-step episode kernels of those layouts against
 the rolling window buffers (test_episodes_inplace.py) and, per layout, an independent replay of the series rows the grids walked
-by the CPU oracle.  The batches are carved out of one generated batch (tests/layouts.py)."""
+by the CPU oracle.  The batches are carved out of one generated batch (tests/layouts.py).  The closed-loop policy kernels and the
+what-if kernels have matrices of the same shape: tests/test_layout_matrix_policy.py, tests/test_layout_matrix_whatif.py."""
 import itertools
 
-import numpy as np
 import pytest
 import torch
 
@@ -14,7 +14,7 @@ import test_episode_rows as rows_tests
 import test_episodes_inplace as inplace_tests
 import test_rollout_episodes as rollout_tests
 import test_step_k_episodes as step_k_tests
-from layouts import carve
+from layouts import carve, replay
 
 EPISODE_LAYOUTS = (0, 1, 2, 4, 5, 14, 15)                    # 3, 6, 7: the generated architectures of the files above
 GENERATED = (3, 6, 7)
@@ -113,34 +113,10 @@ def test_native_auto_reset_equals_the_rolling_window_auto_reset(flags, H, discre
 
 # ---- the independent check: the oracle replays the rows the grids walked ---------------------------------------------------------
 def _replay(oracle, device, flags, series, trace, normalized=True):
-    """The fused launches of `trace` against the CPU oracle: the [K, N] series every grid walked (its row at every step, restarts
-    included), built from the materialised columns and replayed from row 0 -- a restart keeps the module state and moves only the
-    counter, so one batch run covers the restarts.  Rewards and the state after the last launch must equal the fused ones on every
-    grid: the oracle may leave none out."""
-    cols = carved(device, flags, series).numpy_columns()
-    st = {k: cols[k].copy() for k in ("charge", "soc", "gen_status") if k in cols}
-    rows = torch.cat([ln["rows"] for ln in trace["launches"]]).cpu().numpy().astype(np.int64)
-    controls = torch.cat([ln["controls"] for ln in trace["launches"]])
-    reward = torch.cat([ln["reward"] for ln in trace["launches"]]).cpu().numpy()
-    K, n = rows.shape
-    assert K == sum(step_k_tests.LAUNCHES) and rows.min() >= 0 and rows.max() < cols["layout"]["T"]
-    assert len(np.unique(rows[:, 0])) > 10 and (np.diff(rows, axis=0) != 1).any()      # own rows, and restarts among them
-    walked = dict(cols)
-    walked["layout"] = dict(cols["layout"], T=K, final_step=K)
-    walked["load_ts"] = np.ascontiguousarray(np.take_along_axis(cols["load_ts"], rows, 0))
-    walked["pv_ts"] = np.ascontiguousarray(np.take_along_axis(cols["pv_ts"], rows, 0))
-    if cols.get("grid_ts") is not None:
-        walked["grid_ts"] = np.ascontiguousarray(np.take_along_axis(cols["grid_ts"], rows[:, None, :].repeat(4, 1), 0))
-    failed = np.zeros(n, dtype=np.uint8)
-    if trace.get("table") is not None:
-        ref = oracle.rollout_batch(walked, st, 0, K, controls.cpu().numpy(), trace["table"], nthreads=8, failed=failed)
-    else:
-        ref = oracle.run_batch(walked, st, 0, K, controls.double().cpu().numpy(), normalized=normalized, nthreads=8, failed=failed)
-    assert int(failed.sum()) == 0, f"layout {flags}, {series}: the oracle left out {int(failed.sum())} of {n} grids"
-    assert np.array_equal(reward, ref)
-    for name, want in st.items():
-        got = trace["state"][name].cpu().numpy()
-        assert np.array_equal(got.view(np.uint32) if name == "gen_status" else got, want), name
+    """layouts.replay on the batch the helpers carved: every launch of LAUNCHES is in the trace."""
+    assert sum(ln["rows"].shape[0] for ln in trace["launches"]) == sum(step_k_tests.LAUNCHES)
+    assert len(torch.cat([ln["rows"][:, 0] for ln in trace["launches"]]).unique()) > 10          # (grid 0 alone walks more than ten rows)
+    replay(oracle, carved(device, flags, series).numpy_columns(), trace, normalized, f"layout {flags}, {series}")
 
 
 ORACLE_CASES = tuple((flags, SOURCES[li % 3], LENGTHS[li % 2]) for li, flags in enumerate(EPISODE_LAYOUTS))

@@ -1,7 +1,10 @@
-"""The inputs of the layout matrices (tests/test_layout_matrix.py, tests/test_layout_matrix_episodes.py), checked without a GPU:
+"""The inputs of the layout matrices (tests/test_layout_matrix.py, tests/test_layout_matrix_episodes.py,
+tests/test_layout_matrix_policy.py, tests/test_layout_matrix_whatif.py), checked without a GPU:
 layouts.carve gives every one of the ten layouts the fused kernels are compiled for, in both series forms, the CPU oracle replays
 each of them without leaving a grid out, the inputs tell the grid-first layouts from the battery-first ones and reach both genset
-forms of the loops -- and every instantiation of the six fused kernel families that the library holds is a case of those matrices."""
+forms of the loops -- and every instantiation of the fifteen kernel families of FAMILIES that the library holds (the open-loop fused
+kernels, the closed-loop policy kernels, the what-if kernels, the policy gradient, the hot K-step) is a case of those matrices, or
+one of the forms a matrix file names as refused with the refusal asserted."""
 import functools
 import re
 
@@ -143,7 +146,52 @@ def enumerated():
     import test_layout_matrix_episodes as eps
     import test_rollout_episodes as roll
     import test_step_k_episodes as stepk
+    import test_cem as cem
+    import test_layout_matrix_policy as pol
+    import test_layout_matrix_whatif as whatif
+    import test_lookahead as look
+    import test_policy_critic as critic
+    import test_policy_explore as explore
+    import test_policy_gaussian as gauss
+    import test_policy_grad as grad
+    import test_policy_grad_gaussian as grad_gauss
+    import test_policy_rollout as greedy
+    import test_policy_sample as sample
+    import test_step_k_hot as hot
+
+    def flags(arch):
+        return ARCH_FLAGS.get(arch, arch)
+    GREEDY, EXPLORE, SAMPLE, SAMPLE_CRITIC, GAUSSIAN, GAUSSIAN_CRITIC = range(6)         # PolicyHead (csrc/mgx_policy.hpp)
     want = {
+        # (layout, row source) of the greedy closed-loop kernels; cases (discrete, arch, series, ...) / (layout, series, ..., discrete)
+        "rollout_policy_episodes_kernel": {(flags(c[1]), SRC[c[2]]) for c in greedy.CASES if c[0]}
+        | {(c[0], SRC[c[1]]) for c in pol.GREEDY_CASES if c[6]},
+        "step_k_policy_episodes_kernel": {(flags(c[1]), SRC[c[2]]) for c in greedy.CASES if not c[0]}
+        | {(c[0], SRC[c[1]]) for c in pol.GREEDY_CASES if not c[6]},
+        # (layout, row source, head)
+        "rollout_policy_head_episodes_kernel": {(flags(c[1]), SRC[c[2]], EXPLORE) for c in explore.CASES if c[0]}
+        | {(c[0], SRC[c[1]], EXPLORE) for c in pol.EXPLORE_CASES if c[6]}
+        | {(flags(c[0]), SRC[c[1]], head) for c in sample.CASES for head in (SAMPLE, SAMPLE_CRITIC)}      # (test_policy_critic runs them too)
+        | {(c[0], SRC[c[1]], SAMPLE_CRITIC if c[6] else SAMPLE) for c in pol.SAMPLE_CASES},
+        "step_k_policy_head_episodes_kernel": {(flags(c[1]), SRC[c[2]], EXPLORE) for c in explore.CASES if not c[0]}
+        | {(c[0], SRC[c[1]], EXPLORE) for c in pol.EXPLORE_CASES if not c[6]}
+        | {(c[0], SRC[c[1]], GAUSSIAN) for c in gauss.CASES}
+        | {(c[0], SRC[c[1]], GAUSSIAN_CRITIC if c[6] else GAUSSIAN) for c in pol.GAUSSIAN_CASES},
+        # (layout, PER_GRID, row source)
+        "lookahead_episodes_kernel": {(flags(c[0]), c[5], SRC[c[1]]) for c in look.CASES}
+        | {(c[0], c[6], SRC[c[1]]) for c in whatif.DISCRETE_CASES},
+        # (layout, control type, PER_GRID, row source)
+        "lookahead_step_k_episodes_kernel": {(flags(c[0]), _ctype(c[9]), c[5], SRC[c[1]]) for c in look.CONT_CASES}
+        | {(c[0], _ctype(c[7]), c[6], SRC[c[1]]) for c in whatif.CONTINUOUS_CASES},
+        # (layout, row source)
+        "lookahead_gaussian_episodes_kernel": {(flags(c[0]), SRC[c[1]]) for c in cem.CASES} | {(c[0], SRC[c[1]]) for c in whatif.CEM_CASES},
+        # (row width, CRITIC, head: softmax / Gaussian)
+        "policy_grad_kernel": {(c[1], c[3], 0) for c in grad.ONE_SAMPLE_CASES} | {(c[2], True, 0) for c in grad.MANY_SAMPLES_CASES}
+        | {(c[0], c[1], 0) for c in grad.WIDTH_CASES}
+        | {(c[1], c[3], 1) for c in grad_gauss.ONE_SAMPLE_CASES} | {(c[2], True, 1) for c in grad_gauss.MANY_SAMPLES_CASES}
+        | {(c[0], c[1], 1) for c in grad_gauss.WIDTH_CASES},
+        # (layout, control type)
+        "step_k_hot_kernel": {(f, _ctype(dt)) for f in hot.HOT_LAYOUTS for dt in hot.HOT_DTYPES},
         # (layout, control type, RICH, FACT)
         "step_k_kernel": {(f, _ctype(dt), form == "rich", series == "factorised")
                           for f, series, dt in lock.STEP_K_CASES for form in lock.FORMS},
@@ -160,7 +208,19 @@ def enumerated():
         "step_k_episodes_rows_kernel": {(ARCH_FLAGS[c[0]], _ctype(c[4]), SRC[c[1]]) for c in rows.STEP_K_CASES}
         | {(c[0], _ctype(c[4]), SRC[c[1]]) for c in eps.STEP_K_ROWS_CASES},
     }
+    assert critic.CASES is sample.CASES
     return want
+
+
+def refused():
+    """kernel -> the compile-time parts the matrix files name as compiled but out of every call's reach (each file's REFUSED, with a
+    GPU test that asserts the refusal); ``test_every_compiled_specialisation_...`` holds them apart from the cases."""
+    import test_layout_matrix_policy as pol
+    import test_layout_matrix_whatif as whatif
+    out = {}
+    for kernel, part in pol.REFUSED + whatif.REFUSED:
+        out.setdefault(kernel, set()).add(part)
+    return out
 
 
 def compile_time_part(name):
@@ -180,15 +240,30 @@ def compile_time_part(name):
         return kernel, (args[0], args[2], args[3])
     if kernel in ("step_k_episodes_kernel", "step_k_episodes_rows_kernel"):      # <F, U, UA, AT, SRC>
         return kernel, (args[0], args[3], args[4])
+    if kernel in ("rollout_policy_episodes_kernel", "step_k_policy_episodes_kernel"):              # <F, U, SRC>
+        return kernel, (args[0], args[2])
+    if kernel in ("rollout_policy_head_episodes_kernel", "step_k_policy_head_episodes_kernel"):    # <F, U, SRC, HEAD>
+        return kernel, (args[0], args[2], args[3])
+    if kernel == "lookahead_episodes_kernel":                                    # <F, U, PER_GRID, SRC>
+        return kernel, (args[0], args[2], args[3])
+    if kernel == "lookahead_step_k_episodes_kernel":                             # <F, U, UA, AT, PER_GRID, SRC>
+        return kernel, (args[0], args[3], args[4], args[5])
+    if kernel == "lookahead_gaussian_episodes_kernel":                           # <F, U, UA, SRC>
+        return kernel, (args[0], args[3])
+    if kernel == "policy_grad_kernel":                                           # <D, CRITIC, HEAD>
+        return kernel, (args[0], args[1], args[2])
+    if kernel == "step_k_hot_kernel":                                            # <F, U, AT>
+        return kernel, (args[0], args[2])
     return kernel, None
 
 
-def missing_cases(usage, want):
-    """The instantiations of the six families in ``usage`` whose compile-time part no GPU test enumerates."""
+def missing_cases(usage, want, refused=None):
+    """The instantiations in ``usage`` of the families of ``want`` (the fifteen of ``enumerated()``) whose compile-time part no GPU
+    test enumerates and ``refused`` (kernel -> parts with an asserted refusal) does not name."""
     out = []
     for name in sorted(usage):
         kernel, part = compile_time_part(name)
-        if kernel in want and part not in want[kernel]:
+        if kernel in want and part not in want[kernel] and part not in (refused or {}).get(kernel, ()):
             out.append(name)
     return out
 
@@ -204,11 +279,15 @@ def test_every_compiled_specialisation_is_a_case_of_a_gpu_matrix():
     want = enumerated()
     found = {k: sum(1 for name in usage if compile_time_part(name)[0] == k) for k in want}
     assert all(found.values()), found                        # the parser still recognises every family
-    missing = missing_cases(usage, want)
+    out_of_reach = refused()
+    missing = missing_cases(usage, want, out_of_reach)
     assert not missing, f"{len(missing)} compiled specialisation(s) no GPU test runs: {missing}"
     # ... and the other way round: the matrices name nothing the library does not hold (a case that cannot be dispatched)
     held = {k: {compile_time_part(name)[1] for name in usage if compile_time_part(name)[0] == k} for k in want}
     assert all(want[k] <= held[k] for k in want), {k: sorted(want[k] - held[k], key=str) for k in want if not want[k] <= held[k]}
+    # a refused form is a compiled one, and no case claims to run it
+    assert all(k in want and parts <= held[k] and not parts & want[k] for k, parts in out_of_reach.items()), out_of_reach
+    print({k: (len(held[k]), len(out_of_reach.get(k, ()))) for k in sorted(want)})
 
 
 def test_the_coverage_check_names_what_a_dropped_case_leaves_uncovered():
@@ -220,3 +299,20 @@ def test_the_coverage_check_names_what_a_dropped_case_leaves_uncovered():
     assert missing_cases(usage, want) == []
     want["rollout_kernel"] = set()
     assert missing_cases(usage, want) == ["mgx::rollout_kernel<5, 4, true, false, true>"]
+    # one instantiation of each of the nine closed-loop, what-if, gradient and hot families: a case dropped from any of them
+    # leaves exactly that instantiation, and a form named as refused is held apart
+    made_up = {"mgx::rollout_policy_episodes_kernel<14, 4, 2>": (14, 2), "mgx::step_k_policy_episodes_kernel<0, 8, 1>": (0, 1),
+               "mgx::rollout_policy_head_episodes_kernel<4, 8, 0, 3>": (4, 0, 3), "mgx::step_k_policy_head_episodes_kernel<15, 4, 2, 5>": (15, 2, 5),
+               "mgx::lookahead_episodes_kernel<2, 8, true, 1>": (2, True, 1),
+               "mgx::lookahead_step_k_episodes_kernel<5, 4, 4, float, false, 2>": (5, "float", False, 2),
+               "mgx::lookahead_gaussian_episodes_kernel<6, 2, 1, 0>": (6, 0), "mgx::policy_grad_kernel<3, false, 1>": (3, False, 1),
+               "mgx::step_k_hot_kernel<2, 8, float>": (2, "float")}
+    usage = dict.fromkeys(list(made_up) + ["mgx::policy_grad_finish_kernel", "lookahead_pick_kernel"], {})
+    family = lambda name: compile_time_part(name)[0]          # noqa: E731
+    assert len({family(name) for name in made_up}) == 9
+    full = {family(name): {part} for name, part in made_up.items()}
+    assert all(compile_time_part(name) == (family(name), part) for name, part in made_up.items())
+    assert missing_cases(usage, full) == []
+    for name in made_up:
+        assert missing_cases(usage, {**full, family(name): set()}) == [name]
+        assert missing_cases(usage, {**full, family(name): set()}, {family(name): {made_up[name]}}) == []

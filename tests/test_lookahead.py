@@ -1,7 +1,8 @@
 """What-if roll-outs of candidate plans (mgx_lookahead_episodes / mgx_lookahead_step_k_episodes, StepEngine.lookahead_episodes /
 lookahead_step_k_episodes, PerGridWindowEnv.lookahead, ShootingMPC): C plans per grid simulated H steps ahead in one launch that
 commits none of them == C twin envs rolled out with ``rollout`` / ``step_k`` and reduced by ``lookahead_host`` -- returns, steps, pick,
-first action and end SoC bit for bit (torch.equal on fp64: same operations, same order) -- and afterwards nothing has moved."""
+first action and end SoC bit for bit (torch.equal on fp64: same operations, same order) -- and afterwards nothing has moved.  The forms of the kernels these cases leave out -- all ten layouts x the three row sources x shared / per-grid plans
+x the control type -- run in tests/test_layout_matrix_whatif.py, where the CPU oracle also runs every candidate plan."""
 import os
 
 import numpy as np
@@ -80,9 +81,10 @@ class _Gather:
         _lib.set_tunable("grid_major_copy", self.old)
 
 
-def _envs(device, arch, series, length, shaper, obs_h, discrete, count, **kw):
+def _envs(device, arch, series, length, shaper, obs_h, discrete, count, make_batch=None, **kw):
+    """``make_batch(device, arch, series, H)``: the batch factory (default: ``_batch``, a generated batch of architecture ``arch``)."""
     from pymgrid_amd.hetero import PerGridWindowEnv
-    envs = [PerGridWindowEnv(_batch(device, arch, series, obs_h), trajectory_length=length, discrete=discrete, auto_reset=True,
+    envs = [PerGridWindowEnv((make_batch or _batch)(device, arch, series, obs_h), trajectory_length=length, discrete=discrete, auto_reset=True,
                              seed=23 + SOAK, reward_shaping_func=_shaper(shaper), **kw) for _ in range(count)]
     for e in envs:
         torch.manual_seed(41 + SOAK)                   # the same first draw
@@ -104,13 +106,29 @@ def _step_of(plans, best, k, per_grid):
     return plans[b, k, torch.arange(N, device=plans.device)] if per_grid else plans[b, k]
 
 
+def _what_if_start(trace, pe, discrete):
+    """What an independent replay of a what-if call starts from (``trace``: a dict, or None): the columns of the batch -- the state
+    the call finds --, every grid's series row, the steps left in its running episode (the one at ``left`` steps is its last) and,
+    for ids, the priority-list table."""
+    if trace is not None:
+        trace["cols"] = pe.env.batch.numpy_columns()
+        trace["rows"] = pe.env.current_steps.clone()
+        lengths = pe.lengths if pe.lengths is not None else torch.full_like(pe.starts, pe.length)
+        trace["left"] = (pe.starts + lengths - trace["rows"]).to(torch.int64)
+        trace["table"] = pe.env._table if discrete else None
+
+
 def _lookahead_equals_twin_rollouts(device, arch, series, length, H, shaper, per_grid, gamma, prefix, obs_h, discrete,
-                                    dtype=torch.float64, normalized=True):
+                                    dtype=torch.float64, normalized=True, make_batch=None, n_candidates=C_, trace=None):
+    """``make_batch``: the batch factory of ``_envs``; ``n_candidates``: C (at least 4: candidate 3 copies candidate 1);
+    ``trace``: a dict that receives what an independent replay needs -- ``_what_if_start`` before the call, the plans [C, H, N(, A)]
+    every grid was given, the twins' done flags and what the call returned."""
     from pymgrid_amd import lookahead_host
+    C_ = n_candidates
     with _Gather(series):
         kw = {} if discrete else dict(action_dtype=dtype)
         # the env under test, a twin per candidate and one twin nobody looks ahead on
-        envs = _envs(device, arch, series, length, shaper, obs_h, discrete, C_ + 2, **kw)
+        envs = _envs(device, arch, series, length, shaper, obs_h, discrete, C_ + 2, make_batch=make_batch, **kw)
         la, twins, plain = envs[0], envs[1:C_ + 1], envs[C_ + 1]
         g = torch.Generator(device=device); g.manual_seed(3 + SOAK)
         e = la.env.engine
@@ -136,33 +154,38 @@ def _lookahead_equals_twin_rollouts(device, arch, series, length, H, shaper, per
         plans = plans.contiguous()
 
         snap = _snapshot(la)
-        out = la.lookahead(plans, gamma=gamma, normalized=normalized, end_soc=True)
+        soc = "soc" in la.env.batch.cols                   # (a layout without a battery has no end SoC: the call refuses it)
+        _what_if_start(trace, la, discrete)
+        out = la.lookahead(plans, gamma=gamma, normalized=normalized, end_soc=soc)
         _untouched(la, snap)
 
         rewards, socs, dones = [], [], []
         for c, tw in enumerate(twins):
             p = _plan_of(plans, c, per_grid, discrete)
-            r = tw.rollout(p, reward=True, done=True, soc_trace=True) if discrete else \
-                tw.step_k(p, normalized=normalized, reward=True, done=True, soc_trace=True)
-            rewards.append(r["reward"]); socs.append(r["soc_trace"]); dones.append(r["done"])
+            r = tw.rollout(p, reward=True, done=True, soc_trace=soc) if discrete else \
+                tw.step_k(p, normalized=normalized, reward=True, done=True, soc_trace=soc)
+            rewards.append(r["reward"]); socs.append(r.get("soc_trace")); dones.append(r["done"])
         for d in dones[1:]:
             assert torch.equal(d, dones[0])                # the end of an episode depends on the grid alone
         ref = lookahead_host(torch.stack(rewards), dones[0], gamma)
         ar = torch.arange(N, device=device)
-        assert set(out) == {"ret", "steps", "best", "best_ret", "first_action", "end_soc"}
+        if trace is not None:
+            trace.update(plans=torch.stack([_plan_of(plans, c, per_grid, discrete) for c in range(C_)]), done=dones[0], out=dict(out))
+        assert set(out) == {"ret", "steps", "best", "best_ret", "first_action"} | ({"end_soc"} if soc else set())
         assert out["ret"].shape == (C_, N) and torch.equal(out["ret"], ref["ret"])
         assert out["steps"].dtype == torch.int32 and torch.equal(out["steps"], ref["steps"])
         assert out["best"].dtype == torch.int32 and torch.equal(out["best"], ref["best"])
         assert torch.equal(out["best_ret"], ref["best_ret"])
-        assert torch.equal(out["end_soc"], torch.stack([s[ref["last"], ar] for s in socs]))
+        if soc:
+            assert torch.equal(out["end_soc"], torch.stack([s[ref["last"], ar] for s in socs]))
         first = _step_of(plans, ref["best"], 0, per_grid)
         assert out["first_action"].dtype == plans.dtype and torch.equal(out["first_action"], first)
         # the test's own input: ties on every grid and the first of them wins; the steps differ where the case says so
         assert torch.equal(out["ret"][1], out["ret"][3]) and not bool((out["best"] == 3).any())
         steps = out["steps"]
         assert int(steps.min()) >= 1 and int(steps.max()) <= H
-        if length == 6:
-            assert bool((steps == min(H, 1 if prefix else 6)).all())
+        if length is not None:                             # (length 6: 1 step left after the prefix of 5, or all 6)
+            assert prefix < length and bool((steps == min(H, length - prefix)).all())
         elif H == 9:
             assert len(steps.unique()) > 2 and int(steps.max()) == H
         # pick=False: the return launch alone, the same returns

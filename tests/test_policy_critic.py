@@ -2,7 +2,8 @@
 StepEngine.rollout_policy_episodes and PerGridWindowEnv.rollout_policy) and the advantages on the device (mgx_gae, ``pymgrid_amd.gae``):
 the rules of ``mgx_critic`` and ``mgx_gae`` (include/mgx.h) on the host (``ValueHead.value``, ``gae_host``) against scalar Python
 loops, and the kernels against those host statements bit for bit (torch.equal / _same_bits: both rules are fixed sequences of IEEE
-operations on both sides, so there is no tolerance)."""
+operations on both sides, so there is no tolerance).  The forms of the kernels these cases leave out -- all ten layouts x the three row sources -- run in
+tests/test_layout_matrix_policy.py, which also replays the launches on the CPU oracle."""
 import ctypes as C
 import inspect
 import os
@@ -16,8 +17,8 @@ from test_episode_rows import HostStats, _same_bits, _snapshot, _state_equal, _u
 from test_policy_explore import DOCUMENTED as EXPLORE_DOCUMENTED
 from test_policy_explore import _compare, _envs_equal, _forms_of
 from test_policy_rollout import DOCUMENTED as GREEDY_DOCUMENTED
-from test_policy_rollout import WANT, _batch, _c_policy, _n_out, _policy
-from test_policy_sample import CASES, LAUNCHES, N
+from test_policy_rollout import WANT, _batch, _c_policy, _n_out, _policy, _trace_end, _trace_launch, _trace_start
+from test_policy_sample import CASES, LAUNCHES, LENGTH, N, T
 from test_policy_sample import DOCUMENTED as SAMPLE_DOCUMENTED
 from test_policy_sample import _envs, _nan_rows, _rows, _sampling, _spread_policy, _twin_steps
 
@@ -314,39 +315,44 @@ def _value_refs(head, policy, before, ref):
     return values, finals
 
 
-def _fused_equals_stepped(device, arch, series, n_hidden, obs_dtype=F64, P=1, temperature=1.0, vacuous=True):
+def _fused_equals_stepped(device, arch, series, n_hidden, obs_dtype=F64, P=1, temperature=1.0, vacuous=True, n=N, length=LENGTH,
+                          t=T, launches=LAUNCHES, trace=None):
     """The critic launch, in launches of 1, 7 and 64 steps on one env, == its stepped twin after every launch -- everything the
     sampling test compares, and the three value outputs against ``head.value`` on the twin's rows; a third env takes the same
     launches WITHOUT a critic and is left with the same bits; then one more single step.  ``vacuous``: the conditions on the test
-    itself, from the stepped twin alone."""
+    itself, from the stepped twin alone.  ``n``, ``length``, ``t``, ``launches``: another batch size, episode length, series
+    length and other launches; ``trace``: a dict that receives what test_policy_rollout._trace_launch records."""
     from pymgrid_amd import _lib
     old = _lib.get_tunable("grid_major_copy")[0]
     if series == "gather":
         _lib.set_tunable("grid_major_copy", 0)
     try:
-        fused, twin, plain = _envs(device, arch, series, obs_dtype, 3)
+        fused, twin, plain = _envs(device, arch, series, obs_dtype, 3, n=n, length=length, t=t)
         assert torch.equal(fused.obs0, twin.obs0) and fused.obs0.dtype == obs_dtype
         D, n_out = fused.env.engine.obs_dim, _n_out(fused, True)
         index = None
         if P > 1:
-            index = torch.randint(-1, P + 1, (N,), generator=torch.Generator().manual_seed(11)).to(torch.int32)
+            index = torch.randint(-1, P + 1, (n,), generator=torch.Generator().manual_seed(11)).to(torch.int32)
             assert int(index.min()) == -1 and int(index.max()) == P
         policy = _spread_policy(7, twin.obs0, n_hidden, n_out, P=P, index=index)
         head = _head(9, policy)
         sa = _sampling(seed=23, temperature=temperature)
-        hs = HostStats(N, device)
+        hs = HostStats(n, device)
         obs, seen = twin.obs0, []
-        for K in LAUNCHES:
-            out = fused.rollout_policy(policy, K, sampling=sa, probs=True, critic=head, values=True, out=_nan_out(K, N, D, obs_dtype, device),
+        _trace_start(trace, fused, True)
+        for K in launches:
+            out = fused.rollout_policy(policy, K, sampling=sa, probs=True, critic=head, values=True, out=_nan_out(K, n, D, obs_dtype, device),
                                        **WANT)
             before = obs
-            ref, obs = _twin_steps(twin, policy, sa, obs, K, hs, seen)
+            walked = [] if trace is not None else None
+            ref, obs = _twin_steps(twin, policy, sa, obs, K, hs, seen, walked)
+            _trace_launch(trace, walked, out, ref)
             got = {name: out.pop(name) for name in VALUES}
             _compare(out, ref, K)
             d = out["done"]
             assert bool(torch.isnan(out["final_obs"][~d]).all()) and not bool(torch.isnan(out["final_obs"][d]).any()), K
             values, finals = _value_refs(head, policy, before, ref)
-            assert got["values"].dtype == F64 and got["values"].shape == (K, N) and got["last_value"].shape == (N,)
+            assert got["values"].dtype == F64 and got["values"].shape == (K, n) and got["last_value"].shape == (n,)
             assert torch.equal(got["values"], values), K
             assert torch.equal(got["final_values"][d], finals[d]), K
             assert bool(torch.isnan(got["final_values"][~d]).all()) and not bool(torch.isnan(got["final_values"][d]).any()), K
@@ -354,7 +360,7 @@ def _fused_equals_stepped(device, arch, series, n_hidden, obs_dtype=F64, P=1, te
             _envs_equal(fused, twin, K)
             hs.check(fused.episode_stats)
             # the critic changes nothing else: the sampling launch without one
-            same = plain.rollout_policy(policy, K, sampling=sa, probs=True, out=_nan_rows(K, N, D, obs_dtype, device), **WANT)
+            same = plain.rollout_policy(policy, K, sampling=sa, probs=True, out=_nan_rows(K, n, D, obs_dtype, device), **WANT)
             _compare(same, out, K)
             _envs_equal(plain, fused, K)
             for name in fused.episode_stats:
@@ -366,6 +372,9 @@ def _fused_equals_stepped(device, arch, series, n_hidden, obs_dtype=F64, P=1, te
                     for k in range(K):
                         if bool(d[k].any()):
                             assert bool((finals[k][d[k]] != first[k][d[k]]).any()), k
+        _trace_end(trace, fused)
+        if trace is not None:
+            trace["greedy"] = torch.stack([g for _, g in seen])
         if vacuous:                                                    # the stepped twin ALONE says whether the test can pass vacuously
             taken, greedy = torch.stack([a for a, _ in seen]), torch.stack([g for _, g in seen])
             share = float((taken != greedy).double().mean())

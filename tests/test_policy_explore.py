@@ -2,7 +2,8 @@
 mgx_step_k_policy_explore_episodes, ``exploration=`` of StepEngine.rollout_policy_episodes / step_k_policy_episodes and
 PerGridWindowEnv.rollout_policy / step_k_policy): the rule of ``mgx_exploration`` (include/mgx.h) on the host
 (``MLPPolicy.act(obs, exploration, counter)``) and K steps in one launch == a twin stepped K times with it, bit for bit
-(torch.equal: the draws are integer Philox words, the noise a sum of their fields, so there is no tolerance)."""
+(torch.equal: the draws are integer Philox words, the noise a sum of their fields, so there is no tolerance).  The forms of the kernels these cases leave out -- all ten layouts x the three row sources -- run in
+tests/test_layout_matrix_policy.py, which also replays the launches on the CPU oracle."""
 import ctypes as C
 import math
 import os
@@ -14,7 +15,7 @@ import torch
 
 from layouts import LAYOUTS
 from test_episode_rows import HostStats, _same_bits, _snapshot, _state_equal, _untouched
-from test_policy_rollout import WANT, _c_policy, _envs, _launch, _n_out, _policy
+from test_policy_rollout import WANT, _c_policy, _envs, _launch, _n_out, _policy, _trace_end, _trace_launch, _trace_start
 
 F64, F32 = torch.float64, torch.float32
 LAUNCHES = (1, 7, 64)
@@ -186,12 +187,14 @@ def test_the_exploring_kernels_use_what_design_md_says():
 
 
 # ---- GPU: fused == stepped ---------------------------------------------------------------------------------------------------------
-def _twin_steps(twin, policy, ex, obs, K, hs, seen):
+def _twin_steps(twin, policy, ex, obs, K, hs, seen, walked=None):
     """K times ``a = policy.act(obs, ex, counter); obs, r, done, info = twin.step(a)``, the counter read from the env before the
-    step; ``seen`` receives the greedy action beside every action taken."""
+    step; ``seen`` receives the greedy action beside every action taken, ``walked`` every grid's series row before each step."""
     rows = {k: [] for k in ("reward", "done", "soc_trace", "status_trace", "actions", "obs", "final_obs")}
     cols = twin.env.batch.cols
     for _ in range(K):
+        if walked is not None:
+            walked.append(twin.env.current_steps.clone())
         t = twin.env.current_step
         assert isinstance(t, int)
         a = policy.act(obs, ex, t)
@@ -237,10 +240,11 @@ def _explored_mask(ex, t, n, device, scale=None):
 
 
 def _fused_equals_stepped(device, discrete, arch, series, length, n_hidden, n, obs_dtype=F64, launches=LAUNCHES, vacuous=False,
-                          third=False, split=None):
+                          third=False, split=None, trace=None):
     """The exploring launch, in launches of uneven size on one env, == its stepped twin after every launch; then one more single
     step.  ``vacuous``: the conditions on the test itself, from the stepped twin alone.  ``third``: a third env replays the returned
-    actions through the open-loop rollout / step_k.  ``split``: a third env takes every launch in pieces of these sizes."""
+    actions through the open-loop rollout / step_k.  ``split``: a third env takes every launch in pieces of these sizes.
+    ``trace``: a dict that receives what test_policy_rollout._trace_launch records, and per step the greedy action (``greedy``)."""
     from pymgrid_amd import _lib
     old = _lib.get_tunable("grid_major_copy")[0]
     if series == "gather":
@@ -253,10 +257,13 @@ def _fused_equals_stepped(device, discrete, arch, series, length, n_hidden, n, o
         ex = _explore(seed=23, epsilon=EPSILON, sigma=SIGMA)           # (the auto-reset seed of _envs: the tag separates the streams)
         hs = HostStats(n, device)
         obs, seen, restarts = twin.obs0, [], 0
+        _trace_start(trace, fused, discrete)
         for K in launches:
             bufs = dict(final_obs=torch.full((K, n, D), float("nan"), dtype=obs_dtype, device=device))
             out = _launch(fused, policy, K, discrete, out=bufs, exploration=ex, **WANT)
-            ref, obs = _twin_steps(twin, policy, ex, obs, K, hs, seen)
+            walked = [] if trace is not None else None
+            ref, obs = _twin_steps(twin, policy, ex, obs, K, hs, seen, walked)
+            _trace_launch(trace, walked, out, ref)
             _compare(out, ref, K)
             d = out["done"]
             assert bool(torch.isnan(out["final_obs"][~d]).all()) and not bool(torch.isnan(out["final_obs"][d]).any()), K
@@ -278,6 +285,9 @@ def _fused_equals_stepped(device, discrete, arch, series, length, n_hidden, n, o
                 _launch(envs[2], policy, K, discrete, exploration=ex)
             restarts += int(ref["done"].sum())
         assert int(fused.episode_stats["episodes"].sum()) == restarts
+        _trace_end(trace, fused)
+        if trace is not None:
+            trace["greedy"] = torch.stack([g for _, _, g in seen])
         if vacuous:                                                    # the stepped twin ALONE says whether the test can pass vacuously
             if length == 9:
                 assert restarts > n, restarts

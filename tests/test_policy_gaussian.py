@@ -3,7 +3,8 @@
 steps in one launch == a twin stepped K times with ``policy.act(obs, gs, counter, return_logp=True, return_raw=True)``, bit for bit
 (torch.equal: log, sine, cosine and the square root are fixed sequences of IEEE operations on both sides, the draws integer Philox
 words, the division correctly rounded -- so there is no tolerance).  Small on purpose: 193 grids (three waves and a partial one),
-five-step episodes so that grids restart inside a launch, 12 steps."""
+five-step episodes so that grids restart inside a launch, 12 steps.  The forms of the kernels these cases leave out -- all ten layouts x the three row sources -- run in
+tests/test_layout_matrix_policy.py, which also replays the launches on the CPU oracle."""
 import ctypes as C
 import os
 
@@ -13,7 +14,7 @@ import torch
 
 from test_episode_rows import HostStats, _same_bits, _snapshot, _state_equal, _untouched
 from test_policy_explore import _compare, _envs_equal, _forms_of
-from test_policy_rollout import WANT, _c_policy, _envs, _policy
+from test_policy_rollout import WANT, _c_policy, _envs, _policy, _trace_end, _trace_launch, _trace_start
 
 F64, F32 = torch.float64, torch.float32
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -44,12 +45,15 @@ def _nan(K, n, D, dtype, device, values=False):
     return out
 
 
-def _twin_steps(twin, policy, gs, obs, K, hs):
+def _twin_steps(twin, policy, gs, obs, K, hs, walked=None):
     """K times ``u, logp, raw = policy.act(obs, gs, counter, ...); obs, r, done, info = twin.step(u)``, the counter read from the env
-    before the step: what the fused call offers, per step."""
+    before the step: what the fused call offers, per step.  ``walked``: a list that receives every grid's series row before each
+    step."""
     rows = {k: [] for k in ("reward", "done", "soc_trace", "status_trace", "actions", "raw_actions", "logp", "obs", "final_obs")}
     cols = twin.env.batch.cols
     for _ in range(K):
+        if walked is not None:
+            walked.append(twin.env.current_steps.clone())
         t = twin.env.current_step
         assert isinstance(t, int)
         u, logp, raw = policy.act(obs, gs, counter=t, return_logp=True, return_raw=True)
@@ -83,13 +87,13 @@ class _gather:
         _lib.set_tunable("grid_major_copy", self.old)
 
 
-def _population(device, fused, n_hidden, P):
+def _population(device, fused, n_hidden, P, n=N, seed=7):
     D, A = fused.env.engine.obs_dim, fused.env.engine.action_dim
     index = None
     if P > 1:
-        index = torch.randint(-1, P + 1, (N,), generator=torch.Generator().manual_seed(11)).to(torch.int32)
+        index = torch.randint(-1, P + 1, (n,), generator=torch.Generator().manual_seed(11)).to(torch.int32)
         assert int(index.min()) == -1 and int(index.max()) == P
-    return _policy(7, D, n_hidden, A, "continuous", P=P, index=index)
+    return _policy(seed, D, n_hidden, A, "continuous", P=P, index=index)
 
 
 # (layout flags: 2 battery, A = 1; 1 genset, A = 2; 6 battery + grid, A = 2; 3 genset + battery, A = 3; 5 genset + grid, A = 3;
@@ -105,28 +109,53 @@ def test_the_cases_cover_what_they_should():
     assert {c[2] for c in CASES} == {0, 16} and {c[3] for c in CASES} == {F64, F32} and {c[4] for c in CASES} == {1, 3}
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("flags,series,n_hidden,obs_dtype,P", CASES)
-def test_fused_equals_stepped(flags, series, n_hidden, obs_dtype, P, device):
+def _fused_equals_stepped(device, flags, series, n_hidden, obs_dtype, P, critic=False, n=N, length=LENGTH, steps=K, trace=None, seed=7,
+                          sigma=SIGMA):
+    """One Gaussian launch of ``steps`` steps == its stepped twin: everything the greedy test compares, the raw draws and the
+    log-probabilities; ``critic``: the launch with a value head (the other kernel form) -- the three value outputs against
+    ``head.value`` on the twin's rows, everything else as without one; then one more single step.  ``length`` None: own lengths
+    (then only some grids restart).  ``trace``: a dict that receives what test_policy_rollout._trace_launch records; ``seed``: of
+    the policy's parameters."""
+    K = steps
     with _gather(series):
-        fused, twin = _envs(device, False, flags, series, LENGTH, obs_dtype, N)
+        fused, twin = _envs(device, False, flags, series, length, obs_dtype, n)
         e = fused.env.engine
         D, A = e.obs_dim, e.action_dim
-        policy, gs = _population(device, fused, n_hidden, P), _gs()
-        hs = HostStats(N, device)
-        out = fused.step_k_policy(policy, K, sampling=gs, out=_nan(K, N, D, obs_dtype, device), **MORE, **WANT)
-        ref, obs = _twin_steps(twin, policy, gs, twin.obs0, K, hs)
-        assert out["logp"].shape == (K, N) and out["raw_actions"].shape == (K, N, A) and out["logp"].dtype == F64
+        policy, gs = _population(device, fused, n_hidden, P, n, seed), _gs(sigma=sigma)
+        head = _head(9, policy) if critic else None
+        hs = HostStats(n, device)
+        _trace_start(trace, fused, False)
+        more = dict(critic=head, values=True) if critic else {}
+        out = fused.step_k_policy(policy, K, sampling=gs, out=_nan(K, n, D, obs_dtype, device, values=critic), **more, **MORE, **WANT)
+        walked = [] if trace is not None else None
+        ref, obs = _twin_steps(twin, policy, gs, twin.obs0, K, hs, walked)
+        _trace_launch(trace, walked, out, ref)
+        _trace_end(trace, fused)
+        if trace is not None:
+            trace["raw"] = ref["raw_actions"]
+        assert out["logp"].shape == (K, n) and out["raw_actions"].shape == (K, n, A) and out["logp"].dtype == F64
+        d = ref["done"]
+        if critic:
+            got = {name: out.pop(name) for name in VALUES}
+            chosen_on = [twin.obs0] + list(ref["obs"][:-1])
+            assert got["values"].shape == (K, n) and got["last_value"].shape == (n,)
+            assert torch.equal(got["values"], torch.stack([head.value(policy, o) for o in chosen_on]))
+            finals = torch.stack([head.value(policy, o) for o in ref["final_obs"]])
+            assert torch.equal(got["final_values"][d], finals[d])
+            assert bool(torch.isnan(got["final_values"][~d]).all()) and not bool(torch.isnan(got["final_values"][d]).any())
+            assert torch.equal(got["last_value"], head.value(policy, ref["obs"][-1]))
         _compare(out, ref, K)
         d = out["done"]
-        assert int(d.sum()) >= N                                          # every grid restarts inside the launch, most of them twice
+        if length is not None and length < K:
+            assert int(d.sum()) >= n                                      # every grid restarts inside the launch, most of them twice
         assert bool(torch.isnan(out["final_obs"][~d]).all()) and not bool(torch.isnan(out["final_obs"][d]).any())
         _envs_equal(fused, twin, K)
         hs.check(fused.episode_stats)
         # the conditions on the test itself, from the stepped twin alone: the draws move the controls, both edges of the clip occur
         raw, u = ref["raw_actions"], ref["actions"]
-        assert bool(torch.isfinite(ref["logp"]).all()) and ref["logp"].unique().numel() > K * N // 2
-        assert bool((raw != u).any()) and bool((u == 0).any()) and bool(((u > 0) & (u < 1)).any())
+        if A:
+            assert bool(torch.isfinite(ref["logp"]).all()) and ref["logp"].unique().numel() > K * n // 2
+            assert bool((raw != u).any()) and bool((u == 0).any()) and bool(((u > 0) & (u < 1)).any())
         # the env stands where the twin stands: one more single step
         a = policy.act(obs, gs, counter=twin.env.current_step)
         assert torch.equal(a, policy.act(out["obs"][-1], gs, counter=fused.env.current_step))
@@ -134,6 +163,12 @@ def test_fused_equals_stepped(flags, series, n_hidden, obs_dtype, P, device):
         assert torch.equal(o1, o2) and torch.equal(r1, r2) and torch.equal(d1, d2)
         _state_equal(fused.env, twin.env)
         fused.env.close(); twin.env.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("flags,series,n_hidden,obs_dtype,P", CASES)
+def test_fused_equals_stepped(flags, series, n_hidden, obs_dtype, P, device):
+    _fused_equals_stepped(device, flags, series, n_hidden, obs_dtype, P)
 
 
 @pytest.mark.gpu

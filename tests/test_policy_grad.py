@@ -2,7 +2,8 @@
 the rule of include/mgx.h.  One live sample is exact (``==``): a product added to zeros.  Many samples are held to the any-order
 summation bound against the exactly summed per-sample terms (math.fsum) -- the sum goes through the fp64 MFMA, whose inner order
 and rounding are the hardware's -- and must be identical from run to run.  End to end: on the data of a sampling launch with a
-critic, restarts inside, the ratio is exactly 1.0 and with ``returns = values`` the critic's gradient exactly 0.0."""
+critic, restarts inside, the ratio is exactly 1.0 and with ``returns = values`` the critic's gradient exactly 0.0.  WIDTH_CASES runs
+both comparisons once per compiled form of the kernel: every row width 1 .. 12, with and without a critic."""
 import ctypes as C
 import math
 
@@ -17,6 +18,11 @@ from test_policy_sample import _sampling, _spread_policy
 F64, F32 = torch.float64, torch.float32
 NAMES = ("W1", "b1", "W2", "b2", "w", "b")
 U = 2.0 ** -53
+ONE_SAMPLE_CASES = tuple((nh, n_in, n_out, critic) for critic in (True, False) for n_out in (12, 4) for nh, n_in in ((16, 10), (5, 7), (0, 12)))
+MANY_SAMPLES_CASES = ((3, 16, 10, 12), (17, 16, 10, 12), (17, 40, 9, 4), (3, 0, 12, 12))
+# (n_in, critic, n_hidden, n_out): every form policy_grad_kernel<D, CRITIC, softmax> is compiled in -- the row widths D = 1 .. 12 (the
+# small ones are the rows of the small layouts), with and without a critic; hidden units and outputs rotate over the widths
+WIDTH_CASES = tuple((D, critic, (16, 5, 0)[D % 3], (12, 4)[D % 2]) for D in range(1, 13) for critic in (True, False))
 
 
 def _to(c, device):
@@ -51,9 +57,7 @@ def _assert_within_bound(dev, host):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("critic", [True, False])
-@pytest.mark.parametrize("n_out", [12, 4])
-@pytest.mark.parametrize("n_hidden,n_in", [(16, 10), (5, 7), (0, 12)])
+@pytest.mark.parametrize("n_hidden,n_in,n_out,critic", ONE_SAMPLE_CASES)
 def test_one_sample_is_exact(device, n_hidden, n_in, n_out, critic):
     from pymgrid_amd import ppo_grad, ppo_grad_host
     c = make_case(1, 1, n_in, n_hidden, n_out, critic=critic, seed=100 + n_hidden + n_out)
@@ -68,11 +72,24 @@ def test_one_sample_is_exact(device, n_hidden, n_in, n_out, critic):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("K,n_hidden,n_in,n_out", [(3, 16, 10, 12), (17, 16, 10, 12), (17, 40, 9, 4), (3, 0, 12, 12)])
-def test_many_samples_within_the_summation_bound(device, K, n_hidden, n_in, n_out):
+@pytest.mark.parametrize("n_in,critic,n_hidden,n_out", WIDTH_CASES)
+def test_every_row_width_one_sample_is_exact(device, n_in, critic, n_hidden, n_out):
+    test_one_sample_is_exact(device, n_hidden, n_in, n_out, critic)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n_in,critic,n_hidden,n_out", WIDTH_CASES)
+def test_every_row_width_many_samples_within_the_summation_bound(device, n_in, critic, n_hidden, n_out):
+    """K = 3, N = 130: three waves, the last with two live lanes."""
+    test_many_samples_within_the_summation_bound(device, 3, n_hidden, n_in, n_out, critic)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("K,n_hidden,n_in,n_out", MANY_SAMPLES_CASES)
+def test_many_samples_within_the_summation_bound(device, K, n_hidden, n_in, n_out, critic=True):
     """N = 130: three waves, the last with two live lanes; K = 17 crosses chunks of k, the last one partial."""
     from pymgrid_amd import ppo_grad, ppo_grad_host
-    c = make_case(K, 130, n_in, n_hidden, n_out, seed=K + n_hidden)
+    c = make_case(K, 130, n_in, n_hidden, n_out, critic=critic, seed=K + n_hidden)
     kw = dict(clip=0.2, vf_coef=0.5, ent_coef=0.01)
     host = ppo_grad_host(**c, **kw, per_sample=True, ratio=True)
     assert host["terms"].shape[0] == K * 130 and 0.0 < float(host["stats"][3]) < 1.0

@@ -2,7 +2,8 @@
 ``ppo_grad_gaussian_host``, the host statement of the rule of include/mgx.h.  One live sample is exact (``==``): a product added to
 zeros.  Many samples are held to the any-order summation bound against the exactly summed per-sample terms (math.fsum) and must be
 identical from run to run.  End to end: on the data of a Gaussian launch with a critic, restarts inside, the ratio equals the host's
-bit for bit and stays inside the derived bound, and with ``returns = values`` the critic's gradient is exactly 0.0."""
+bit for bit and stays inside the derived bound, and with ``returns = values`` the critic's gradient is exactly 0.0.  WIDTH_CASES runs
+the first two once per compiled form of the kernel: every row width 1 .. 12, with and without a critic."""
 import ctypes as C
 
 import pytest
@@ -22,10 +23,29 @@ def _cpu(c):
     return {k: (v.cpu() if torch.is_tensor(v) else v) for k, v in c.items()}
 
 
+ONE_SAMPLE_CASES = tuple((nh, n_in, A, critic) for critic in (True, False) for A in (4, 3, 1) for nh, n_in in ((16, 10), (5, 7), (0, 12)))
+MANY_SAMPLES_CASES = ((3, 16, 10, 4, False), (17, 16, 10, 4, True), (17, 40, 9, 3, False), (3, 0, 12, 3, True), (17, 0, 12, 4, False))
+# (n_in, critic, n_hidden, A): every form policy_grad_kernel<D, CRITIC, Gaussian> is compiled in -- the row widths D = 1 .. 12, with and
+# without a critic; hidden units and the number of controls rotate over the widths (in this order of A every one-sample case is live
+# on the host; with (4, 3, 2, 1) the sample of D = 4 leaves its five hidden units dead and W2's gradient zero)
+WIDTH_CASES = tuple((D, critic, (16, 5, 0)[D % 3], (3, 4, 1, 2)[D % 4]) for D in range(1, 13) for critic in (True, False))
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize("critic", [True, False])
-@pytest.mark.parametrize("A", [4, 3, 1])
-@pytest.mark.parametrize("n_hidden,n_in", [(16, 10), (5, 7), (0, 12)])
+@pytest.mark.parametrize("n_in,critic,n_hidden,A", WIDTH_CASES)
+def test_every_row_width_one_sample_is_exact(device, n_in, critic, n_hidden, A):
+    test_one_sample_is_exact(device, n_hidden, n_in, A, critic)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n_in,critic,n_hidden,A", WIDTH_CASES)
+def test_every_row_width_many_samples_within_the_summation_bound(device, n_in, critic, n_hidden, A):
+    """K = 3, N = 130: three waves, the last with two live lanes."""
+    test_many_samples_within_the_summation_bound(device, 3, n_hidden, n_in, A, False, critic)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n_hidden,n_in,A,critic", ONE_SAMPLE_CASES)
 def test_one_sample_is_exact(device, n_hidden, n_in, A, critic):
     from pymgrid_amd import ppo_grad_gaussian, ppo_grad_gaussian_host
     c = make_case_gaussian(1, 1, n_in, n_hidden, A, critic=critic, seed=100 + n_hidden + A)
@@ -44,16 +64,15 @@ def test_one_sample_is_exact(device, n_hidden, n_in, A, critic):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("K,n_hidden,n_in,A,dead", [(3, 16, 10, 4, False), (17, 16, 10, 4, True), (17, 40, 9, 3, False), (3, 0, 12, 3, True),
-                                                    (17, 0, 12, 4, False)])
-def test_many_samples_within_the_summation_bound(device, K, n_hidden, n_in, A, dead):
+@pytest.mark.parametrize("K,n_hidden,n_in,A,dead", MANY_SAMPLES_CASES)
+def test_many_samples_within_the_summation_bound(device, K, n_hidden, n_in, A, dead, critic=True):
     """N = 130: three waves, the last with two live lanes; K = 17 crosses chunks of k, the last one partial.  ``dead``: a column with
     sigma 0 and a scale ladder with zeros (grids without a live column)."""
     from pymgrid_amd import ppo_grad_gaussian, ppo_grad_gaussian_host
     N = 130
     sigma = (0.3, 0.0, 0.2, 0.05) if dead else (0.3, 0.1, 0.2, 0.05)
     scale = (torch.arange(N, dtype=F64) % 5) * 0.5 if dead else None                        # 0.0, 0.5, .. 2.0: every fifth grid is off
-    c = make_case_gaussian(K, N, n_in, n_hidden, A, seed=K + n_hidden, sigma=sigma, scale=scale)
+    c = make_case_gaussian(K, N, n_in, n_hidden, A, critic=critic, seed=K + n_hidden, sigma=sigma, scale=scale)
     host = ppo_grad_gaussian_host(**c, **KW, per_sample=True, ratio=True)
     assert host["terms"].shape[0] == K * N and 0.0 < float(host["stats"][3]) < 1.0
     if dead:

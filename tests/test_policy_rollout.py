@@ -3,7 +3,8 @@ mgx_step_k_policy_episodes, StepEngine.rollout_policy_episodes / step_k_policy_e
 step_k_policy): K steps in one launch == a twin stepped K times with ``policy.act(obs)`` on the observation its last step
 returned -- rewards, done, traces, the actions taken, the rows, the rows before the restarts, the episode arrays, the state and
 the statistics, bit for bit (torch.equal; MLPPolicy.act performs the kernel's IEEE operations in the kernel's order, so there is no
-tolerance)."""
+tolerance).  The forms of the kernels these cases leave out -- all ten layouts x the three row sources -- run in
+tests/test_layout_matrix_policy.py, which also replays the launches on the CPU oracle."""
 import ctypes as C
 
 import numpy as np
@@ -60,11 +61,14 @@ def _n_out(pe, discrete):
     return pe.env.action_space.n if discrete else pe.env.engine.action_dim
 
 
-def _twin_steps(twin, policy, obs, K, hs):
-    """K times ``a = policy.act(obs); obs, r, done, info = twin.step(a)``: what the fused call offers, per step."""
+def _twin_steps(twin, policy, obs, K, hs, walked=None):
+    """K times ``a = policy.act(obs); obs, r, done, info = twin.step(a)``: what the fused call offers, per step.  ``walked``: a list
+    that receives every grid's series row before each step."""
     rows = {k: [] for k in ("reward", "done", "soc_trace", "status_trace", "actions", "obs", "final_obs")}
     cols = twin.env.batch.cols
     for _ in range(K):
+        if walked is not None:
+            walked.append(twin.env.current_steps.clone())
         a = policy.act(obs)
         obs, r, d, info = twin.step(a) if a.dtype == torch.int32 else twin.step(a, normalized=True)
         rows["actions"].append(a.to(torch.uint8) if a.dtype == torch.int32 else a.clone())
@@ -86,11 +90,34 @@ def _launch(pe, policy, K, discrete, **kw):
 WANT = dict(reward=True, done=True, soc_trace=True, status_trace=True, actions=True, observations=True, final_observations=True)
 
 
+def _trace_start(trace, pe, discrete):
+    """What an independent replay of a closed-loop launch starts from (``trace``: a dict, or None): the columns of the batch after
+    the reset, on the host, and the priority-list table of a discrete env."""
+    if trace is not None:
+        trace["cols"] = pe.env.batch.numpy_columns()
+        trace["table"] = pe.env._table if discrete else None
+
+
+def _trace_launch(trace, walked, out, ref):
+    """One launch: the series rows the twin walked, the actions the launch reports and its rewards; of the stepped twin ALONE (for
+    the conditions on a test itself) the done flags and the actions taken."""
+    if trace is not None:
+        trace.setdefault("launches", []).append(dict(rows=torch.stack(walked), controls=out["actions"].contiguous(), reward=out["reward"],
+                                                     done=ref["done"], taken=ref["actions"]))
+
+
+def _trace_end(trace, pe):
+    if trace is not None:
+        cols = pe.env.batch.cols
+        trace["state"] = {name: cols[name].clone() for name in ("charge", "soc", "gen_status") if name in cols}
+
+
 def _fused_equals_stepped(device, discrete, arch, series, length, n_hidden, n, obs_dtype=F64, launches=LAUNCHES, tie=False,
-                          closed=False, third=False):
+                          closed=False, third=False, trace=None, seed=7):
     """The closed-loop launch, in launches of uneven size on one env, == its stepped twin after every launch; then the next single
     step.  ``closed``: the conditions on the test itself (restarts, the ids / controls really follow the observations).
-    ``third``: a third env replays the returned actions through the open-loop rollout / step_k."""
+    ``third``: a third env replays the returned actions through the open-loop rollout / step_k.  ``trace``: a dict that receives
+    what an independent replay needs (_trace_start / _trace_launch / _trace_end); ``seed``: of the policy's parameters."""
     from pymgrid_amd import _lib
     old = _lib.get_tunable("grid_major_copy")[0]
     if series == "gather":
@@ -101,17 +128,20 @@ def _fused_equals_stepped(device, discrete, arch, series, length, n_hidden, n, o
         assert torch.equal(fused.obs0, twin.obs0) and fused.obs0.dtype == obs_dtype
         D = fused.env.engine.obs_dim
         head = "discrete" if discrete else "continuous"
-        policy = _policy(7, D, n_hidden, _n_out(fused, discrete), head)
+        policy = _policy(seed, D, n_hidden, _n_out(fused, discrete), head)
+        _trace_start(trace, fused, discrete)
         if tie:                                                # the tie on the output the first observations favour: it really decides steps
             fav = int(torch.bincount(policy.act(twin.obs0).long(), minlength=policy.n_out).argmax())
-            policy = _policy(7, D, n_hidden, policy.n_out, head, tie=fav)
+            policy = _policy(seed, D, n_hidden, policy.n_out, head, tie=fav)
         hs = HostStats(n, device)
         obs = twin.obs0
         restarts, taken, moved = 0, [], False
         for K in launches:
             bufs = dict(final_obs=torch.full((K, n, D), float("nan"), dtype=obs_dtype, device=device))
             out = _launch(fused, policy, K, discrete, out=bufs, **WANT)
-            ref, obs = _twin_steps(twin, policy, obs, K, hs)
+            walked = [] if trace is not None else None
+            ref, obs = _twin_steps(twin, policy, obs, K, hs, walked)
+            _trace_launch(trace, walked, out, ref)
             assert set(out) == set(ref), (sorted(out), sorted(ref))
             assert out["final_obs"] is bufs["final_obs"] and out["obs"].dtype == obs_dtype
             for name in out:
@@ -148,6 +178,7 @@ def _fused_equals_stepped(device, discrete, arch, series, length, n_hidden, n, o
             if K > 1:
                 moved |= bool((ref["actions"][1:] != ref["actions"][:-1]).any())
         assert int(fused.episode_stats["episodes"].sum()) == restarts
+        _trace_end(trace, fused)
         if closed:
             assert restarts > n, restarts
             assert moved                                       # a grid's action changes between two steps of one launch

@@ -2,7 +2,8 @@
 StepEngine.rollout_policy_episodes and PerGridWindowEnv.rollout_policy): the rule of ``mgx_sampling`` (include/mgx.h) on the host
 (``policy_exp``, ``MLPPolicy.act(obs, sampling, counter, return_prob=True)``) and K steps in one launch == a twin stepped K times
 with it, bit for bit (torch.equal: exp is a fixed sequence of IEEE operations on both sides, the draws are integer Philox words, the
-probability one IEEE division, so there is no tolerance)."""
+probability one IEEE division, so there is no tolerance).  The forms of the kernels these cases leave out -- all ten layouts x the three row sources -- run in
+tests/test_layout_matrix_policy.py, which also replays the launches on the CPU oracle."""
 import ctypes as C
 import math
 import os
@@ -16,7 +17,7 @@ from test_episode_rows import HostStats, _same_bits, _snapshot, _state_equal, _u
 from test_policy_explore import DOCUMENTED as EXPLORE_DOCUMENTED
 from test_policy_explore import _compare, _envs_equal, _forms_of
 from test_policy_rollout import DOCUMENTED as GREEDY_DOCUMENTED
-from test_policy_rollout import WANT, _batch, _c_policy, _n_out, _policy
+from test_policy_rollout import WANT, _batch, _c_policy, _n_out, _policy, _trace_end, _trace_launch, _trace_start
 
 F64, F32 = torch.float64, torch.float32
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -321,12 +322,12 @@ def test_the_sampling_kernel_uses_what_design_md_says():
 
 
 # ---- GPU: fused == stepped ---------------------------------------------------------------------------------------------------------
-def _envs(device, arch, series, obs_dtype, count, twin=1, n=N):
+def _envs(device, arch, series, obs_dtype, count, twin=1, n=N, length=LENGTH, t=T):
     """``count`` discrete PerGridWindowEnv of the same batch, seed and first draw; number ``twin`` (the stepped one; None: none)
     reports the rows before the restarts."""
     from pymgrid_amd.hetero import PerGridWindowEnv
-    kw = dict(trajectory_length=LENGTH, discrete=True, auto_reset=True, seed=23, obs_dtype=obs_dtype)
-    envs = [PerGridWindowEnv(_batch(device, arch, series, n, t=T), final_observation=(q == twin), **kw) for q in range(count)]
+    kw = dict(trajectory_length=length, discrete=True, auto_reset=True, seed=23, obs_dtype=obs_dtype)
+    envs = [PerGridWindowEnv(_batch(device, arch, series, n, t=t), final_observation=(q == twin), **kw) for q in range(count)]
     for e in envs:
         torch.manual_seed(41)                   # the same first draw
         e.obs0 = e.reset()
@@ -351,12 +352,14 @@ def _spread_policy(seed, obs0, n_hidden, n_out, P=1, index=None):
     return MLPPolicy(raw.W1, raw.b1, raw.W2 / f, raw.b2 / f, policy_index=raw.policy_index, head="discrete")
 
 
-def _twin_steps(twin, policy, sa, obs, K, hs, seen=None):
+def _twin_steps(twin, policy, sa, obs, K, hs, seen=None, walked=None):
     """K times ``a, p = policy.act(obs, sa, counter, return_prob=True); obs, r, done, info = twin.step(a)``, the counter read from the
-    env before the step; ``seen`` receives the greedy id beside every id taken."""
+    env before the step; ``seen`` receives the greedy id beside every id taken, ``walked`` every grid's series row before each step."""
     rows = {k: [] for k in ("reward", "done", "soc_trace", "status_trace", "actions", "probs", "obs", "final_obs")}
     cols = twin.env.batch.cols
     for _ in range(K):
+        if walked is not None:
+            walked.append(twin.env.current_steps.clone())
         t = twin.env.current_step
         assert isinstance(t, int)
         a, p = policy.act(obs, sa, counter=t, return_prob=True)
@@ -379,29 +382,34 @@ def _nan_rows(K, n, D, dtype, device):
     return dict(final_obs=torch.full((K, n, D), float("nan"), dtype=dtype, device=device))
 
 
-def _fused_equals_stepped(device, arch, series, n_hidden, obs_dtype=F64, P=1, temperature=1.0, vacuous=True):
+def _fused_equals_stepped(device, arch, series, n_hidden, obs_dtype=F64, P=1, temperature=1.0, vacuous=True, n=N, length=LENGTH,
+                          t=T, launches=LAUNCHES, trace=None):
     """The sampling launch, in launches of 1, 7 and 64 steps on one env, == its stepped twin after every launch -- traces, ids,
     probs, rows, state, episode arrays, statistics; then one more single step.  ``vacuous``: the conditions on the test itself,
-    from the stepped twin alone."""
+    from the stepped twin alone.  ``n``, ``length``, ``t``, ``launches``: another batch size, episode length, series length and
+    other launches; ``trace``: a dict that receives what test_policy_rollout._trace_launch records."""
     from pymgrid_amd import _lib
     old = _lib.get_tunable("grid_major_copy")[0]
     if series == "gather":
         _lib.set_tunable("grid_major_copy", 0)
     try:
-        fused, twin = _envs(device, arch, series, obs_dtype, 2)
+        fused, twin = _envs(device, arch, series, obs_dtype, 2, n=n, length=length, t=t)
         assert torch.equal(fused.obs0, twin.obs0) and fused.obs0.dtype == obs_dtype
         D, n_out = fused.env.engine.obs_dim, _n_out(fused, True)
         index = None
         if P > 1:
-            index = torch.randint(-1, P + 1, (N,), generator=torch.Generator().manual_seed(11)).to(torch.int32)
+            index = torch.randint(-1, P + 1, (n,), generator=torch.Generator().manual_seed(11)).to(torch.int32)
         policy = _spread_policy(7, twin.obs0, n_hidden, n_out, P=P, index=index)
         sa = _sampling(seed=23, temperature=temperature)              # (the auto-reset seed of the envs: the tag separates the streams)
-        hs = HostStats(N, device)
+        hs = HostStats(n, device)
         obs, seen = twin.obs0, []
-        for K in LAUNCHES:
-            out = fused.rollout_policy(policy, K, sampling=sa, probs=True, out=_nan_rows(K, N, D, obs_dtype, device), **WANT)
-            ref, obs = _twin_steps(twin, policy, sa, obs, K, hs, seen)
-            assert out["probs"].dtype == F64 and out["probs"].shape == (K, N)
+        _trace_start(trace, fused, True)
+        for K in launches:
+            out = fused.rollout_policy(policy, K, sampling=sa, probs=True, out=_nan_rows(K, n, D, obs_dtype, device), **WANT)
+            walked = [] if trace is not None else None
+            ref, obs = _twin_steps(twin, policy, sa, obs, K, hs, seen, walked)
+            _trace_launch(trace, walked, out, ref)
+            assert out["probs"].dtype == F64 and out["probs"].shape == (K, n)
             _compare(out, ref, K)
             d = out["done"]
             assert bool(torch.isnan(out["final_obs"][~d]).all()) and not bool(torch.isnan(out["final_obs"][d]).any()), K
@@ -409,6 +417,9 @@ def _fused_equals_stepped(device, arch, series, n_hidden, obs_dtype=F64, P=1, te
             hs.check(fused.episode_stats)
             if K == 64:
                 assert int(ref["done"].sum()) >= 1                     # a grid restarts inside the 64-step launch
+        _trace_end(trace, fused)
+        if trace is not None:
+            trace["greedy"] = torch.stack([g for _, g in seen])
         if vacuous:                                                    # the stepped twin ALONE says whether the test can pass vacuously
             taken, greedy = torch.stack([a for a, _ in seen]), torch.stack([g for _, g in seen])
             share = float((taken != greedy).double().mean())

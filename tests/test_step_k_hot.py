@@ -1,6 +1,7 @@
 """step_k_hot_kernel (csrc/mgx_step_hot.hip): the kernel of its own that the lock-step reward + SoC launch of mgx_step_k takes on
 factorised series without a GridModule.  It must compute, bit for bit, what step_k_kernel computes for the same launch (tunable
-step_k_hot = 0) and what K single steps compute: reward, SoC trace and the state columns after the launch."""
+step_k_hot = 0) and what K single steps compute: reward, SoC trace and the state columns after the launch.  HOT_LAYOUTS x HOT_DTYPES
+name the compiled forms: tests/test_layouts.py fails when the library holds one that is not among them."""
 import pytest
 import torch
 
@@ -115,9 +116,12 @@ def _actions(device, K, N, A, dtype, normalized, seed):
     return a.to(dtype).contiguous()
 
 
+HOT_LAYOUTS, HOT_DTYPES = (1, 2, 3), (torch.float64, torch.float32)      # the forms step_k_hot_kernel<F, U, AT> is compiled in
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize("action_dtype", [torch.float64, torch.float32], ids=["f64", "f32"])
-@pytest.mark.parametrize("flags", [1, 2, 3])
+@pytest.mark.parametrize("action_dtype", HOT_DTYPES, ids=["f64", "f32"])
+@pytest.mark.parametrize("flags", HOT_LAYOUTS)
 def test_hot_kernel_equals_step_k_kernel_and_single_steps(flags, action_dtype, device, hot):
     """Layouts 1, 2, 3 x float64 / float32 controls x normalised or not; N = 1, 65, 300 (two workgroups of 192 grids: a wholly
     inactive wave that still meets the barriers, a partial wave), 301 in two shards; every K around the group size, the largest K
