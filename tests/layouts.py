@@ -1,6 +1,11 @@
 """Any of the ten module layouts the fused kernels are compiled for (template parameter F: bit 0 genset, bit 1 battery, bit 2 grid,
 bit 3 grid before battery), carved out of ONE generated ``genset+battery+grid`` batch: the columns of the absent modules are
-dropped, everything else -- series, parameters, initial state -- is cloned, so the ten batches differ in their module set alone."""
+dropped, everything else -- series, parameters, initial state -- is cloned, so the ten batches differ in their module set alone.
+
+The second half builds the inputs of the GENERAL path (several modules of a kind per grid) from parameter dicts
+(``MicrogridBatch.from_grids`` on the device, ``oracle.OracleMultiMicrogrid`` on the CPU) and collects what the oracle returns into
+arrays, so that a test compares whole columns: ``general_grids`` / ``general_controls`` / ``drawn_lists``, ``OracleGrids``,
+``addend_counts``, ``log_columns``, ``episodes_vs_oracle``."""
 import dataclasses
 
 import numpy as np
@@ -84,3 +89,312 @@ def replay(oracle, cols, trace, normalized=True, label=""):
     for name, want in st.items():
         got = trace["state"][name].cpu().numpy()
         assert np.array_equal(got.view(np.uint32) if name == "gen_status" else got, want), (label, name)
+
+
+# ---- the general path: grids with several modules of a kind, built from parameter dicts ------------------------------------------
+PLAIN, STRESSED, MIRRORED = 0, 1, 2
+
+
+def random_multi_grid(rs, T, n_gen, n_bat, n_grid, n_load, n_pv, horizon=0, grid_first=False):
+    """The parameter dict of one microgrid with the given numbers of modules: every instance its own parameters, every grid
+    instance its own ``grid_ts`` (outages among its rows), gensets with timers 0..2 and both initial states."""
+    g = dict(load_ts=80 * rs.rand(T, n_load) + 5, pv_ts=60 * rs.rand(T, n_pv) * (rs.rand(T, n_pv) > 0.3), horizon=horizon,
+             final_step=T, initial_step=0, unbalanced=dict(loss_load_cost=10.0, overgeneration_cost=1.0 + rs.rand()),
+             controllable_order=["genset", "grid", "battery"] if grid_first else ["genset", "battery", "grid"])
+    if n_gen:
+        g["genset"] = [dict(running_min_production=float(rs.choice([0.0, 5.0, 12.0])), running_max_production=40.0 + 40 * rs.rand(),
+                            genset_cost=0.3 + 0.3 * rs.rand(), co2_per_unit=2.0, cost_per_unit_co2=0.1,
+                            start_up_time=int(rs.randint(0, 3)), wind_down_time=int(rs.randint(0, 3)),
+                            init_start_up=bool(rs.randint(0, 2))) for _ in range(n_gen)]
+    if n_bat:
+        g["battery"] = [dict(min_capacity=10.0, max_capacity=60.0 + 80 * rs.rand(), max_charge=20.0 + 10 * rs.rand(),
+                             max_discharge=25.0, efficiency=float(rs.choice([0.9, 0.95, 1.0])), battery_cost_cycle=0.02 * rs.rand(),
+                             init_soc=0.3 + 0.6 * rs.rand()) for _ in range(n_bat)]
+    if n_grid:
+        g["grid"] = [dict(max_import=30.0 + 40 * rs.rand(), max_export=20.0 + 30 * rs.rand(), cost_per_unit_co2=0.1)
+                     for _ in range(n_grid)]
+        g["grid_ts"] = [np.stack([0.1 + rs.rand(T), 0.5 * rs.rand(T), 0.3 * rs.rand(T), (rs.rand(T) > 0.2).astype(float)], axis=1)
+                        for _ in range(n_grid)]
+    return g
+
+
+def populations(N, mirrored=False):
+    """[N] PLAIN / STRESSED / MIRRORED: the first half of the grids is the stressed population (loads x 4, batteries and grids asked
+    to discharge and import: long ``provided`` lists that end in loss load); with ``mirrored`` the last quarter is its mirror image
+    (pvs x 4, batteries and grids asked to charge and export: long ``absorbed`` lists that end in overgeneration)."""
+    pop = np.full(N, PLAIN)
+    pop[:N // 2] = STRESSED
+    if mirrored:
+        pop[N - N // 4:] = MIRRORED
+    return pop
+
+
+def general_grids(flags, counts, N, T, seed, horizon=0, mirrored=False):
+    """N parameter dicts of layout ``flags`` (one of LAYOUTS; ``controllable_order`` follows bit 3) with ``counts`` = (n_genset,
+    n_battery, n_grid, n_load, n_pv) modules, for ``MicrogridBatch.from_grids`` and ``oracle.OracleMultiMicrogrid``."""
+    ng, nb, nr, nl, npv = counts
+    if flags not in LAYOUTS or (ng > 0, nb > 0, nr > 0) != (bool(flags & F_GENSET), bool(flags & F_BATTERY), bool(flags & F_GRID)):
+        raise ValueError(f"the counts {counts} are not a mix of layout {flags}")
+    if min(nl, npv) < 1 or max(counts) < 2:
+        raise ValueError(f"{counts}: the general path takes at least one load and pv, and several modules of some kind")
+    rs = np.random.RandomState(seed)
+    grids = [random_multi_grid(rs, T, ng, nb, nr, nl, npv, horizon, bool(flags & F_GRID_FIRST)) for _ in range(N)]
+    for g, p in zip(grids, populations(N, mirrored)):
+        if p == STRESSED:
+            g["load_ts"] = g["load_ts"] * 4
+        elif p == MIRRORED:
+            g["pv_ts"] = g["pv_ts"] * 4
+    return grids
+
+
+def general_controls(rs, K, N, counts, mirrored=False):
+    """Normalised controls [K, N, A]: U[0, 1), the battery and grid columns of the stressed population from the upper half (they
+    discharge and import), of the mirrored one from the lower half."""
+    ng, nb, nr = counts[:3]
+    a = rs.rand(K, N, 2 * ng + nb + nr)
+    pop = populations(N, mirrored)
+    a[:, pop == STRESSED, 2 * ng:] = 0.5 + 0.5 * a[:, pop == STRESSED, 2 * ng:]
+    a[:, pop == MIRRORED, 2 * ng:] = 0.5 * a[:, pop == MIRRORED, 2 * ng:]
+    return a
+
+
+def raw_controls(a, counts):
+    """Unnormalised controls out of normalised ones: genset goals 0 / 1, genset requests in [0, 60), battery and grid requests in
+    [-42, 78) (the stressed population's above 18)."""
+    ng = counts[0]
+    raw = (a * 2 - 0.7) * 60
+    raw[..., 0:2 * ng:2] = np.round(a[..., 0:2 * ng:2])
+    raw[..., 1:2 * ng:2] = a[..., 1:2 * ng:2] * 60
+    return raw
+
+
+def instances_differ(grids):
+    """True where, in every grid, any two instances of a kind differ in a parameter (and any two grid instances in their series)."""
+    for g in grids:
+        for kind in ("genset", "battery", "grid"):
+            inst = g.get(kind, [])
+            for i in range(len(inst)):
+                for j in range(i):
+                    if inst[i] == inst[j] or (kind == "grid" and np.array_equal(g["grid_ts"][i], g["grid_ts"][j])):
+                        return False
+        for name in ("load_ts", "pv_ts"):
+            ts = g[name]
+            if any(np.array_equal(ts[:, i], ts[:, j]) for i in range(ts.shape[1]) for j in range(i)):
+                return False
+    return True
+
+
+def drawn_lists(rs, counts, n_lists=24):
+    """int32 [n_lists, width, 3] priority lists over module instances, drawn by hand (the reference's enumeration is factorial in the
+    elements): every module somewhere, genset goals 0 / 1, a module named twice (the second is skipped, priority_list.py:82-88),
+    padding and an element the layout does not have in between; one list in five stops short of the last modules."""
+    ng, nb, nr = counts[:3]
+    mods = [(0, j) for j in range(ng)] + [(1, j) for j in range(nb)] + [(2, j) for j in range(nr)]
+    rows = []
+    for _ in range(n_lists):
+        els = [(k, j, int(rs.randint(0, 2)) if k == 0 else 0) for k, j in (mods[q] for q in rs.permutation(len(mods)))]
+        els.insert(int(rs.randint(0, len(els) + 1)), (-1, -1, -1))
+        els.insert(int(rs.randint(0, len(els) + 1)), (int(rs.randint(0, 3)), 5, 0))
+        els.insert(int(rs.randint(1, len(els) + 1)), els[0])
+        rows.append(els[: len(mods) + 3] if rs.rand() < 0.8 else els[: max(1, len(mods) - 1)])
+    width = max(len(r) for r in rows)
+    tab = -np.ones((len(rows), width, 3), dtype=np.int32)
+    for q, r in enumerate(rows):
+        tab[q, :len(r)] = r
+    return tab
+
+
+def own_elements(table, counts):
+    """The lists of ``table`` [n_lists, width, 3] as the oracle takes them: padding and elements naming a module the layout does not
+    have are left out, as the device skips them."""
+    n = counts[:3]
+    return [[(int(k), int(j), int(a)) for k, j, a in pl if 0 <= k <= 2 and 0 <= j < n[k]] for pl in table]
+
+
+def status_words(cur, goal, up, down):
+    """The device's packed genset status (uint32) of the oracle's four counters."""
+    return (np.asarray(cur).astype(np.uint32) | (np.asarray(goal).astype(np.uint32) << 8) | (np.asarray(up).astype(np.uint32) << 16)
+            | (np.asarray(down).astype(np.uint32) << 24))
+
+
+class OracleGrids:
+    """``oracle.OracleMultiMicrogrid`` of every grid of a batch, stepped together; what the oracle returns is collected into arrays
+    (a record array of ``MStepOut`` per step, observation rows, state columns) so that a test compares column by column.  An
+    exception of the oracle (the reference's AssertionError, an unbalanced step) is not caught: no grid may be left out."""
+
+    def __init__(self, oracle, grids):
+        self.oms = [oracle.OracleMultiMicrogrid(g) for g in grids]
+        self.dtype = np.dtype(oracle.MStepOut)
+        self.N = len(grids)
+
+    def reset(self, rows):
+        """Moves every grid's counter (``rows``: one row, or [N]) and keeps the module state, as Microgrid.reset does -> obs [N, D]."""
+        rows = np.broadcast_to(np.asarray(rows), (self.N,))
+        return np.stack([om.reset(int(t)) for om, t in zip(self.oms, rows)])
+
+    def set_rows(self, rows, only=None):
+        """Moves the counter of every grid (``only``: of the grids of a mask [N]) to ``rows`` [N]."""
+        for j in (range(self.N) if only is None else np.flatnonzero(only)):
+            self.oms[j].s.t = int(rows[j])
+
+    def rows(self):
+        return np.array([om.s.t for om in self.oms])
+
+    def observe(self):
+        return np.stack([om.observe() for om in self.oms])
+
+    def step(self, controls, normalized=True):
+        """One ``run`` of every grid (controls [N, A]) -> MStepOut records [N]."""
+        rec = np.empty(self.N, dtype=self.dtype)
+        for j, om in enumerate(self.oms):
+            rec[j] = np.frombuffer(om.run(controls[j], normalized), dtype=self.dtype, count=1)[0]
+        return rec
+
+    def run(self, controls, normalized=True, observe=False):
+        """K steps (controls [K, N, A]) -> records [K, N] (and the observation rows [K, N, D] behind every step)."""
+        recs, obs = [], []
+        for a in controls:
+            recs.append(self.step(a, normalized))
+            if observe:
+                obs.append(self.observe())
+        return (np.stack(recs), np.stack(obs)) if observe else np.stack(recs)
+
+    def expand(self, plists):
+        """``populate_action`` of every grid's list (``plists``: N lists of (kind, instance, action)) -> raw controls [N, A]."""
+        return np.stack([om.populate_action(pl) for om, pl in zip(self.oms, plists)])
+
+    def state(self):
+        """The state columns as the batch holds them: charge / soc [n_battery, N], gen_status uint32 [n_genset, N]."""
+        c = self.oms[0].counts
+        out = {}
+        if c["battery"]:
+            out["charge"] = np.array([[om.s.battery[q].charge for om in self.oms] for q in range(c["battery"])])
+            out["soc"] = np.array([[om.s.battery[q].soc for om in self.oms] for q in range(c["battery"])])
+        if c["genset"]:
+            st = [[(om.s.genset[q].gen_cur, om.s.genset[q].gen_goal, om.s.genset[q].gen_up, om.s.genset[q].gen_down)
+                   for om in self.oms] for q in range(c["genset"])]
+            out["gen_status"] = status_words(*np.moveaxis(np.array(st), -1, 0))
+        return out
+
+
+def log_columns(rec, names):
+    """name -> the oracle's column [..., N] of the device's log (``engine.log_names``: ``name`` / ``name[j]``) out of MStepOut
+    records; ``genset_status`` is the packed word as the log holds it (a double); ``violations`` is not the oracle's (None).  The
+    vectorised twin of ``OracleMultiMicrogrid.log_row`` (tests/test_layouts.py holds the two against each other)."""
+    out = {}
+    for n in names:
+        base, j = (n[:n.index("[")], int(n[n.index("[") + 1:-1])) if n.endswith("]") else (n, 0)
+        if base == "genset_status":
+            g = rec["genset"][..., j]
+            out[n] = status_words(g["gen_cur"], g["gen_goal"], g["gen_up"], g["gen_down"]).astype(np.float64)
+        elif base.startswith("genset_"):
+            out[n] = rec["genset"][..., j][base]
+        elif base in ("discharge_amount", "charge_amount", "battery_reward", "soc_pre", "charge_pre"):
+            out[n] = rec["battery"][..., j][base]
+        elif base.startswith("grid_"):
+            out[n] = rec["grid"][..., j][base]
+        else:
+            out[n] = rec["common"][base] if base in rec["common"].dtype.names else None
+    return out
+
+
+def assert_log_equals(log, rec, names, label=""):
+    """A device log [..., L, N] (host array) against the oracle's records [..., N], column by column, bit for bit."""
+    columns = log_columns(rec, names)
+    assert len(columns) == len(names) == log.shape[-2]
+    assert [n for n, want in columns.items() if want is None] == ["violations"], "a log column the oracle side does not know"
+    for c, (n, want) in enumerate(columns.items()):
+        if want is not None:
+            assert np.array_equal(log[..., c, :], want), (label, n)
+
+
+def requests(grids, controls, normalized):
+    """(battery requests [..., N, n_battery], grid requests [..., N, n_grid]) in energy units, as ``battery_step`` / ``grid_step`` of
+    oracle/mgx_oracle.c denormalise a control (low + (high - low) * v, a zero spread taken as 1), in their order of operations."""
+    nb, nr = len(grids[0].get("battery", [])), len(grids[0].get("grid", []))
+    ng = len(grids[0].get("genset", []))
+    bat, grd = controls[..., 2 * ng:2 * ng + nb], controls[..., 2 * ng + nb:]
+    if not normalized:
+        return bat, grd
+
+    def denormalise(lo, hi, v):
+        spread = hi - lo
+        return lo + np.where(spread == 0.0, 1.0, spread) * v
+    par = lambda kind, key: np.array([[q[key] for q in g.get(kind, [])] for g in grids], dtype=np.float64).reshape(len(grids), -1)  # noqa: E731
+    if nb:
+        bat = denormalise(-par("battery", "max_discharge") / par("battery", "efficiency"),
+                          par("battery", "max_charge") * par("battery", "efficiency"), bat)
+    if nr:
+        grd = denormalise(-1 * par("grid", "max_export"), par("grid", "max_import"), grd)
+    return bat, grd
+
+
+def addend_counts(grids, rec, controls, normalized):
+    """(addends of ``provided``, addends of ``absorbed``) [..., N] of the oracle steps ``rec`` (MStepOut records) taken under
+    ``controls`` [..., N, A]: by the rule of ``mstep_append`` in oracle/mgx_oracle.c a module appends ONE addend, a zero included, to
+    the list of the side it acted on -- a genset and a pv to ``provided``, a load to ``absorbed``, a battery and a grid by the SIGN OF
+    THE REQUEST (below zero: ``absorbed``; zero and above: ``provided``), not by the amount that went through (an empty battery asked
+    to discharge appends 0.0 to ``provided``) -- and the unbalanced-energy module closes the step on ``absorbed`` (overgeneration:
+    the balance after the controllable modules is positive) or on ``provided`` (loss load).  The records hold the amounts, not the
+    requests, so the sign is taken from the controls; where an amount is not zero it must agree, which is asserted."""
+    g0 = grids[0]
+    ng, nb, nr = len(g0.get("genset", [])), len(g0.get("battery", [])), len(g0.get("grid", []))
+    nl, npv = g0["load_ts"].shape[1], g0["pv_ts"].shape[1]
+    bat, grd = requests(grids, controls, normalized)
+    bat_source, grid_source = ~(bat < 0), ~(grd < 0)
+    assert not (rec["battery"]["charge_amount"][..., :nb] != 0)[bat_source].any()
+    assert not (rec["battery"]["discharge_amount"][..., :nb] != 0)[~bat_source].any()
+    assert not (rec["grid"]["grid_export"][..., :nr] != 0)[grid_source].any()
+    assert not (rec["grid"]["grid_import"][..., :nr] != 0)[~grid_source].any()
+    over = rec["common"]["overgeneration"] > 0
+    assert not (over & (rec["common"]["loss_load"] != 0)).any()
+    provided = ng + npv + bat_source.sum(-1) + grid_source.sum(-1) + ~over
+    absorbed = nl + (~bat_source).sum(-1) + (~grid_source).sum(-1) + over
+    return provided, absorbed
+
+
+def episodes_vs_oracle(oracle, env, grids, K, draw, first=None, label=""):
+    """K steps of ``env``, a PerGridWindowEnv(auto_reset=True) over ``MicrogridBatch.from_grids(grids)`` (continuous or discrete; not
+    yet reset), replayed on the multi-instance CPU oracle with the rows every grid walked, taken from what the env reports (``starts``,
+    ``lengths``, ``current_steps``): a restart moves the counter and keeps the module state.  Rewards, done flags (an episode is over
+    when its length is used up), observation rows (of a restarted grid: the first row of its new episode) and the final state of
+    every module instance must be the oracle's, bit for bit, on every grid.  ``draw(k)``: ids [N] of the env's ``actions_list`` or
+    normalised controls [N, A] of step k (host arrays); ``first``: the (starts, lengths) of the first episodes, else the env draws
+    them.  Returns the restarts per grid."""
+    import torch
+    dev, N = env.full.device, len(grids)
+    discrete = hasattr(env.env, "actions_list")
+    og = OracleGrids(oracle, grids)
+    obs = env.reset(*first) if first is not None else env.reset()
+
+    def lengths_now():
+        return np.full(N, env.length) if env.lengths is None else env.lengths.cpu().numpy().astype(np.int64)
+    rows, left = env.env.current_steps.cpu().numpy(), lengths_now()
+    assert np.array_equal(rows, env.starts.cpu().numpy()), label
+    assert np.array_equal(obs.cpu().numpy(), og.reset(rows)), (label, "first rows")
+    restarts = np.zeros(N, dtype=np.int64)
+    for k in range(K):
+        a = draw(k)
+        if discrete:
+            lists = env.env.actions_list
+            plists = [lists[i] if env.env._instances else [(m, 0, act) for m, act in lists[i]] for i in a]
+            want = og.step(og.expand(plists), False)
+            obs, reward, done, _ = env.step(torch.as_tensor(a, dtype=torch.int32, device=dev))
+        else:
+            want = og.step(a, True)
+            obs, reward, done, _ = env.step(torch.as_tensor(a, dtype=torch.float64, device=dev))
+        done = done.cpu().numpy().astype(bool)
+        assert np.array_equal(reward.cpu().numpy(), want["common"]["reward"]), (label, k)
+        left = left - 1
+        assert np.array_equal(done, left == 0), (label, k)
+        after = env.env.current_steps.cpu().numpy()
+        assert np.array_equal(after[~done], rows[~done] + 1) and np.array_equal(after[done], env.starts.cpu().numpy()[done]), (label, k)
+        rows, left = after, np.where(done, lengths_now(), left)
+        restarts += done
+        og.set_rows(rows, only=done)                              # a restart moves the counter; every other grid's is the oracle's own
+        assert np.array_equal(og.rows(), rows), (label, k)
+        assert np.array_equal(obs.cpu().numpy(), og.observe()), (label, k, "rows")
+    for name, want in og.state().items():
+        got = env.env.batch.cols[name].cpu().numpy().reshape(want.shape[0], N)
+        assert np.array_equal(got.view(np.uint32) if name == "gen_status" else got, want), (label, name)
+    return restarts

@@ -2,9 +2,11 @@
 tests/test_layout_matrix_policy.py, tests/test_layout_matrix_whatif.py), checked without a GPU:
 layouts.carve gives every one of the ten layouts the fused kernels are compiled for, in both series forms, the CPU oracle replays
 each of them without leaving a grid out, the inputs tell the grid-first layouts from the battery-first ones and reach both genset
-forms of the loops -- and every instantiation of the fifteen kernel families of FAMILIES that the library holds (the open-loop fused
-kernels, the closed-loop policy kernels, the what-if kernels, the policy gradient, the hot K-step) is a case of those matrices, or
-one of the forms a matrix file names as refused with the refusal asserted."""
+forms of the loops -- and every instantiation of the twenty-three kernel families of ``enumerated()`` that the library holds (the
+open-loop fused kernels, the closed-loop policy kernels, the what-if kernels, the policy gradient, the hot K-step, and the eight
+families of the general path, tests/test_general_path_matrix.py) is a case of those matrices, or one of the forms a matrix file names
+as refused with the refusal asserted.  The inputs of the general-path matrix are checked here too: their ``provided`` lists reach
+the eight and nine addends from which the sum takes numpy's pairwise order, and they tell the two stepping orders apart."""
 import functools
 import re
 
@@ -130,9 +132,128 @@ def test_the_inputs_reach_both_genset_forms_of_the_loops():
             assert torch.equal(_full(series, True).cols[name], mixed[name])
 
 
+# ---- the inputs of the general-path matrix (tests/test_general_path_matrix.py) ---------------------------------------------------
+def _general_mixes():
+    import test_general_path_matrix as general
+    return general.MIXES
+
+
+@pytest.mark.parametrize("flags,counts", _general_mixes(), ids=lambda v: str(v).replace(" ", ""))
+def test_the_general_path_inputs_meet_their_conditions(flags, counts):
+    """The reference side of every mix of the matrix, run here without a GPU: the oracle leaves no grid out (any exception fails),
+    two instances of a kind never share their parameters, the fused launches hold eight and nine ``provided`` addends on at least
+    1 % of their (step, grid) pairs wherever the list can hold that many (the mirrored mix: eight ``absorbed`` ones), the genset
+    status words take more than two values -- ``reference()`` and ``lists_reference()`` assert all of it; the shares are printed."""
+    import test_general_path_matrix as general
+    ref, lists = general.reference(flags, counts), general.lists_reference(flags, counts)
+    print(f"layout {flags}, counts {counts}: shares of the fused launches' pairs {ref['shares']}, of the list roll-outs' {lists['shares']}")
+    assert all(np.isfinite(ln["rec"]["common"]["reward"]).all() for ln in ref["launches"] + lists["launches"])
+
+
+@pytest.mark.parametrize("flags,counts", [(7, (2, 2, 2, 2, 2)), (15, (2, 3, 1, 1, 1)), (0, (0, 0, 0, 2, 2))])
+def test_the_vectorised_log_columns_are_the_oracles_log_row(flags, counts):
+    """layouts.log_columns (the record arrays of a whole launch) against OracleMultiMicrogrid.log_row (one MStepOut), the statement of
+    the log's names in oracle/oracle.py: every column log_row gives, value for value, the packed status word against the four counters
+    log_row gives under their own names, and ``violations`` the only name neither has."""
+    import test_general_path_matrix as general
+    from layouts import log_columns
+    from oracle import oracle as orc
+    from pymgrid_amd import MicrogridBatch
+    grids, ref = general.grids_of(flags, counts), general.reference(flags, counts)
+    names = MicrogridBatch.from_grids(grids, device="cpu").layout.log_names
+    rec = ref["launches"][2]["rec"]
+    columns = log_columns(rec, names)
+    assert list(columns) == list(names) and [n for n in names if columns[n] is None] == ["violations"]
+    om = orc.OracleMultiMicrogrid(grids[0])
+    for k, j in ((0, 0), (3, 17), (8, 199)):
+        out = orc.MStepOut.from_buffer_copy(rec[k, j].tobytes())
+        for n, v in zip(names, om.log_row(out, names)):
+            if v is not None:
+                assert columns[n][k, j] == v, (n, k, j)
+            elif n != "violations":
+                assert n.startswith("genset_status")
+                sfx = n[len("genset_status"):]
+                cur, goal, up, down = (int(x) for x in om.log_row(out, [c + sfx for c in ("gen_cur", "gen_goal", "gen_up", "gen_down")]))
+                assert columns[n][k, j] == float(cur | (goal << 8) | (up << 16) | (down << 24)), (n, k, j)
+
+
+def _provided_lists(grids, rec, controls, normalized, grid_first):
+    """The ``provided`` list of every oracle step of ``rec`` [K, N], rebuilt from the log columns in the order the sweep appends
+    (gensets, then the discharging batteries and the importing grids in the layout's order, the pv, the loss load): values
+    [K, N, slots] and a mask of the slots the step filled.  One pv only: the log holds the sum over the pvs."""
+    from layouts import requests
+    g0 = grids[0]
+    ng, nb, nr = len(g0.get("genset", [])), len(g0.get("battery", [])), len(g0.get("grid", []))
+    assert g0["pv_ts"].shape[1] == 1
+    bat, grd = requests(grids, controls, normalized)
+    over = rec["common"]["overgeneration"] > 0
+    vals = [rec["genset"]["genset_production"][..., j] for j in range(ng)]
+    used = [np.ones_like(over)] * ng
+    bats = ([rec["battery"]["discharge_amount"][..., j] for j in range(nb)], [~(bat[..., j] < 0) for j in range(nb)])
+    grds = ([rec["grid"]["grid_import"][..., j] for j in range(nr)], [~(grd[..., j] < 0) for j in range(nr)])
+    for v, u in ((grds, bats) if grid_first else (bats, grds)):
+        vals += v; used += u
+    vals += [rec["common"]["renewable_used"], rec["common"]["loss_load"]]
+    used += [np.ones_like(over), ~over]
+    return np.stack(vals, axis=-1), np.stack(used, axis=-1)
+
+
+@pytest.mark.parametrize("flags,counts", [(7, (2, 2, 2, 1, 1)), (7, (3, 3, 1, 1, 1)), (3, (3, 3, 0, 1, 1)), (7, (3, 3, 3, 1, 1)),
+                                          (15, (2, 3, 1, 1, 1))])
+def test_the_general_path_inputs_reach_the_pairwise_order_of_the_sums(flags, counts):
+    """Where the log holds every addend (one pv), the ``provided`` list of each oracle step of the fused launches is rebuilt in slot
+    order: numpy's sum of it (oracle.np_sum: pairwise from eight addends on) IS the step's ``overall_provided`` on every pair, which
+    proves the rebuild and layouts.addend_counts -- and on some of the pairs with eight or more addends the plain running sum is
+    NOT: a kernel that added its slots up one after the other, or in the order of a wrong slot list, would show on these inputs."""
+    import test_general_path_matrix as general
+    from layouts import addend_counts
+    from oracle import oracle as orc
+    grids, ref = general.grids_of(flags, counts), general.reference(flags, counts)
+    long_lists = differ = 0
+    for ln in ref["launches"]:
+        wide = ln["controls"].astype(np.float64)
+        vals, used = _provided_lists(grids, ln["rec"], wide, ln["normalized"], bool(flags & 8))
+        assert np.array_equal(used.sum(-1), addend_counts(grids, ln["rec"], wide, ln["normalized"])[0])
+        overall = ln["rec"]["common"]["overall_provided"]
+        for k, j in np.ndindex(overall.shape):
+            lst = vals[k, j][used[k, j]]
+            assert orc.np_sum(lst) == overall[k, j], (flags, counts, k, j, lst)
+            if lst.size >= 8:
+                running = 0.0
+                for v in lst:
+                    running += v
+                long_lists += 1
+                differ += running != overall[k, j]
+    print(f"layout {flags}, counts {counts}: the running sum differs from numpy's on {differ} of the {long_lists} pairs with eight or "
+          f"more addends ({differ / max(long_lists, 1):.4f})")
+    assert long_lists > 0 and differ > 0
+
+
+@pytest.mark.parametrize("battery_first,grid_first,counts", [(6, 14, (0, 2, 2, 2, 2)), (7, 15, (2, 2, 2, 2, 2))])
+def test_the_general_path_inputs_tell_grid_first_from_battery_first(battery_first, grid_first, counts):
+    """With two of a kind, the SAME grids (but for the order of their module list) under the SAME controls: the oracle's rewards of
+    the two stepping orders differ -- a general-path kernel that took batteries and grids in the wrong order would show."""
+    import test_general_path_matrix as general
+    from layouts import OracleGrids, general_controls
+    from oracle import oracle as orc
+    orc.build()
+    controls = general_controls(np.random.RandomState(2), 30, general.N, counts)
+    rewards = []
+    for flags in (battery_first, grid_first):
+        og = OracleGrids(orc, general.grids_of(flags, counts))
+        og.reset(T0)
+        rewards.append(og.run(controls, True)["common"]["reward"])
+    differ = rewards[0] != rewards[1]
+    print(f"layouts {battery_first} / {grid_first}, counts {counts}: {differ.mean():.4f} of the pairs, "
+          f"{int(differ.any(axis=0).sum())} of {general.N} grids")
+    assert differ.any()
+
+
 # ---- every compiled specialisation of the fused kernels is a case of a GPU matrix -----------------------------------------------
 SRC = {"factorised": 0, "materialised": 1, "gather": 2}      # EP_SRC_* of the episode kernels
 ARCH_FLAGS = {"genset+battery": 3, "battery+grid": 6, "genset+battery+grid": 7}
+GENERAL_FAMILIES = ("step_multi_kernel", "step_k_multi_kernel", "step_k_multi_small_kernel", "rollout_multi_small_kernel",
+                    "step_lists_small_kernel", "expand_multi_kernel", "check_multi_kernel", "observe_multi_kernel")
 
 
 def _ctype(dtype):
@@ -209,6 +330,14 @@ def enumerated():
         | {(c[0], _ctype(c[4]), SRC[c[1]]) for c in eps.STEP_K_ROWS_CASES},
     }
     assert critic.CASES is sample.CASES
+    # the general path: (layout, EP) of step_multi_kernel and step_lists_small_kernel, (layout, counts: "RT" or the five compile-time
+    # ones) of the two register loops, (layout,) of the rest -- what the calls of every case launch, by the rule stated beside CASES
+    import test_general_path_matrix as general
+    for kernel in GENERAL_FAMILIES:
+        want[kernel] = set()
+    for case in general.CASES:
+        for kernel, part in general.compiled_forms(*case):
+            want[kernel].add(part)
     return want
 
 
@@ -217,8 +346,9 @@ def refused():
     GPU test that asserts the refusal); ``test_every_compiled_specialisation_...`` holds them apart from the cases."""
     import test_layout_matrix_policy as pol
     import test_layout_matrix_whatif as whatif
+    import test_general_path_matrix as general
     out = {}
-    for kernel, part in pol.REFUSED + whatif.REFUSED:
+    for kernel, part in pol.REFUSED + whatif.REFUSED + general.REFUSED:
         out.setdefault(kernel, set()).add(part)
     return out
 
@@ -229,9 +359,21 @@ def compile_time_part(name):
     m = re.fullmatch(r"(?:\w+::)*(\w+)<(.*)>", name.strip())
     if not m:
         return None, None
-    kernel, args = m.group(1), [a.strip() for a in m.group(2).split(",")]
+    kernel, args, depth = m.group(1), [""], 0
+    for ch in m.group(2):                                    # split at the commas outside nested template arguments
+        depth += (ch == "<") - (ch == ">")
+        if ch == "," and depth == 0:
+            args.append("")
+        else:
+            args[-1] += ch
 
     def val(a):
+        a = a.strip()
+        counts = re.fullmatch(r"(?:\w+::)*CountsCT<(.*)>", a)
+        if counts:                                           # mgx::CountsCT<2, 2, 1, 1, 1>: the five compile-time counts
+            return tuple(int(c) for c in counts.group(1).split(","))
+        if re.fullmatch(r"(?:\w+::)*CountsRT", a):
+            return "RT"
         return {"true": True, "false": False}.get(a, int(a) if re.fullmatch(r"-?\d+", a) else a)
     args = [val(a) for a in args]
     if kernel in ("step_k_kernel", "rollout_kernel"):               # <F, U, AT | PER_STEP, RICH, FACT>
@@ -254,11 +396,17 @@ def compile_time_part(name):
         return kernel, (args[0], args[1], args[2])
     if kernel == "step_k_hot_kernel":                                            # <F, U, AT>
         return kernel, (args[0], args[2])
+    if kernel in ("step_multi_kernel", "step_lists_small_kernel"):               # <F, EP>
+        return kernel, (args[0], args[1])
+    if kernel in ("step_k_multi_small_kernel", "rollout_multi_small_kernel"):    # <F, CNT, M>
+        return kernel, (args[0], args[1])
+    if kernel in ("step_k_multi_kernel", "expand_multi_kernel", "check_multi_kernel", "observe_multi_kernel"):    # <F>
+        return kernel, (args[0],)
     return kernel, None
 
 
 def missing_cases(usage, want, refused=None):
-    """The instantiations in ``usage`` of the families of ``want`` (the fifteen of ``enumerated()``) whose compile-time part no GPU
+    """The instantiations in ``usage`` of the families of ``want`` (those of ``enumerated()``) whose compile-time part no GPU
     test enumerates and ``refused`` (kernel -> parts with an asserted refusal) does not name."""
     out = []
     for name in sorted(usage):
@@ -312,6 +460,20 @@ def test_the_coverage_check_names_what_a_dropped_case_leaves_uncovered():
     assert len({family(name) for name in made_up}) == 9
     full = {family(name): {part} for name, part in made_up.items()}
     assert all(compile_time_part(name) == (family(name), part) for name, part in made_up.items())
+    assert missing_cases(usage, full) == []
+    for name in made_up:
+        assert missing_cases(usage, {**full, family(name): set()}) == [name]
+        assert missing_cases(usage, {**full, family(name): set()}, {family(name): {made_up[name]}}) == []
+    # ... and of the eight families of the general path (the compile-time counts nest: the arguments split at depth 0)
+    made_up = {"mgx::step_multi_kernel<14, true>": (14, True), "mgx::step_k_multi_kernel<5>": (5,),
+               "mgx::step_k_multi_small_kernel<7, mgx::CountsCT<2, 2, 1, 1, 1>, 2>": (7, (2, 2, 1, 1, 1)),
+               "mgx::rollout_multi_small_kernel<15, mgx::CountsRT, 2>": (15, "RT"), "mgx::step_lists_small_kernel<1, false>": (1, False),
+               "mgx::expand_multi_kernel<6>": (6,), "mgx::check_multi_kernel<2>": (2,), "mgx::observe_multi_kernel<0>": (0,)}
+    usage = dict.fromkeys(list(made_up) + ["mgx::obs_windows_k_multi_kernel<7, float>", "mgx::action_bounds_kernel<7>"], {})
+    assert {family(name) for name in made_up} == set(GENERAL_FAMILIES)
+    full = {family(name): {part} for name, part in made_up.items()}
+    assert all(compile_time_part(name) == (family(name), part) for name, part in made_up.items())
+    assert compile_time_part("mgx::step_k_multi_small_kernel<3, mgx::CountsCT<3, 3, 0, 1, 1>, 3>")[1] == (3, (3, 3, 0, 1, 1))
     assert missing_cases(usage, full) == []
     for name in made_up:
         assert missing_cases(usage, {**full, family(name): set()}) == [name]

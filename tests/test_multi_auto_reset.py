@@ -9,6 +9,8 @@ import numpy as np
 import pytest
 import torch
 
+from layouts import episodes_vs_oracle, random_multi_grid
+
 pytestmark = pytest.mark.gpu
 SOAK = int(os.environ.get("MGX_FUZZ_SEED", "0"))          # soak runs: another draw of every batch / episode / action sequence
 
@@ -154,71 +156,23 @@ def test_inplace_discrete_episodes_equal_gathered_windows(counts, H, device):
     inpl.close(); gath.close()
 
 
-def _random_multi_grid(rs, T, n_gen, n_bat, n_grid, n_load, n_pv):
-    g = dict(load_ts=80 * rs.rand(T, n_load) + 5, pv_ts=60 * rs.rand(T, n_pv) * (rs.rand(T, n_pv) > 0.3), horizon=0, final_step=T,
-             initial_step=0, unbalanced=dict(loss_load_cost=10.0, overgeneration_cost=1.0 + rs.rand()),
-             controllable_order=["genset", "battery", "grid"])
-    g["genset"] = [dict(running_min_production=float(rs.choice([0.0, 5.0, 12.0])), running_max_production=40.0 + 40 * rs.rand(),
-                        genset_cost=0.3 + 0.3 * rs.rand(), co2_per_unit=2.0, cost_per_unit_co2=0.1, start_up_time=int(rs.randint(0, 3)),
-                        wind_down_time=int(rs.randint(0, 3)), init_start_up=bool(rs.randint(0, 2))) for _ in range(n_gen)]
-    g["battery"] = [dict(min_capacity=10.0, max_capacity=60.0 + 80 * rs.rand(), max_charge=20.0 + 10 * rs.rand(), max_discharge=25.0,
-                         efficiency=float(rs.choice([0.9, 0.95, 1.0])), battery_cost_cycle=0.02 * rs.rand(),
-                         init_soc=0.3 + 0.6 * rs.rand()) for _ in range(n_bat)]
-    g["grid"] = [dict(max_import=30.0 + 40 * rs.rand(), max_export=20.0 + 30 * rs.rand(), cost_per_unit_co2=0.1) for _ in range(n_grid)]
-    g["grid_ts"] = [np.stack([0.1 + rs.rand(T), 0.5 * rs.rand(T), 0.3 * rs.rand(T), (rs.rand(T) > 0.2).astype(float)], axis=1)
-                    for _ in range(n_grid)]
-    return g
-
-
 @pytest.mark.parametrize("length", [6, None])
 def test_generator_drawn_episodes_vs_the_oracle(length, device, oracle):
     """PerGridWindowEnv(discrete=True, auto_reset=True, generator=g) on 48 grids built from module lists: every grid's sequence of
     episodes (start, length at each restart) and priority lists replayed on the multi-instance CPU oracle (populate_action, run; a
-    restart moves the counter and keeps the state) -- rewards, done flags, observation rows and the final state `==`."""
+    restart moves the counter and keeps the state) -- rewards, done flags, observation rows and the final state `==`
+    (layouts.episodes_vs_oracle)."""
     from pymgrid_amd import MicrogridBatch
     from pymgrid_amd.hetero import PerGridWindowEnv
     N, T, K = 48, 40, 60
     rs = np.random.RandomState(17 + SOAK)
-    grids = [_random_multi_grid(rs, T, 2, 2, 1, 1, 1) for _ in range(N)]
+    grids = [random_multi_grid(rs, T, 2, 2, 1, 1, 1) for _ in range(N)]
     gen = torch.Generator(device=device); gen.manual_seed(23 + SOAK)
     env = PerGridWindowEnv(MicrogridBatch.from_grids(grids, device=device), trajectory_length=length, discrete=True, auto_reset=True,
                            generator=gen, remove_redundant_gensets=False)
     assert env.native and not env._device_draws
-    obs = [env.reset().cpu().numpy()]
-
-    def episodes_now():
-        s = env.starts.cpu().numpy()
-        ln = np.full(N, length) if env.lengths is None else env.lengths.cpu().numpy()
-        return s.copy(), ln.copy()
-    s0, l0 = episodes_now()
-    episodes = [[(int(s0[j]), int(l0[j]))] for j in range(N)]
-    ids, rewards, dones = [], [], []
-    for k in range(K):
-        a = rs.randint(0, env.action_space.n, size=N)
-        o, r, d, _ = env.step(torch.as_tensor(a, dtype=torch.int32, device=device))
-        ids.append(a); rewards.append(r.cpu().numpy()); dones.append(d.cpu().numpy()); obs.append(o.cpu().numpy())
-        s, ln = episodes_now()
-        for j in np.flatnonzero(dones[-1]):
-            episodes[j].append((int(s[j]), int(ln[j])))
-    assert sum(len(e) - 1 for e in episodes) > N                     # more restarts than grids
-    charge = env.env.batch.cols["charge"].cpu().numpy()
-    soc = env.env.batch.cols["soc"].cpu().numpy()
-    for j, gp in enumerate(grids):
-        om = oracle.OracleMultiMicrogrid(gp)
-        ep = iter(episodes[j])
-        start, n_left = next(ep)
-        assert np.array_equal(obs[0][j], om.reset(start)), j
-        for k in range(K):
-            out = om.run(om.populate_action(env.actions_list[ids[k][j]]), False)
-            assert rewards[k][j] == out.common.reward, (j, k)
-            n_left -= 1
-            assert bool(dones[k][j]) == (n_left == 0), (j, k)
-            if n_left == 0:
-                start, n_left = next(ep)
-                om.reset(start)
-            assert np.array_equal(obs[k + 1][j], om.observe()), (j, k)
-        for b in range(2):
-            assert charge[b, j] == om.s.battery[b].charge and soc[b, j] == om.s.battery[b].soc, (j, b)
+    restarts = episodes_vs_oracle(oracle, env, grids, K, lambda k: rs.randint(0, env.action_space.n, size=N))
+    assert int(restarts.sum()) > N                                   # more restarts than grids
     env.env.close()
 
 

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 from conftest import multi_cases
+from layouts import random_multi_grid as _random_multi_grid
 
 
 def test_multi_instance_oracle_vs_reference(oracle):
@@ -132,27 +133,6 @@ def test_multi_instance_discrete_env_vs_reference(device):
             if name in one.batch.cols:
                 assert torch.equal(twin.batch.cols[name], one.batch.cols[name])
         twin.close(); one.close()
-
-
-def _random_multi_grid(rs, T, n_gen, n_bat, n_grid, n_load, n_pv, horizon, grid_first):
-    g = dict(load_ts=80 * rs.rand(T, n_load) + 5, pv_ts=60 * rs.rand(T, n_pv) * (rs.rand(T, n_pv) > 0.3), horizon=horizon,
-             final_step=T, initial_step=0, unbalanced=dict(loss_load_cost=10.0, overgeneration_cost=1.0 + rs.rand()),
-             controllable_order=["genset", "grid", "battery"] if grid_first else ["genset", "battery", "grid"])
-    if n_gen:
-        g["genset"] = [dict(running_min_production=float(rs.choice([0.0, 5.0, 12.0])), running_max_production=40.0 + 40 * rs.rand(),
-                            genset_cost=0.3 + 0.3 * rs.rand(), co2_per_unit=2.0, cost_per_unit_co2=0.1,
-                            start_up_time=int(rs.randint(0, 3)), wind_down_time=int(rs.randint(0, 3)),
-                            init_start_up=bool(rs.randint(0, 2))) for _ in range(n_gen)]
-    if n_bat:
-        g["battery"] = [dict(min_capacity=10.0, max_capacity=60.0 + 80 * rs.rand(), max_charge=20.0 + 10 * rs.rand(),
-                             max_discharge=25.0, efficiency=float(rs.choice([0.9, 0.95, 1.0])), battery_cost_cycle=0.02 * rs.rand(),
-                             init_soc=0.3 + 0.6 * rs.rand()) for _ in range(n_bat)]
-    if n_grid:
-        g["grid"] = [dict(max_import=30.0 + 40 * rs.rand(), max_export=20.0 + 30 * rs.rand(), cost_per_unit_co2=0.1)
-                     for _ in range(n_grid)]
-        g["grid_ts"] = [np.stack([0.1 + rs.rand(T), 0.5 * rs.rand(T), 0.3 * rs.rand(T), (rs.rand(T) > 0.2).astype(float)], axis=1)
-                        for _ in range(n_grid)]
-    return g
 
 
 @pytest.mark.gpu
