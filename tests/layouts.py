@@ -5,7 +5,10 @@ dropped, everything else -- series, parameters, initial state -- is cloned, so t
 The second half builds the inputs of the GENERAL path (several modules of a kind per grid) from parameter dicts
 (``MicrogridBatch.from_grids`` on the device, ``oracle.OracleMultiMicrogrid`` on the CPU) and collects what the oracle returns into
 arrays, so that a test compares whole columns: ``general_grids`` / ``general_controls`` / ``drawn_lists``, ``OracleGrids``,
-``addend_counts``, ``log_columns``, ``episodes_vs_oracle``."""
+``addend_counts``, ``log_columns``, ``episodes_vs_oracle``.
+
+The third part is the reference side of the single-step family (tests/test_single_step_matrix.py): ``single_params`` turns the
+columns of a carved batch into the dicts ``oracle.OracleMicrogrid`` takes, ``OracleSingles`` steps one such microgrid per grid."""
 import dataclasses
 
 import numpy as np
@@ -282,19 +285,23 @@ def log_columns(rec, names):
     records; ``genset_status`` is the packed word as the log holds it (a double); ``violations`` is not the oracle's (None).  The
     vectorised twin of ``OracleMultiMicrogrid.log_row`` (tests/test_layouts.py holds the two against each other)."""
     out = {}
+    flat = "common" not in rec.dtype.names                    # StepOut records of OracleSingles: one module of a kind, one record
+    common = rec if flat else rec["common"]
+    part = (lambda kind, j: rec) if flat else (lambda kind, j: rec[kind][..., j])
     for n in names:
         base, j = (n[:n.index("[")], int(n[n.index("[") + 1:-1])) if n.endswith("]") else (n, 0)
+        assert not (flat and j), n
         if base == "genset_status":
-            g = rec["genset"][..., j]
+            g = part("genset", j)
             out[n] = status_words(g["gen_cur"], g["gen_goal"], g["gen_up"], g["gen_down"]).astype(np.float64)
         elif base.startswith("genset_"):
-            out[n] = rec["genset"][..., j][base]
+            out[n] = part("genset", j)[base]
         elif base in ("discharge_amount", "charge_amount", "battery_reward", "soc_pre", "charge_pre"):
-            out[n] = rec["battery"][..., j][base]
+            out[n] = part("battery", j)[base]
         elif base.startswith("grid_"):
-            out[n] = rec["grid"][..., j][base]
+            out[n] = part("grid", j)[base]
         else:
-            out[n] = rec["common"][base] if base in rec["common"].dtype.names else None
+            out[n] = common[base] if base in common.dtype.names else None
     return out
 
 
@@ -353,48 +360,193 @@ def addend_counts(grids, rec, controls, normalized):
     return provided, absorbed
 
 
-def episodes_vs_oracle(oracle, env, grids, K, draw, first=None, label=""):
-    """K steps of ``env``, a PerGridWindowEnv(auto_reset=True) over ``MicrogridBatch.from_grids(grids)`` (continuous or discrete; not
-    yet reset), replayed on the multi-instance CPU oracle with the rows every grid walked, taken from what the env reports (``starts``,
-    ``lengths``, ``current_steps``): a restart moves the counter and keeps the module state.  Rewards, done flags (an episode is over
-    when its length is used up), observation rows (of a restarted grid: the first row of its new episode) and the final state of
-    every module instance must be the oracle's, bit for bit, on every grid.  ``draw(k)``: ids [N] of the env's ``actions_list`` or
-    normalised controls [N, A] of step k (host arrays); ``first``: the (starts, lengths) of the first episodes, else the env draws
-    them.  Returns the restarts per grid."""
-    import torch
-    dev, N = env.full.device, len(grids)
-    discrete = hasattr(env.env, "actions_list")
-    og = OracleGrids(oracle, grids)
-    obs = env.reset(*first) if first is not None else env.reset()
+class EpisodeReplay:
+    """The steps of ``env``, a PerGridWindowEnv(auto_reset=True), replayed on the CPU oracle ``og`` (an ``OracleGrids`` or
+    ``OracleSingles`` over the env's batch) with the rows every grid walked, taken from what the env reports (``starts``, ``lengths``,
+    ``current_steps``): a restart moves the counter and keeps the module state.  ``begin(obs)`` takes the rows of the env's reset,
+    ``oracle_step(a)`` steps the oracle under the ids / controls ``a`` and returns the tensor the env takes, ``after(k, ...)`` holds what
+    the env's step returned against it: rewards, done flags (an episode is over when its length is used up), observation rows (of a
+    restarted grid: the first row of its new episode; ``final``: ``info["final_observation"]`` of the finished grids, the oracle's rows
+    behind the step, before the restart moves the counter; float32 rows: the oracle's rounded), ``finish()`` the state of every module
+    instance -- the oracle's, bit for bit, on every grid.  The steps of a fleet's buckets interleave: one replay per bucket."""
 
-    def lengths_now():
-        return np.full(N, env.length) if env.lengths is None else env.lengths.cpu().numpy().astype(np.int64)
-    rows, left = env.env.current_steps.cpu().numpy(), lengths_now()
-    assert np.array_equal(rows, env.starts.cpu().numpy()), label
-    assert np.array_equal(obs.cpu().numpy(), og.reset(rows)), (label, "first rows")
-    restarts = np.zeros(N, dtype=np.int64)
-    for k in range(K):
-        a = draw(k)
-        if discrete:
+    def __init__(self, env, og, label="", final=False):
+        import torch
+        self.env, self.og, self.label, self.final = env, og, label, final
+        self.discrete = hasattr(env.env, "actions_list")
+        self.rounded = (lambda rows: rows.astype(np.float32)) if env.env.engine.obs_dtype == torch.float32 else (lambda rows: rows)
+        self.restarts = np.zeros(og.N, dtype=np.int64)
+
+    def lengths_now(self):
+        env = self.env
+        return np.full(self.og.N, env.length) if env.lengths is None else env.lengths.cpu().numpy().astype(np.int64)
+
+    def begin(self, obs):
+        env = self.env
+        self.rows, self.left = env.env.current_steps.cpu().numpy(), self.lengths_now()
+        assert np.array_equal(self.rows, env.starts.cpu().numpy()), self.label
+        assert np.array_equal(obs.cpu().numpy(), self.rounded(self.og.reset(self.rows))), (self.label, "first rows")
+
+    def oracle_step(self, a):
+        import torch
+        env, og = self.env, self.og
+        if self.discrete:
             lists = env.env.actions_list
-            plists = [lists[i] if env.env._instances else [(m, 0, act) for m, act in lists[i]] for i in a]
-            want = og.step(og.expand(plists), False)
-            obs, reward, done, _ = env.step(torch.as_tensor(a, dtype=torch.int32, device=dev))
-        else:
-            want = og.step(a, True)
-            obs, reward, done, _ = env.step(torch.as_tensor(a, dtype=torch.float64, device=dev))
+            single = isinstance(og, OracleSingles)                # its lists hold (module, action) elements
+            plists = [lists[i] if env.env._instances or single else [(m, 0, act) for m, act in lists[i]] for i in a]
+            self.want = og.step(og.expand(plists), False)
+            return torch.as_tensor(a, dtype=torch.int32, device=env.full.device)
+        self.want = og.step(a, True)
+        return torch.as_tensor(a, dtype=env.env.engine.action_dtype, device=env.full.device)
+
+    def after(self, k, obs, reward, done, info):
+        env, og, label = self.env, self.og, self.label
         done = done.cpu().numpy().astype(bool)
-        assert np.array_equal(reward.cpu().numpy(), want["common"]["reward"]), (label, k)
-        left = left - 1
+        assert np.array_equal(reward.cpu().numpy(), common(self.want)["reward"]), (label, k)
+        left = self.left - 1
         assert np.array_equal(done, left == 0), (label, k)
+        if self.final:
+            assert np.array_equal(info["final_observation"].cpu().numpy()[done], self.rounded(og.observe())[done]), (label, k, "final rows")
         after = env.env.current_steps.cpu().numpy()
-        assert np.array_equal(after[~done], rows[~done] + 1) and np.array_equal(after[done], env.starts.cpu().numpy()[done]), (label, k)
-        rows, left = after, np.where(done, lengths_now(), left)
-        restarts += done
-        og.set_rows(rows, only=done)                              # a restart moves the counter; every other grid's is the oracle's own
-        assert np.array_equal(og.rows(), rows), (label, k)
-        assert np.array_equal(obs.cpu().numpy(), og.observe()), (label, k, "rows")
-    for name, want in og.state().items():
-        got = env.env.batch.cols[name].cpu().numpy().reshape(want.shape[0], N)
-        assert np.array_equal(got.view(np.uint32) if name == "gen_status" else got, want), (label, name)
-    return restarts
+        assert np.array_equal(after[~done], self.rows[~done] + 1) and np.array_equal(after[done], env.starts.cpu().numpy()[done]), (label, k)
+        self.rows, self.left = after, np.where(done, self.lengths_now(), left)
+        self.restarts += done
+        og.set_rows(after, only=done)                             # a restart moves the counter; every other grid's is the oracle's own
+        assert np.array_equal(og.rows(), after), (label, k)
+        assert np.array_equal(obs.cpu().numpy(), self.rounded(og.observe())), (label, k, "rows")
+
+    def finish(self):
+        for name, want in self.og.state().items():
+            got = self.env.env.batch.cols[name].cpu().numpy().reshape(want.shape)
+            assert np.array_equal(got.view(np.uint32) if name == "gen_status" else got, want), (self.label, name)
+        return self.restarts
+
+
+def episodes_vs_oracle(oracle, env, grids, K, draw, first=None, label="", final=False):
+    """K steps of ``env``, a PerGridWindowEnv(auto_reset=True) over ``MicrogridBatch.from_grids(grids)`` (continuous or discrete; not
+    yet reset), replayed on the CPU oracle (``EpisodeReplay``): rewards, done flags, observation rows and the final state of every
+    module instance must be the oracle's, bit for bit, on every grid.  ``grids``: the parameter dicts (the multi-instance oracle), or
+    the oracle side itself (an ``OracleSingles`` over the env's batch); ``draw(k)``: ids [N] of the env's ``actions_list`` or
+    normalised controls [N, A] of step k (host arrays); ``first``: the (starts, lengths) of the first episodes, else the env draws
+    them; ``final``: the env reports ``info["final_observation"]``.  Returns the restarts per grid."""
+    og = grids if isinstance(grids, (OracleGrids, OracleSingles)) else OracleGrids(oracle, grids)
+    replay = EpisodeReplay(env, og, label, final)
+    replay.begin(env.reset(*first) if first is not None else env.reset())
+    for k in range(K):
+        replay.after(k, *env.step(replay.oracle_step(draw(k))))
+    return replay.finish()
+
+
+# ---- the single-step family: one module of every kind, an OracleMicrogrid per grid ------------------------------------------------
+KIND_NAMES = ("genset", "battery", "grid")                   # module ids of a priority-list element (pymgrid_amd.priority_list)
+
+
+def common(rec):
+    """The whole-microgrid fields (reward, done, the balance) of step records: MStepOut's ``common``, or the StepOut itself."""
+    return rec["common"] if "common" in rec.dtype.names else rec
+
+
+def single_params(cols):
+    """``MicrogridBatch.numpy_columns()`` of a batch with one module of every kind (a ``carve()``) -> the N parameter dicts
+    ``oracle.OracleMicrogrid`` takes: the series, every parameter, the battery's ``charge`` / ``soc`` and the genset's four status
+    counters as the batch holds them now, ``controllable_order`` (grid first: layouts 14 / 15), ``horizon`` and ``final_step``."""
+    lay = cols["layout"]
+    N, grid_first = lay["N"], bool(lay.get("grid_before_battery", 0))
+    assert cols["load_ts"].shape == cols["pv_ts"].shape == (lay["T"], N), "one load and one pv per grid"
+    out = []
+    for j in range(N):
+        f = lambda name: float(cols[name][j])                # noqa: E731
+        p = dict(load_ts=np.ascontiguousarray(cols["load_ts"][:, j]), pv_ts=np.ascontiguousarray(cols["pv_ts"][:, j]),
+                 horizon=int(lay["horizon"]), initial_step=0, final_step=int(lay["final_step"]),
+                 unbalanced=dict(loss_load_cost=f("loss_load_cost"), overgeneration_cost=f("overgeneration_cost")),
+                 controllable_order=["genset", "grid", "battery"] if grid_first else ["genset", "battery", "grid"])
+        if lay["has_battery"]:
+            p["battery"] = dict(min_capacity=f("bat_min_capacity"), max_capacity=f("bat_max_capacity"), max_charge=f("bat_max_charge"),
+                                max_discharge=f("bat_max_discharge"), efficiency=f("bat_efficiency"),
+                                battery_cost_cycle=f("bat_cost_cycle"), charge=f("charge"), soc=f("soc"))
+        if lay["has_genset"]:
+            times, word = int(cols["gen_times"][j]), int(cols["gen_status"][j])
+            p["genset"] = dict(running_min_production=f("gen_running_min"), running_max_production=f("gen_running_max"),
+                               genset_cost=f("gen_cost"), co2_per_unit=f("gen_co2_per_unit"), cost_per_unit_co2=f("gen_cost_per_unit_co2"),
+                               start_up_time=times & 0xff, wind_down_time=(times >> 16) & 0xff, allow_abortion=not (times >> 8) & 1,
+                               status=[word & 0xff, (word >> 8) & 0xff, (word >> 16) & 0xff, (word >> 24) & 0xff])
+        if lay["has_grid"]:
+            p["grid"] = dict(max_import=f("grid_max_import"), max_export=f("grid_max_export"), cost_per_unit_co2=f("grid_cost_per_unit_co2"))
+            p["grid_ts"] = np.ascontiguousarray(cols["grid_ts"][:, :, j])
+        out.append(p)
+    return out
+
+
+class OracleSingles:
+    """``oracle.OracleMicrogrid`` of EVERY grid of a batch with one module of every kind (``numpy_columns()`` through
+    ``single_params``), stepped together with the oracle's own surface -- ``run``, ``observe``, ``reset``, ``populate_action`` -- and
+    collected into arrays: StepOut records, observation rows, state columns.  The twin of ``OracleGrids``; an exception of the oracle
+    (the reference's AssertionError, an unbalanced step, an assert of ``_populate_action``) is not caught: no grid may be left out."""
+
+    def __init__(self, oracle, cols):
+        lay = cols["layout"]
+        self.has = (bool(lay["has_genset"]), bool(lay["has_battery"]), bool(lay["has_grid"]))
+        self.oms = [oracle.OracleMicrogrid(p) for p in single_params(cols)]
+        self.dtype = np.dtype(oracle.StepOut)
+        self.N = len(self.oms)
+        self.action_dim = 2 * self.has[0] + self.has[1] + self.has[2]
+
+    def reset(self, rows):
+        """Moves every grid's counter (``rows``: one row, or [N]) and keeps the module state -> obs [N, D]."""
+        rows = np.broadcast_to(np.asarray(rows), (self.N,))
+        return np.stack([om.reset(int(t)) for om, t in zip(self.oms, rows)])
+
+    def set_rows(self, rows, only=None):
+        for j in (range(self.N) if only is None else np.flatnonzero(only)):
+            self.oms[j].s.t = int(rows[j])
+
+    def rows(self):
+        return np.array([om.s.t for om in self.oms])
+
+    def observe(self):
+        return np.stack([om.observe() for om in self.oms])
+
+    def _control(self, a):
+        """A control row (genset goal, genset energy, battery, grid: the ones the layout has) as ``run`` takes it."""
+        d, c = {}, 0
+        if self.has[0]:
+            d["genset"] = (a[0], a[1]); c = 2
+        if self.has[1]:
+            d["battery"] = a[c]; c += 1
+        if self.has[2]:
+            d["grid"] = a[c]
+        return d
+
+    def step(self, controls, normalized=True):
+        """One ``run`` of every grid (controls [N, A]) -> StepOut records [N]."""
+        rec = np.empty(self.N, dtype=self.dtype)
+        for j, om in enumerate(self.oms):
+            rec[j] = np.frombuffer(om.run(self._control(controls[j]), normalized), dtype=self.dtype, count=1)[0]
+        return rec
+
+    def run(self, controls, normalized=True, observe=False):
+        """K steps (controls [K, N, A]) -> records [K, N] (and the observation rows [K, N, D] behind every step)."""
+        recs, obs = [], []
+        for a in controls:
+            recs.append(self.step(a, normalized))
+            if observe:
+                obs.append(self.observe())
+        return (np.stack(recs), np.stack(obs)) if observe else np.stack(recs)
+
+    def expand(self, plists):
+        """``populate_action`` of every grid's list (``plists``: N lists of (module id, action)) -> raw controls [N, A]."""
+        out = np.zeros((self.N, self.action_dim))
+        for j, (om, pl) in enumerate(zip(self.oms, plists)):
+            d = om.populate_action([(KIND_NAMES[m], act) for m, act in pl])
+            out[j] = list(d.get("genset", [])) + [d[k] for k in ("battery", "grid") if k in d]
+        return out
+
+    def state(self):
+        """The state columns as the batch holds them: charge / soc [N], gen_status uint32 [N]."""
+        out = {}
+        if self.has[1]:
+            out["charge"] = np.array([om.s.charge for om in self.oms])
+            out["soc"] = np.array([om.s.soc for om in self.oms])
+        if self.has[0]:
+            out["gen_status"] = status_words(*np.array([om.status for om in self.oms]).T)
+        return out

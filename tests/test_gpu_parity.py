@@ -753,7 +753,9 @@ def test_random_fleet_every_module_set_vs_oracle(seed, device, oracle):
     """Device vs oracle over a random fleet that covers EVERY kernel specialisation: all 8 module sets (incl. genset-only,
     grid-only, genset+grid, battery-only, none), both battery / grid sweep orders, several load / renewable modules,
     horizons 0 / 3 / 24, lossy and degenerate batteries, genset timers and initial states, weak grids, raw and
-    out-of-range requests.  Bucketed by layout, 25 steps each: reward, done, state, observation and every log column."""
+    out-of-range requests.  Bucketed by layout, 25 steps each: reward, done, state, observation and every log column.
+    A grid on which the oracle raises the reference's AssertionError (an over-full lossy battery) is left out from there on: at most
+    10 % of the fleet, and of every module set at least one grid is compared to the end."""
     from pymgrid_amd import MicrogridBatch, StepEngine, unpack_status
     rs = np.random.RandomState(4242 + seed)
     T = 40
@@ -791,7 +793,9 @@ def test_random_fleet_every_module_set_vs_oracle(seed, device, oracle):
             p["controllable_order"] = ["grid", "battery"]
         grids.append(p)
     buckets = _buckets(grids)
-    assert len({(g.get("genset") is not None, g.get("battery") is not None, g.get("grid") is not None) for g in grids}) == 8
+    module_set = lambda g: (g.get("genset") is not None, g.get("battery") is not None, g.get("grid") is not None)   # noqa: E731
+    assert len({module_set(g) for g in grids}) == 8
+    left_out = []                                             # fleet indices of the grids the oracle gave up on
     for idx in buckets:
         sub = [grids[i] for i in idx]
         eng = StepEngine(MicrogridBatch.from_grids(sub, device=device))
@@ -863,7 +867,12 @@ def test_random_fleet_every_module_set_vs_oracle(seed, device, oracle):
                 assert cols["charge"][j].item() == om.s.charge and cols["soc"][j].item() == om.s.soc, idx[j]
             if L.has_genset:
                 assert unpack_status(cols["gen_status"][j:j + 1].cpu().numpy().view(np.uint32))[0].tolist() == list(om.status), idx[j]
+        left_out += [idx[j] for j, om in enumerate(oms) if om is None]
         eng.close()
+    assert len(left_out) <= 0.10 * len(grids), (len(left_out), len(grids))
+    left_out = set(left_out)
+    compared = {module_set(g) for i, g in enumerate(grids) if i not in left_out}
+    assert len(compared) == 8, sorted({module_set(g) for g in grids} - compared)
 
 
 def test_stream_shards_equal_one_engine(device):

@@ -2,11 +2,12 @@
 tests/test_layout_matrix_policy.py, tests/test_layout_matrix_whatif.py), checked without a GPU:
 layouts.carve gives every one of the ten layouts the fused kernels are compiled for, in both series forms, the CPU oracle replays
 each of them without leaving a grid out, the inputs tell the grid-first layouts from the battery-first ones and reach both genset
-forms of the loops -- and every instantiation of the twenty-three kernel families of ``enumerated()`` that the library holds (the
-open-loop fused kernels, the closed-loop policy kernels, the what-if kernels, the policy gradient, the hot K-step, and the eight
-families of the general path, tests/test_general_path_matrix.py) is a case of those matrices, or one of the forms a matrix file names
-as refused with the refusal asserted.  The inputs of the general-path matrix are checked here too: their ``provided`` lists reach
-the eight and nine addends from which the sum takes numpy's pairwise order, and they tell the two stepping orders apart."""
+forms of the loops -- and every instantiation of the thirty-seven kernel families of ``enumerated()`` that the library holds (the
+open-loop fused kernels, the closed-loop policy kernels, the what-if kernels, the policy gradient, the hot K-step, the eight
+families of the general path, tests/test_general_path_matrix.py, and the fourteen of the single-step path,
+tests/test_single_step_matrix.py, whose inputs are checked at the end of this file) is a case of those matrices, or one of the forms
+a matrix file names as refused with the refusal asserted.  The inputs of the general-path matrix are checked here too: their
+``provided`` lists reach the eight and nine addends from which the sum takes numpy's pairwise order, and they tell the two stepping orders apart."""
 import functools
 import re
 
@@ -252,6 +253,7 @@ def test_the_general_path_inputs_tell_grid_first_from_battery_first(battery_firs
 # ---- every compiled specialisation of the fused kernels is a case of a GPU matrix -----------------------------------------------
 SRC = {"factorised": 0, "materialised": 1, "gather": 2}      # EP_SRC_* of the episode kernels
 ARCH_FLAGS = {"genset+battery": 3, "battery+grid": 6, "genset+battery+grid": 7}
+UNTEMPLATED_FAMILIES = ("fleet_step_kernel",)               # no template: one instantiation, the empty compile-time part
 GENERAL_FAMILIES = ("step_multi_kernel", "step_k_multi_kernel", "step_k_multi_small_kernel", "rollout_multi_small_kernel",
                     "step_lists_small_kernel", "expand_multi_kernel", "check_multi_kernel", "observe_multi_kernel")
 
@@ -338,6 +340,15 @@ def enumerated():
     for case in general.CASES:
         for kernel, part in general.compiled_forms(*case):
             want[kernel].add(part)
+    # the single-step family: what the calls of every case of every table launch, by the rule stated beside the tables
+    import test_single_step_matrix as single
+    for kernel in single.FAMILIES:
+        want[kernel] = set()
+    for kind, cases in single.all_cases():
+        for case in cases:
+            for kernel, part in single.compiled_forms(kind, case):
+                want[kernel].add(part)
+    assert set(want) >= set(single.FAMILIES) and all(want[k] for k in single.FAMILIES)
     return want
 
 
@@ -347,8 +358,9 @@ def refused():
     import test_layout_matrix_policy as pol
     import test_layout_matrix_whatif as whatif
     import test_general_path_matrix as general
+    import test_single_step_matrix as single
     out = {}
-    for kernel, part in pol.REFUSED + whatif.REFUSED + general.REFUSED:
+    for kernel, part in pol.REFUSED + whatif.REFUSED + general.REFUSED + single.REFUSED:
         out.setdefault(kernel, set()).add(part)
     return out
 
@@ -356,9 +368,13 @@ def refused():
 def compile_time_part(name):
     """(kernel, compile-time part) of a demangled instantiation such as ``mgx::step_k_kernel<7, 8, double, false, true>``; the ring
     depths (U, UA) follow from the rest and are left out."""
-    m = re.fullmatch(r"(?:\w+::)*(\w+)<(.*)>", name.strip())
+    # (a kernel with internal linkage may carry its namespace in brackets; one that is no template has no argument list: the
+    #  pointer form of the fleet kernel, whose compile-time part is empty)
+    m = re.fullmatch(r"(?:(?:\w+|\(anonymous namespace\))::)*(\w+)(?:<(.*)>)?(?: \(\.\w+\))?", name.strip())
     if not m:
         return None, None
+    if m.group(2) is None:
+        return m.group(1), (() if m.group(1) in UNTEMPLATED_FAMILIES else None)
     kernel, args, depth = m.group(1), [""], 0
     for ch in m.group(2):                                    # split at the commas outside nested template arguments
         depth += (ch == "<") - (ch == ">")
@@ -401,6 +417,19 @@ def compile_time_part(name):
     if kernel in ("step_k_multi_small_kernel", "rollout_multi_small_kernel"):    # <F, CNT, M>
         return kernel, (args[0], args[1])
     if kernel in ("step_k_multi_kernel", "expand_multi_kernel", "check_multi_kernel", "observe_multi_kernel"):    # <F>
+        return kernel, (args[0],)
+    # the single-step family (tests/test_single_step_matrix.py)
+    if kernel in ("step_kernel", "step_discrete_kernel"):                        # <F, EP>
+        return kernel, (args[0], args[1])
+    if kernel in ("check_kernel", "check_discrete_kernel", "expand_kernel", "observe_kernel", "action_bounds_kernel"):    # <F>
+        return kernel, (args[0],)
+    if kernel == "obs_rows_wave_kernel":                                         # <F, NOISE, OT>
+        return kernel, (args[0], args[1], args[2])
+    if kernel in ("obs_windows_k_kernel", "obs_windows_k_multi_kernel"):         # <F, OT>
+        return kernel, (args[0], args[1])
+    if kernel in ("patch_windows_kernel", "normalise_series_kernel"):            # <GRID, OT>, <C, OT>
+        return kernel, (args[0], args[1])
+    if kernel == "fleet_step_kernel_v":                                          # <EP>
         return kernel, (args[0],)
     return kernel, None
 
@@ -478,3 +507,185 @@ def test_the_coverage_check_names_what_a_dropped_case_leaves_uncovered():
     for name in made_up:
         assert missing_cases(usage, {**full, family(name): set()}) == [name]
         assert missing_cases(usage, {**full, family(name): set()}, {family(name): {made_up[name]}}) == []
+    # ... and of the families of the single-step path (tests/test_single_step_matrix.py); the pointer form of the fleet kernel is no
+    # template: one instantiation, whose compile-time part is empty
+    made_up = {"mgx::step_kernel<14, true>": (14, True), "mgx::step_discrete_kernel<5, false>": (5, False), "mgx::check_kernel<6>": (6,),
+               "mgx::check_discrete_kernel<15>": (15,), "mgx::expand_kernel<1>": (1,), "mgx::observe_kernel<0>": (0,),
+               "mgx::action_bounds_kernel<2>": (2,), "mgx::obs_rows_wave_kernel<4, true, float>": (4, True, "float"),
+               "mgx::obs_windows_k_kernel<3, double>": (3, "double"), "mgx::obs_windows_k_multi_kernel<7, float>": (7, "float"),
+               "mgx::patch_windows_kernel<true, float>": (True, "float"), "mgx::normalise_series_kernel<4, double>": (4, "double"),
+               "mgx::fleet_step_kernel_v<true>": (True,), "mgx::fleet_step_kernel": (),
+               "(anonymous namespace)::fleet_step_kernel_v<false>": (False,)}
+    usage = dict.fromkeys(list(made_up) + ["mgx::fleet_step_kernel_vm", "mgx::gather_windows_kernel"], {})
+    assert len({family(name) for name in made_up}) == 14
+    assert all(compile_time_part(name) == (family(name), part) for name, part in made_up.items())
+    full = {}
+    for name, part in made_up.items():
+        full.setdefault(family(name), set()).add(part)
+    assert missing_cases(usage, full) == []
+    for name in made_up:
+        less = {**full, family(name): full[family(name)] - {made_up[name]}}
+        assert missing_cases(usage, less) == [name]
+        assert missing_cases(usage, less, {family(name): {made_up[name]}}) == []
+
+
+# ---- the inputs of the single-step matrix (tests/test_single_step_matrix.py) ------------------------------------------------------
+def test_the_columns_of_a_carved_batch_give_the_oracles_parameter_dicts():
+    """layouts.single_params on layouts 7 and 14: the dicts carry the battery's charge / soc, the genset's status counters and timers,
+    ``controllable_order`` (grid first on 14), horizon and final_step; an OracleMicrogrid of them, stepped, is the batch oracle's
+    replay of the same columns -- reward for reward -- and its state is what ``numpy_columns()`` held."""
+    import test_single_step_matrix as single
+    from layouts import OracleSingles, single_params
+    from oracle import oracle as orc
+    orc.build()
+    for flags in (7, 14):
+        cols = single.columns(flags, 3)
+        params = single_params(cols)
+        assert len(params) == single.N and all(p["horizon"] == 3 and p["final_step"] == single.T for p in params)
+        assert all(("genset" in p, "battery" in p, "grid" in p) == (bool(flags & 1), True, True) for p in params)
+        assert all(p["controllable_order"].index("grid") < p["controllable_order"].index("battery") for p in params) == (flags == 14)
+        assert [p["battery"]["charge"] for p in params] == cols["charge"].tolist() and [p["battery"]["soc"] for p in params] == cols["soc"].tolist()
+        og = OracleSingles(orc, cols)
+        for name, want in og.state().items():
+            assert np.array_equal(want, cols[name]), (flags, name)
+        if flags & 1:
+            times = cols["gen_times"]
+            assert [p["genset"]["start_up_time"] for p in params] == (times & 0xff).tolist()
+            assert [p["genset"]["wind_down_time"] for p in params] == ((times >> 16) & 0xff).tolist()
+            assert len(set((times & 0xff).tolist())) > 1, "mixed timers"
+        rs = np.random.RandomState(flags)
+        controls = rs.rand(8, single.N, og.action_dim)
+        og.reset(single.T0)
+        rec = og.run(controls, True)
+        st = _state(cols)
+        failed = np.zeros(single.N, dtype=np.uint8)
+        reward = orc.run_batch(cols, st, single.T0, 8, controls, normalized=True, failed=failed)
+        assert int(failed.sum()) == 0 and np.array_equal(rec["reward"], reward), flags
+        for name, want in og.state().items():
+            assert np.array_equal(want, st[name]), (flags, name)
+
+
+def _single_references():
+    import test_single_step_matrix as single
+    need = sorted({(case[0], 0, case[2]) for case in single.LOCKSTEP_CASES}
+                  | {(case[0], case[1], "double") for case in single.ROWS_CASES + single.RING_CASES + single.VIEW_CASES})
+    return need
+
+
+@pytest.mark.parametrize("flags,H,ctype", _single_references())
+def test_the_single_step_inputs_meet_their_conditions(flags, H, ctype):
+    """The reference side of every lock-step, row, ring and view case of the single-step matrix, run here without a GPU: the oracle
+    leaves out no grid (any exception fails), both values of ``done`` occur, every form of the genset status word occurs (off, on,
+    starting up, winding down), and with a horizon the windows of the last rows run into the padding behind the series --
+    ``lockstep_reference`` asserts all of it."""
+    import test_single_step_matrix as single
+    ref = single.lockstep_reference(flags, H, ctype)
+    assert ref["rec"].shape == (single.STEPS + single.TAIL, single.N)
+    assert ref["obs"].shape[2] == ref["obs0"].shape[1] == carve(single._full("materialised", H), flags).layout.obs_dim
+    assert ref["controls"].dtype == (np.float32 if ctype == "float" else np.float64)
+    assert ((ref["controls"] == 0) | (ref["controls"] == 1)).any() or flags == 0
+
+
+@pytest.mark.parametrize("flags", LAYOUTS)
+def test_the_general_path_ring_inputs_meet_their_conditions(flags):
+    """The reference side of the ring refill of the general path: no grid left out, the last step alone reports done, two instances
+    of a kind never share their parameters -- ``multi_reference`` asserts it."""
+    import test_single_step_matrix as single
+    ref = single.multi_reference(flags)
+    assert np.isfinite(ref["rec"]["reward"]).all() and np.isfinite(ref["obs"]).all()
+    assert ref["obs"].shape[:2] == (single.STEPS + single.TAIL, single.MULTI_N)
+
+
+@pytest.mark.parametrize("H", [0, 3])
+@pytest.mark.parametrize("flags", LAYOUTS)
+def test_the_single_step_discrete_inputs_meet_their_conditions(flags, H):
+    """... and of the discrete cases: no grid left out (an assert of ``populate_action`` fails here), the ids reach every list of the
+    layout, both genset goals occur, the last step alone reports done -- ``discrete_reference`` asserts it."""
+    import test_single_step_matrix as single
+    ref = single.discrete_reference(flags, H)
+    assert ref["control"].shape == (single.STEPS + single.TAIL, single.N, single.action_dim(flags))
+    assert np.isfinite(ref["rec"]["reward"]).all()
+
+
+def test_the_single_step_case_tables_are_complete():
+    """Every (layout, row type) of the row, ring and view tables sees one of the two horizons and every layout both; the episode table
+    holds every layout continuous and discrete with whole rows, and all four forms of the ring patch; every case names forms the
+    dispatch rule knows."""
+    import test_single_step_matrix as single
+    for table in (single.ROWS_CASES, single.RING_CASES, single.VIEW_CASES):
+        assert {(c[0], c[2]) for c in table} == {(f, ot) for f in LAYOUTS for ot in single.FLOATS}
+        assert all({c[1] for c in table if c[0] == f} == set(single.HORIZONS) for f in LAYOUTS)
+    # the fleet kernels pick the layout's step body by a run-time switch, one for continuous and one for discrete items: the compiled
+    # symbols cannot show a case label nobody runs, the table must -- every (kernel form, layout, discrete) triple, once
+    triples = [t for c in single.FLEET_CASES for t in single.fleet_triples(c)]
+    assert len(triples) == len(set(triples)) and set(triples) == {(form, f, d) for form in single.FLEET_KERNELS for f in LAYOUTS
+                                                                   for d in (False, True)}
+    assert all(len(fleet) <= 5 for fleet in single.FLEETS), "MGX_FLEET_MAX buckets share a launch"
+    assert {c[:3] for c in single.EPISODE_CASES if c[2] == 0} == {(f, d, 0) for f in LAYOUTS for d in (False, True)}
+    patched = {part for c in single.EPISODE_CASES for k, part in single.compiled_forms("episodes", c) if k == "patch_windows_kernel"}
+    assert patched == {(g, ot) for g in (False, True) for ot in single.FLOATS}
+    assert single.EPISODE_STEPS // single.LENGTH >= 2 and single.T - single.LENGTH > single.N // 16, "restarts on every grid, own rows"
+    assert single.N % single.BLOCK == 64 + 13 and single.N // single.BLOCK == 2 and single.N % 16 == 13
+    for kind, cases in single.all_cases():
+        assert len(set(cases)) == len(cases) and all(single.compiled_forms(kind, c) for c in cases), kind
+
+
+def _episode_inputs():
+    import test_single_step_matrix as single
+    return sorted({(c[0], c[2], c[1]) for c in single.EPISODE_CASES})
+
+
+@pytest.mark.parametrize("flags,H,discrete", _episode_inputs())
+def test_the_oracle_replays_the_first_episodes_of_the_episode_cases(flags, H, discrete):
+    """The oracle half of the episode and episode-fleet cases as far as it is known without a GPU: the first episodes start at rows
+    drawn on the host (``episode_starts``) and take the case's own draws; the oracle leaves out no grid (an exception fails), and with
+    one fixed length for every grid each of them is over -- and restarted -- after exactly LENGTH steps, EPISODE_STEPS // LENGTH times
+    in a case.  The rows of the later episodes are drawn on the device: an exception of the oracle there fails the GPU case."""
+    import test_single_step_matrix as single
+    from layouts import OracleSingles
+    from oracle import oracle as orc
+    orc.build()
+    og = OracleSingles(orc, single.columns(flags, H))
+    starts = single.episode_starts(flags)
+    assert starts.min() >= 0 and starts.max() + single.LENGTH <= single.T and len(np.unique(starts)) > 10
+    og.reset(starts)
+    draw, lists = single.episode_draws(flags, discrete), single.priority_lists(flags)
+    for k in range(single.LENGTH):
+        a = draw(k)
+        rec = og.step(og.expand([lists[i] for i in a]), False) if discrete else og.step(a, True)
+        assert np.isfinite(rec["reward"]).all()
+    assert np.array_equal(og.rows(), starts + single.LENGTH) and single.EPISODE_STEPS // single.LENGTH >= 2
+
+
+@pytest.mark.parametrize("flags", LAYOUTS)
+def test_the_raise_errors_golden_meets_its_conditions(flags):
+    """tests/golden/raise_errors.npz (make_raise_errors_goldens.py), re-asserted from the file: 16 grids and 24 steps per layout, half
+    of the grids raw; for every module kind of the layout at least 20 % of the (step, grid) pairs are refused (ValueError) and at
+    least 20 % accepted; every request exactly at the instantaneous limit is accepted and every one an ulp beyond it refused; the
+    recorded table is the layout's own enumeration of priority lists; the bounds are recorded where there is a battery / a grid."""
+    import test_single_step_matrix as single
+    from pymgrid_amd import MicrogridBatch
+    from pymgrid_amd.priority_list import table_array
+    g = single.raise_errors_golden(flags)
+    assert len(g["grids"]) == 16 and g["requests"].shape[:2] == (24, 16) and int(g["raw"].sum()) == 8
+    assert flags_of(MicrogridBatch.from_grids(g["grids"], device="cpu").layout) == flags
+    assert np.array_equal(g["table"], table_array(single.priority_lists(flags)))
+    assert 16 * single.GOLDEN_TILES // 2 == 336
+    for q in range(3):
+        exc, how = g["exception"][..., q], g["how"][..., q]
+        if not flags & (1 << q):
+            assert (exc == single.GOLDEN_ABSENT).all() and (g["list_exception"][..., q] == single.GOLDEN_ABSENT).all()
+            continue
+        refused = exc == single.GOLDEN_VALUE_ERROR
+        assert 0.2 <= refused.mean() <= 0.8, (flags, q, refused.mean())
+        assert np.isin(exc, (single.GOLDEN_NONE, single.GOLDEN_VALUE_ERROR, single.GOLDEN_ASSERTION_ERROR)).all()
+        at, beyond = how == single.GOLDEN_AT_LIMIT, how == single.GOLDEN_BEYOND
+        assert at[:, g["raw"]].any() and beyond[:, g["raw"]].any() and not at[:, ~g["raw"]].any() and not beyond[:, ~g["raw"]].any()
+        assert not refused[at].any(), (flags, q, "a request at the limit was refused")
+        assert refused[beyond].all(), (flags, q, "a request one ulp beyond the limit was accepted")
+        if q:
+            assert np.isfinite(g["bounds"][:, :, q - 1]).all()
+    if flags & 1:                                            # timers and both initial states among the gensets; weak grids below
+        assert len({(p["genset"]["start_up_time"], p["genset"]["wind_down_time"]) for p in g["grids"]}) > 4
+    if flags & 4:
+        assert any((p["grid_ts"][:, 3] == 0).any() for p in g["grids"])
